@@ -7,7 +7,11 @@ samples (sorted merge) -> fine MLP -> composite + per-pixel argmax point (nerf_t
 Everything is resident in HBM when the timed region starts; weights are seeded random (no dataset /
 checkpoint in the container); poses follow load_blender.py's pose_spherical.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures only the headline: the render group (the timed steps above). `--full` adds every other section
+(CPU baselines, training step, attack loop, 8-NN, split-precision render; with N > 1 the strong-scaling render leg and
+the sharded attack leg). `--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy.
 
 This file is the PARENT: it never imports numpy / torch and never touches the GPU. Every section group runs in a fresh
 child (`bench.py --child <group> --out <file>`, code in bench_sections.py) that appends result objects to <file> one JSON
@@ -37,6 +41,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 LINE_LIMIT = 1800                       # bytes; the driver's stdout tail is 2000 characters
 GROUP_OF = {'selftest': 'selftest', 'render': 'render', 'cpu': 'cpu', 'train': 'train', 'attack': 'attack', 'knn': 'extras', 'f16x3': 'extras'}
 GROUPS = ('selftest', 'render', 'cpu', 'train', 'attack', 'extras')
+FULL_SECTIONS = 'render,cpu,train,attack,knn,f16x3'
+PLAIN_SECTIONS = 'render'
 PG_TIMEOUT_S = 180                      # the children's process-group timeout (bench_sections.child_render reads it)
 
 
@@ -274,26 +280,41 @@ def parent_main(args, argv):
     sys.exit(0 if ok else 1)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='run every section (default sections %s; N > 1: also the strong-scaling and sharded attack legs); '
+                         'a plain run measures the render group only' % FULL_SECTIONS)
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the arrays the last timed render step returned (rank 0) to DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-attack', action='store_true', help='skip the extra train / attack / knn / f16x3 sections')
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL; default) or gloo (rehearsal on a 1-GPU box)')
     ap.add_argument('--device', type=int, default=None, help='force the HIP device index (rehearsal: all ranks on GPU 0)')
-    ap.add_argument('--sections', default='render,cpu,train,attack,knn,f16x3',
-                    help='comma list of render,cpu,train,attack,knn,f16x3 (the contract keys of the JSON line need render)')
+    ap.add_argument('--sections', default=None,
+                    help='comma list of render,cpu,train,attack,knn,f16x3 (the contract keys of the JSON line need render); '
+                         'default: %s, with --full or --child: %s' % (PLAIN_SECTIONS, FULL_SECTIONS))
     ap.add_argument('--child', default=None, choices=GROUPS, help='internal / profiling: run ONE section group in this process')
     ap.add_argument('--out', default=None, help='with --child: append result objects to this file instead of printing them')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.sections is None:             # a child runs the one group it was asked for, with all of that group's legs
+        args.sections = FULL_SECTIONS if args.full or args.child else PLAIN_SECTIONS
     args.section_set = set(x for x in args.sections.split(',') if x)
     unknown = args.section_set - set(GROUP_OF)
     if unknown:
         ap.error('unknown sections: %s' % ', '.join(sorted(unknown)))
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+def main():
+    args = parse_args()
     if args.child:
         import bench_sections
         bench_sections.run_child(args)

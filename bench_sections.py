@@ -931,6 +931,32 @@ def _emitter(path):
     return emit
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """`bench.py --dump-outputs DIR`: each array as DIR/<name>.npy, float32 (float64 and wide integers as float64), at most
+    `limit` bytes in all. Arrays that together exceed it are each cut to the same share of their flattened elements, picked
+    with seed 0, so that the dumps of two builds still compare element for element. -> {name: saved shape}."""
+    import numpy as _np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, 'detach') else _np.asarray(v)
+        wide = a.dtype in (_np.float64, _np.int32, _np.int64, _np.uint32, _np.uint64)
+        host[k] = a.astype(_np.float64 if wide else _np.float32)
+    total = sum(a.nbytes for a in host.values())
+    budget = limit - 256 * len(host)                         # room for the .npy headers
+    saved = {}
+    for k, a in sorted(host.items()):
+        if total > budget:
+            rs = _np.random.RandomState(0)
+            a = a.reshape(-1)[_np.unique(rs.randint(0, a.size, max(1, a.size * budget // total)))]
+        _np.save(os.path.join(path, k + '.npy'), a)
+        saved[k] = a.shape
+    return saved
+
+
 def _device(args):
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs an MI355X: torch.cuda.is_available() is False (no CPU path)')
@@ -1035,6 +1061,11 @@ def child_render(args, emit):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
     assert torch.isfinite(out[0]).all()
+    if rank == 0 and args.dump_outputs:
+        rgb, disp, acc, pts_max, extras = out
+        arrays = dict(rgb_map=rgb, disp_map=disp, acc_map=acc, pts_max=pts_max)
+        arrays.update(extras)
+        write_outputs(args.dump_outputs, arrays)
 
     # HBM traffic of the dominant kernel from the separate rocprofv3 --pmc passes of this same command (corrected as
     # MI355X_MICROARCH.md prescribes); profiles/ travels with the repo, the counters cannot be read from inside bench.py
@@ -1074,7 +1105,7 @@ def child_render(args, emit):
             'rccl_ranks': rccl_ranks,
         })
 
-    if world > 1 and not args.no_attack:
+    if world > 1 and args.full and not args.no_attack:
         # The legs hold collectives: an exception on ONE rank would leave the others waiting. Every rank reports its own
         # outcome, then all of them agree (MAX of an error flag) before anyone trusts the numbers.
         err = None

@@ -1,7 +1,8 @@
 """bench.py's parent process: it never imports torch, runs every section group in a fresh child, keeps what a child emitted
 before it died, prints ONE short contract line on stdout (< 1800 bytes: round 4's 20 KB line was truncated by the driver's
 capture and never parsed) and writes everything else to the detail file. `--gpus N` without a launcher spawns its own N
-ranks. CPU only: the `selftest` group has no GPU work, and NERFAIL_BENCH_FAKE_RENDER stands in for the render child."""
+ranks. CPU only but for the last test: the `selftest` group has no GPU work, and NERFAIL_BENCH_FAKE_RENDER stands in for the
+render child."""
 import json
 import os
 import subprocess
@@ -130,3 +131,55 @@ def test_parent_never_imports_torch():
 def test_unknown_section_is_refused():
     r = subprocess.run([sys.executable, BENCH, '--sections', 'nonsense'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=60)
     assert r.returncode != 0 and 'unknown sections' in r.stderr
+
+
+def test_plain_run_measures_the_render_group_only(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full starts the render child and nothing else."""
+    r, line, detail = run(tmp_path, {'NERFAIL_BENCH_FAKE_RENDER': FULL}, args=('--gpus', '1', '--steps', '4', '--warmup', '2'))
+    assert r.returncode == 0, r.stderr
+    assert set(detail['sections']) == {'render'}
+    assert line['steps'] == 4 and line['warmup'] == 2 and line['ms_per_step'] > 0
+
+
+def test_full_selects_every_section():
+    import bench
+    assert bench.parse_args([]).section_set == {'render'}
+    full = bench.parse_args(['--full'])
+    assert full.full and full.section_set == set(bench.GROUP_OF) - {'selftest'}
+    assert bench.parse_args(['--full', '--sections', 'render,knn']).section_set == {'render', 'knn'}
+    assert bench.parse_args(['--child', 'extras']).section_set == full.section_set       # a child group keeps all its legs
+    assert bench.parse_args(['--dump-outputs', 'x']).dump_outputs == 'x'
+
+
+def test_write_outputs_converts_and_caps(tmp_path):
+    import numpy as np
+    import torch
+    import bench_sections as B
+    small = {'a': torch.arange(6, dtype=torch.float16).reshape(2, 3), 'b': np.ones(4, bool), 'c': np.arange(3, dtype=np.float64)}
+    assert B.write_outputs(str(tmp_path / 's'), small) == {'a': (2, 3), 'b': (4,), 'c': (3,)}
+    a, b, c = (np.load(str(tmp_path / 's' / (k + '.npy'))) for k in 'abc')
+    assert a.dtype == np.float32 and b.dtype == np.float32 and c.dtype == np.float64
+    assert np.array_equal(a, np.arange(6).reshape(2, 3)) and np.array_equal(b, np.ones(4))
+    big = {'x': np.random.RandomState(1).rand(3000, 1000).astype(np.float32), 'y': np.zeros((1000, 1000))}      # 20 MB
+    s1 = B.write_outputs(str(tmp_path / 'b1'), big, limit=4 * 10 ** 6)
+    s2 = B.write_outputs(str(tmp_path / 'b2'), big, limit=4 * 10 ** 6)
+    assert s1 == s2 and len(s1['x']) == 1 and 0 < s1['x'][0] < 3000 * 1000
+    assert sum(os.path.getsize(str(tmp_path / 'b1' / f)) for f in os.listdir(str(tmp_path / 'b1'))) <= 4 * 10 ** 6
+    assert np.array_equal(np.load(str(tmp_path / 'b1' / 'x.npy')), np.load(str(tmp_path / 'b2' / 'x.npy')))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_render(rank_launcher, tmp_path):
+    """The real render child (started by the clean launcher): --dump-outputs writes what the last timed step returned."""
+    out = tmp_path / 'out'
+    rep = rank_launcher(BENCH, 1, ['--gpus', '1', '--steps', '1', '--warmup', '0', '--dump-outputs', str(out)], timeout=300,
+                        env={'NERFAIL_BENCH_DETAIL': str(tmp_path / 'detail.json')})
+    log = rep['logs'][0]
+    assert rep['rc'] == [0], log
+    line = json.loads([ln for ln in log.splitlines() if ln.startswith('{"metric"')][-1])
+    assert line['steps'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+    import numpy as np
+    rgb, pts = np.load(str(out / 'rgb_map.npy')), np.load(str(out / 'pts_max.npy'))
+    assert rgb.shape == (800, 800, 3) and rgb.dtype == np.float32 and np.isfinite(rgb).all()
+    assert pts.shape == (800, 800, 3) and (out / 'acc_map.npy').exists() and (out / 'rgb0.npy').exists()
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10 ** 6

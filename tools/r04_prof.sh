@@ -25,5 +25,5 @@ echo "counter passes done"
 python3 tools/pmc_summary.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} --kernel-trace -- python3 bench.py --child {render|train|attack} --steps 1 --warmup 0 (NERFAIL_BENCH_LIGHT=1)" > $O/pmc_hbm_traffic.json || exit 1
 find $O -name "*.db" -delete; find $O -name "*kernel_trace.csv" -delete; find $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE -name "*counter_collection.csv" -delete
 cp $O/pmc_hbm_traffic.json profiles/r04_pmc_hbm_traffic.json
-timeout -k 10 420 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 420 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 tail -c 300 $O/bench_default.json
