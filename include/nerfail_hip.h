@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 7
+#define NERFAIL_ABI_VERSION 8
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -121,7 +121,10 @@ int nerfail_mlp_fwd(const float* packed, int D, int W, int skip, const float* pt
 /* Which kernel serves nerfail_mlp_fwd / nerfail_mlp_fwd_embedded: 0 = automatic (default: the LDS-streaming kernel for
  * even depths <= 8, else the register-streamed one), 1 = register-streamed (mlp.hip), 2 = LDS-streaming (mlp_lds.hip;
  * shapes it does not cover return NERFAIL_EINVAL). Both compute the same f32 FMA chains in the same order; the switch
- * exists for A/B timing and for the parity test of one against the other. Process-wide; returns the previous value. */
+ * exists for A/B timing and for the parity test of one against the other. 3 = the bf16x3 kernel (mlp_x3.hip) for the x3
+ * entry points below (an error where it does not cover the shape; the other entry points select automatically). Under 0 the
+ * x3 entry points use it wherever it covers the shape. Initial value from NERFAIL_FWD_KERNEL=reg|lds|x (read once).
+ * Process-wide; returns the previous value. */
 int nerfail_mlp_fwd_select(int which);
 
 /* Which kernel serves nerfail_mlp_bwd_data / nerfail_mlp_bwd_data2: 0 = automatic (default: the LDS-ring kernel for W = 256 and
@@ -133,6 +136,22 @@ int nerfail_mlp_bwd_select(int which);
 /* NeRF.forward on an already embedded batch x[M, 63+27] (RH:100-123 as a standalone call). */
 int nerfail_mlp_fwd_embedded(const float* packed, int D, int W, int skip, const float* x, int64_t M,
                              float* raw, void* stream);
+
+/* ---- bf16x3 inference: same contracts as nerfail_mlp_fwd / _fwd_embedded / _fwd_rays, f32-accurate, not bitwise ----------
+ * Every f32 product as six bf16 products (hi/mid/lo round-to-nearest split of both operands, the three smallest cross terms
+ * dropped: about 2^-26 |a||b| per product). Covers W = 256 at even depths <= 8 (nerfail_mlp_packed_x3_bytes returns 0 for
+ * other shapes). `x3`: nerfail_mlp_packed_x3_bytes() bytes, filled on the device by nerfail_mlp_pack_x3 from the f32 image
+ * `packed`, which the kernel still reads for the biases and heads. The entry points run the bf16x3 kernel under the
+ * automatic selection when x3 is non-NULL and the shape is covered (and, for _rays, acts is NULL); otherwise exactly the
+ * path of the f32 entry point. */
+size_t nerfail_mlp_packed_x3_bytes(int D, int W, int skip);
+int nerfail_mlp_pack_x3(const float* packed, int D, int W, int skip, void* x3, void* stream);
+int nerfail_mlp_fwd_x3(const float* packed, const void* x3, int D, int W, int skip, const float* pts, const float* viewdirs,
+                       int64_t M, int samples_per_ray, float* raw, void* stream);
+int nerfail_mlp_fwd_embedded_x3(const float* packed, const void* x3, int D, int W, int skip, const float* x, int64_t M,
+                                float* raw, void* stream);
+int nerfail_mlp_fwd_rays_x3(const float* packed, const void* x3, int D, int W, int skip, const float* rays,
+                            const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream);
 
 /* ---- split-precision ("f16x3") forward: same contract as nerfail_mlp_fwd, fp32-equivalent results --------
  * Every product a*w is evaluated as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on the fp16 matrix cores with fp32

@@ -27,7 +27,8 @@ CFLAGS = ['-O3', '--offload-arch=' + ARCH, '-fPIC', '-std=c++17', '-ffp-contract
 # per-file flags. mlp_lds.hip: its fully unrolled layer loops (32 quads x 32 pinned MFMAs, some as inline asm) exceed the
 # size up to which hipcc honours '#pragma unroll' (16 384); not unrolled, the accumulator arrays would be indexed at run time
 # and live in scratch.
-FILE_FLAGS = {'mlp_lds.hip': ['-mllvm', '-pragma-unroll-threshold=65536']}
+FILE_FLAGS = {'mlp_lds.hip': ['-mllvm', '-pragma-unroll-threshold=65536'],
+              'mlp_x3.hip': ['-mllvm', '-pragma-unroll-threshold=65536']}   # (the same for the bf16x3 kernel)
 
 
 def _sources():

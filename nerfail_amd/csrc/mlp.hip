@@ -27,6 +27,11 @@
 
 namespace nerfail {
 
+bool mlp_x3_covers(const MlpLayout& L, int W);                                      // mlp_x3.hip
+size_t mlp_x3_bytes(const MlpLayout& L, int W);
+int pack_mlp_x3(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s);
+int launch_mlp_x3(const MlpArgs& a, const void* img, int W, hipStream_t s);
+
 // ------------------------------------------------------------------------------------- packing
 // One launch per MFMA layer: writes the A-fragment image [quad][tile][lane][4] and the bias image.
 __global__ void pack_layer_kernel(const float* __restrict__ w, const float* __restrict__ b, int out_f, int in_f,
@@ -322,7 +327,12 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_kernel(MlpArgs a) {
 // Inference goes to the LDS-streaming kernel (mlp_lds.hip) when it covers the shape (even depth <= 8); the training
 // forward (activations saved) and the other shapes run the register-streamed kernel below. nerfail_mlp_fwd_select /
 // NERFAIL_FWD_KERNEL=reg|lds force one of them (A/B timing, parity test of one against the other).
-static int g_fwd_select = [] { const char* e = getenv("NERFAIL_FWD_KERNEL"); return e ? (e[0] == 'r' ? 1 : (e[0] == 'l' ? 2 : 0)) : 0; }();
+// The x3 entry points (nerfail_mlp_fwd_x3 and kin) run the bf16x3 kernel (mlp_x3.hip) under the automatic selection when it
+// covers the shape; NERFAIL_FWD_KERNEL=x forces it there, =reg / =lds force the exact-f32 kernels everywhere.
+static int g_fwd_select = [] {
+    const char* e = getenv("NERFAIL_FWD_KERNEL");
+    return e ? (e[0] == 'r' ? 1 : (e[0] == 'l' ? 2 : (e[0] == 'x' ? 3 : 0))) : 0;
+}();
 static bool use_lds_kernel(const MlpArgs& a) {
     if (g_fwd_select == 1) return false;
     if (g_fwd_select == 2) return true;
@@ -351,13 +361,25 @@ static int launch_mlp(const MlpArgs& a, int W, hipStream_t s) {
     return NERFAIL_OK;
 }
 
+// x3 entry points: the bf16x3 kernel for inference when the selection allows it and it covers the shape, else exactly
+// launch_mlp. Forced ('x') on a shape it does not cover, or without an image, is an error.
+static int launch_mlp_x3_or(const MlpArgs& a, const void* img, int W, hipStream_t s) {
+    if (a.acts == nullptr && (g_fwd_select == 0 || g_fwd_select == 3)) {
+        if (g_fwd_select == 3 || (img != nullptr && mlp_x3_covers(a.lay, W))) {
+            if (img == nullptr) { set_error("nerfail_mlp_fwd_x3: NERFAIL_FWD_KERNEL=x without a bf16x3 image"); return NERFAIL_EINVAL; }
+            return launch_mlp_x3(a, img, W, s);
+        }
+    }
+    return launch_mlp(a, W, s);
+}
+
 }  // namespace nerfail
 
 using namespace nerfail;
 
 extern "C" int nerfail_mlp_fwd_select(int which) {
     const int prev = g_fwd_select;
-    if (which >= 0 && which <= 2) g_fwd_select = which;
+    if (which >= 0 && which <= 3) g_fwd_select = which;
     return prev;
 }
 
@@ -496,4 +518,54 @@ extern "C" int nerfail_mlp_fwd_rays(const float* packed, int D, int W, int skip,
     a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = nullptr; a.rays = rays; a.z = z_vals; a.raw = raw; a.acts = acts;
     a.M = M; a.spr = samples_per_ray;
     return launch_mlp(a, W, as_stream(stream));
+}
+
+// ---- bf16x3 inference (mlp_x3.hip): the weight stream split once into three bf16 planes; each entry point takes both images
+extern "C" size_t nerfail_mlp_packed_x3_bytes(int D, int W, int skip) {
+    MlpLayout L;
+    return make_layout(D, W, skip, L) ? mlp_x3_bytes(L, W) : 0;
+}
+
+extern "C" int nerfail_mlp_pack_x3(const float* packed, int D, int W, int skip, void* out, void* stream) {
+    MlpLayout L;
+    NF_REQUIRE(make_layout(D, W, skip, L), "unsupported (D, W)");
+    NF_REQUIRE(packed != nullptr && out != nullptr, "NULL pointer");
+    return pack_mlp_x3(packed, L, W, out, as_stream(stream));
+}
+
+extern "C" int nerfail_mlp_fwd_x3(const float* packed, const void* x3, int D, int W, int skip, const float* pts,
+                                  const float* viewdirs, int64_t M, int samples_per_ray, float* raw, void* stream) {
+    NF_REQUIRE(M >= 0, "M is negative");
+    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
+    MlpArgs a;
+    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
+    if (M == 0) return NERFAIL_OK;
+    NF_REQUIRE(packed != nullptr && pts != nullptr && viewdirs != nullptr && raw != nullptr, "NULL pointer");
+    a.packed = packed; a.pts = pts; a.viewdirs = viewdirs; a.xemb = nullptr; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = nullptr; a.M = M; a.spr = samples_per_ray;
+    return launch_mlp_x3_or(a, x3, W, as_stream(stream));
+}
+
+extern "C" int nerfail_mlp_fwd_embedded_x3(const float* packed, const void* x3, int D, int W, int skip, const float* x, int64_t M,
+                                           float* raw, void* stream) {
+    NF_REQUIRE(M >= 0, "M is negative");
+    MlpArgs a;
+    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
+    if (M == 0) return NERFAIL_OK;
+    NF_REQUIRE(packed != nullptr && x != nullptr && raw != nullptr, "NULL pointer");
+    a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = x; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = nullptr; a.M = M; a.spr = 1;
+    return launch_mlp_x3_or(a, x3, W, as_stream(stream));
+}
+
+extern "C" int nerfail_mlp_fwd_rays_x3(const float* packed, const void* x3, int D, int W, int skip, const float* rays,
+                                       const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
+    NF_REQUIRE(n_rays >= 0, "n_rays is negative");
+    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
+    MlpArgs a;
+    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
+    const int64_t M = n_rays * samples_per_ray;
+    if (M == 0) return NERFAIL_OK;
+    NF_REQUIRE(packed != nullptr && rays != nullptr && z_vals != nullptr && raw != nullptr, "NULL pointer");
+    a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = nullptr; a.rays = rays; a.z = z_vals; a.raw = raw; a.acts = acts;
+    a.M = M; a.spr = samples_per_ray;
+    return launch_mlp_x3_or(a, x3, W, as_stream(stream));
 }

@@ -23,13 +23,9 @@
 //   * biases and the two thin heads live in a constant LDS area loaded once per workgroup.
 // Bound: f32 MFMA (157.3 TFLOP/s dense); 1 186 816 FLOP per sample (D8 W256). LDS: 12*NT KB ring + 14 KB constants + 48 KB parked operands.
 #include <type_traits>
-#include "mlp_layout.h"
+#include "mlp_lds.h"
 
 namespace nerfail {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
 
 #ifndef NF_LDS_SPREAD
 #define NF_LDS_SPREAD 1     // 1: one piece of side work per MFMA shadow (WRing::step, inference kernels); 0: round-2 form
@@ -66,8 +62,6 @@ typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
 #define NF_LDS_GPM 4        // pieces per ring group = NF_LDS_GPM * NT (4: one barrier per 4 quads of a W-wide layer)
 #endif
 
-template <int N> __device__ __forceinline__ void lds_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ f32x4 lds_read4(const float* p) { return *(lds_cf4*)p; }
 
 template <int NT>
 struct LdsCfg {
@@ -416,13 +410,6 @@ __device__ __forceinline__ void lds_part(Ring& st, f32x16 (&acc)[NIN], Hook hook
     }
 }
 
-// max(x, 0) as ONE integer instruction on the bit pattern (negative floats are negative integers; -0 -> +0). fmaxf costs
-// two: hipcc first canonicalises an accumulator value (v_max x, x) before the IEEE-mode v_max with 0.
-__device__ __forceinline__ float relu_bits(float x) {
-    const int i = __float_as_int(x);
-    return __int_as_float(i > 0 ? i : 0);
-}
-
 // ---- training stores. Written as inline asm in the "SGPR base + 32-bit lane offset + immediate" form: ONE VGPR (the lane's
 // offset inside a slot) serves every saved value of the kernel. Left to hipcc, each destination became a 64-bit per-lane
 // pointer pair that was hoisted and spilled, and a scratch reload drains the LDS-DMA queue (vmcnt retires in order).
@@ -435,59 +422,6 @@ __device__ __forceinline__ void st_acc_reg(const float* sbase, unsigned voff, in
 // the 16 ReLU bits of one accumulator tile: entry's [64 lanes][4 dwords] image, tile t = 16-bit field t of the lane
 __device__ __forceinline__ void st_mask16(const float* sentry, unsigned vlane16, int t, unsigned bits) {
     asm volatile("global_store_short %0, %1, %2 offset:%3" ::"v"(vlane16), "v"(bits), "s"(sentry), "i"(2 * t) : "memory");
-}
-
-// dot product of a thin head's weights (LDS, accumulator order [OT][2][16]) with relu(x): VALU + one cross-half shuffle.
-// One tile at a time (sched_barrier): left alone, hipcc reads all 128 accumulators into VGPRs first and the register
-// allocator answers by spilling the positional encodings across the whole layer loop.
-template <int OT, int NIN>
-__device__ __forceinline__ float lds_head(const f32x16 (&x)[NIN], const float* w, int h) {
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < OT; ++t) {
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const f32x4 wv = lds_read4(w + (t * 2 + h) * 16 + 4 * r4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = x[t][4 * r4 + e];
-                asm("" : "+v"(v));     // opaque copy: otherwise hipcc shares these ReLUs with the next layer's operand
-                                       // preparation and keeps all 128 results alive in between (spills)
-                s = fmaf(wv[e], relu_bits(v), s);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return s + __shfl_xor(s, 32, 64);
-}
-
-// Three heads over the same input (rgb_linear's three rows): every accumulator register is read ONCE (round 5: three calls of
-// lds_head moved each of the 64 registers to a VGPR three times - an accumulator read goes through the matrix pipe, ~13 cycles).
-// Each sum is the same fma chain in the same order as lds_head's: the bits do not change.
-template <int OT, int NIN>
-__device__ __forceinline__ void lds_head3(const f32x16 (&x)[NIN], const float* w, int stride, int h, float (&out)[3]) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < OT; ++t) {
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const float* p = w + (t * 2 + h) * 16 + 4 * r4;
-            const f32x4 w0 = lds_read4(p), w1 = lds_read4(p + stride), w2 = lds_read4(p + 2 * stride);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = x[t][4 * r4 + e];
-                asm("" : "+v"(v));
-                v = relu_bits(v);
-                s0 = fmaf(w0[e], v, s0);
-                s1 = fmaf(w1[e], v, s1);
-                s2 = fmaf(w2[e], v, s2);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    out[0] = s0 + __shfl_xor(s0, 32, 64);
-    out[1] = s1 + __shfl_xor(s1, 32, 64);
-    out[2] = s2 + __shfl_xor(s2, 32, 64);
 }
 
 // SKIP: where the skip connection's extra part is compiled in: 0 nowhere, 1 first / 2 second layer of a pair.

@@ -109,6 +109,8 @@ class NeRF(nn.Module):
         self._packed_key = None
         self._packed16 = None
         self._packed16_key = None
+        self._packed_x3 = None
+        self._packed_x3_key = None
         # 'f32' : exact-f32 MFMA kernel (default).  'f16x3': split-precision fp16 MFMA kernel, fp32-equivalent
         # results (each product as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi with fp32 accumulation), inference only.
         self.precision = 'f32'
@@ -151,6 +153,23 @@ class NeRF(nn.Module):
         buf = torch.empty((n,), dtype=torch.float32, device=params[0].device)
         _lib.check(lib.nerfail_mlp_pack(mp, _lib.dev(buf), _lib.stream()))
         self._packed, self._packed_key = buf, key
+        return buf
+
+    def packed_x3(self):
+        """bf16x3 weight image of the inference kernel (nerfail_mlp_pack_x3, split on the device from packed()), cached and
+        invalidated like packed(). None for shapes the bf16x3 kernel does not cover: the x3 entry points then run the f32 path."""
+        f32 = self.packed()
+        params = list(self.parameters())
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if self._packed_x3_key == key:
+            return self._packed_x3
+        lib = _lib.load()
+        n = lib.nerfail_mlp_packed_x3_bytes(self.D, self.W, self._skip())
+        buf = None
+        if n:
+            buf = torch.empty((n,), dtype=torch.uint8, device=f32.device)
+            _lib.check(lib.nerfail_mlp_pack_x3(_lib.dev(f32), self.D, self.W, self._skip(), _lib.dev(buf), _lib.stream()))
+        self._packed_x3, self._packed_x3_key = buf, key
         return buf
 
     def _mlp_params(self, keep):
@@ -240,8 +259,9 @@ class NeRF(nn.Module):
         assert x.shape[-1] == self.input_ch + self.input_ch_views
         flat = x.reshape(-1, x.shape[-1])
         out = torch.empty((flat.shape[0], 4), dtype=torch.float32, device=flat.device)
-        _lib.check(_lib.load().nerfail_mlp_fwd_embedded(_lib.dev(self.packed()), self.D, self.W, self._skip(),
-                                                        _lib.dev(flat, 'x'), flat.shape[0], _lib.dev(out), _lib.stream()))
+        _lib.check(_lib.load().nerfail_mlp_fwd_embedded_x3(_lib.dev(self.packed()), _lib.dev(self.packed_x3()), self.D, self.W,
+                                                           self._skip(), _lib.dev(flat, 'x'), flat.shape[0], _lib.dev(out),
+                                                           _lib.stream()))
         return out.reshape(x.shape[:-1] + (4,))
 
 
