@@ -7,20 +7,27 @@
 // is exact in f32, and what is dropped (a1b2 + a2b1 + a2b2 and the residuals) adds up to about 2^-26 |a||b|, below one
 // f32 rounding. The result is f32-accurate, not bitwise that of the exact-f32 kernel (mlp_lds.hip) - any reordering of
 // an f32 sum differs in the last bits as well. bf16 has the f32 exponent range: no pre-scale, no weight-range limit.
-// Cost per 32x32x16 f32-equivalent: 6 v_mfma_f32_32x32x16_bf16 (6 x 32 cycles) against 8 v_mfma_f32_32x32x2_f32 (8 x 64).
+// Cost per 32x32x16 f32-equivalent: 12 v_mfma_f32_16x16x32_bf16 (12 x 16 cycles) against 8 v_mfma_f32_32x32x2_f32 (8 x 64).
+// The 16x16x32 shape takes the cycles per FLOP of the 32x32x16 one, but the chip holds a higher clock under it on random
+// operands re-read from LDS (tools/clockprobe/mfma_clock.hip: 1.09x the FLOP/s at this kernel's LDS bytes per FLOP).
 //
 // Structure: that of nerf_mlp_fwd_lds_kernel (mlp_lds.hip) - one wave per SIMD, 32 samples x all channels per wave, every
-// layer transposed (the 32x32 accumulator tile of one layer is the B operand of the next), the weight stream shared by
-// the 4 waves of a workgroup through an LDS-DMA ring with one barrier per group, running across layer boundaries; biases
-// and the thin alpha / rgb heads in a constant LDS area (f32, computed exactly as there); encoding in the kernel.
+// layer transposed (the accumulator tiles of one layer are the B operand of the next), the weight stream shared by the 4
+// waves of a workgroup through an LDS-DMA ring with one barrier per group, running across layer boundaries; biases and
+// the thin alpha / rgb heads in a constant LDS area (f32, computed exactly as there); encoding in the kernel.
+//   * accumulators: per 16-row out tile two 16x16 tiles, one per sample half n (samples 16n + (lane & 15)); lane group
+//     g = lane >> 4 holds rows 4g .. 4g+3 of both. 16 out tiles x 2 halves x 4 registers = 128 per activation array.
 //   * A operand: the bf16x3 image (nerfail_mlp_pack_x3, split ONCE on the device from the f32 image), laid out per layer as
-//     [k16 step][out tile][plane][lane][8 bf16]: one 1 KB piece = the fragment of one (step, tile, plane).
-//   * B operand: registers 8s'..8s'+7 of an accumulator tile are the k order of one 32x32x16 step (the pack puts the
-//     weights in that order). The ReLU is applied lazily where an operand is consumed; each k16 chunk is split ONCE, one
-//     step ahead, and serves all 8 out tiles (4 in the views layer).
-//   * one "tile-step" = the 6 MFMAs of one (k16 step, out tile) with its 3 pieces; ring group = 8 tile-steps = 24 pieces,
-//     4 groups in the ring (96 KB). Fragments are read two tile-steps ahead, so the group boundary sits at the group's
-//     second-to-last tile-step (both remaining tile-steps' fragments are in registers when the slot is released).
+//     [k32 step][16-row out tile][plane][lane][8 bf16]: one 1 KB piece = the fragment of one (step, tile, plane); lane l
+//     holds row l & 15 of the tile and k positions 8(l >> 4) .. +7 of the step.
+//   * B operand: element j of lane group g in k32 step u is channel 32u + 4g + (j & 3) + 16(j >> 2), i.e. registers 0..3 of
+//     out tiles 2u and 2u+1 of the layer before - no lane movement (the pack permutes the weights' k index to match). The
+//     ReLU is applied lazily where an operand is consumed; each k32 step is split ONCE, one step ahead, and serves all 16
+//     out tiles (8 in the views layer).
+//   * one "tile-step" = the 12 MFMAs of one (k32 step, out tile): 6 products x 2 sample halves, with its 3 pieces; ring
+//     group = 8 tile-steps = 24 pieces, 4 groups in the ring (96 KB). Fragments are read two tile-steps ahead, so the group
+//     boundary sits at the group's second-to-last tile-step (both remaining tile-steps' fragments are in registers when
+//     the slot is released).
 #include "mlp_lds.h"
 
 namespace nerfail {
@@ -33,7 +40,8 @@ typedef __attribute__((address_space(3))) const u32x4 lds_cu4;
 typedef __attribute__((address_space(3))) const f32x2 lds_cf2;
 
 struct X3Cfg {
-    static constexpr int NT = 8;                 // W = 256 only
+    static constexpr int NT = 8;                 // W = 256 only (32-row tiles of the f32 image)
+    static constexpr int OT = 2 * NT;            // 16-row out tiles
     static constexpr int GP = 24;                // pieces per ring group: 8 tile-steps x 3 planes
     static constexpr int S = 4;                  // groups in the ring
     static constexpr int RP = GP * S;            // ring pieces (96 KB)
@@ -61,9 +69,9 @@ static inline bool make_x3_layout(const MlpLayout& L, int W, X3Layout& X) {
     for (int l = 0; l <= L.D + 1; ++l) {
         const unsigned OT = (l == L.D + 1) ? L.NT / 2 : L.NT;
         const unsigned quads = L.w_count[l] / (OT * kPiece);
-        if (quads & 1) return false;
+        if (quads & 3) return false;
         X.off[l] = off;
-        off += quads / 2 * OT * 3;
+        off += quads / 4 * (2 * OT) * 3;                           // [k32 step][16-row out tile][plane]
     }
     X.pieces = off;
     return off % X3Cfg::GP == 0;
@@ -78,7 +86,11 @@ __device__ __forceinline__ void sub_bf2(float& x0, float& x1, unsigned p) {     
     x1 -= __uint_as_float(p & 0xffff0000u);
 }
 
-// ---- the bf16x3 image from the f32 image: one thread per (layer step, tile, lane), 8 weights -> 3 x 16 bytes
+// ---- the bf16x3 image from the f32 image: one thread per (layer step, tile, lane), 8 weights -> 3 x 16 bytes.
+// The f32 image holds layer l as [quad Q][32-row tile][lane32][4]: weight (row i, k-step 4Q + e) of half h at lane32
+// i + 32h, element e; for a hidden part, (Q, e, h) is channel 32(Q / 4) + acc_channel(4(Q % 4) + e, h). Element j of lane
+// group g in k32 step u is (Q, e, h) = (4u + (g >> 1) + 2(j >> 2), j & 3, g & 1): channel 32u + 4g + (j & 3) + 16(j >> 2).
+// The encoding parts (whole k32 steps too) take the same map; the kernel's parked-operand reader follows it.
 struct X3PackArgs {
     MlpLayout L;
     X3Layout X;
@@ -90,12 +102,14 @@ __global__ void pack_x3_kernel(const float* __restrict__ packed, X3PackArgs p, u
     if (ts * 3 >= p.X.pieces) return;
     int l = 0;
     while (l < p.L.D + 1 && ts * 3 >= p.X.off[l + 1]) ++l;
-    const int OT = (l == p.L.D + 1) ? p.L.NT / 2 : p.L.NT;
+    const int OT32 = (l == p.L.D + 1) ? p.L.NT / 2 : p.L.NT, OT16 = 2 * OT32;
     const long r = ts - p.X.off[l] / 3;
-    const int s = (int)(r / OT), t = (int)(r % OT);
-    const float* w = packed + p.L.w_off[l] + lane * 4;
-    const f32x4 q0 = *reinterpret_cast<const f32x4*>(w + ((2 * s) * OT + t) * kPiece);
-    const f32x4 q1 = *reinterpret_cast<const f32x4*>(w + ((2 * s + 1) * OT + t) * kPiece);
+    const int u = (int)(r / OT16), t = (int)(r % OT16);
+    const int row = 16 * t + (lane & 15), lg = lane >> 4;          // out channel; lane group
+    const int q = 4 * u + (lg >> 1);
+    const float* w = packed + p.L.w_off[l] + (row >> 5) * kPiece + ((row & 31) + 32 * (lg & 1)) * 4;
+    const f32x4 q0 = *reinterpret_cast<const f32x4*>(w + (q * OT32) * kPiece);
+    const f32x4 q1 = *reinterpret_cast<const f32x4*>(w + ((q + 2) * OT32) * kPiece);
     float x[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
     u32x4 hi, mid, lo;
 #pragma unroll
@@ -124,7 +138,7 @@ struct X3Ring {
     float* ring;                     // LDS ring base
     const float* rl;                 // ring + lane * 4
     int total;                       // stream length in pieces (multiple of GP)
-    int src, slot, rd, wave;         // next group's first source piece, its ring group, next ring piece to read
+    int src, slot, rd, wave;         // next group's first source piece, its ring group, first ring piece of the group read next
     u32x4 f1[3], f2[3];              // fragments of the next two tile-steps
 
     template <int I>
@@ -152,9 +166,10 @@ struct X3Ring {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
-    __device__ __forceinline__ u32x4 frag(int p) const { return *(lds_cu4*)(rl + (rd + p) * kPiece); }
-    __device__ __forceinline__ void advance() {
-        rd += 3;
+    // plane p of the tile-step at position POS (mod SPG) of the group read next: a constant offset from one address per group
+    __device__ __forceinline__ u32x4 frag(int POS, int p) const { return *(lds_cu4*)(rl + (rd + 3 * POS + p) * kPiece); }
+    __device__ __forceinline__ void next_group() {
+        rd += C::GP;
         if (rd >= C::RP) rd = 0;
     }
     // S-1 groups issued, group 0 readable; then the state right behind a boundary tile-step that sat two tile-steps before
@@ -170,100 +185,163 @@ struct X3Ring {
         dma(0);
         dma(1);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) f1[p] = frag(p);
-        advance();
+        for (int p = 0; p < 3; ++p) f1[p] = frag(0, p);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) f2[p] = frag(p);
-        advance();
+        for (int p = 0; p < 3; ++p) f2[p] = frag(1, p);
     }
 };
 
-__device__ __forceinline__ void mfma_x3(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+__device__ __forceinline__ void mfma_x3(f32x4& acc, const u32x4& a, const u32x4& b) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 }
 
-// One tile-step at stream position POS (mod SPG, a constant after unrolling): the six MFMAs of out tile `acc`, smallest
-// product first, each with ONE piece of side work in its shadow: MFMA 0 the refill DMA, MFMAs 1..3 a fragment read of the
-// tile-step two ahead, side(k) behind MFMA k (operand preparation, bias tiles).
+// Index of channel 16t + 4g + i (i = 0..3) in a bias piece or thin head, stored in the 32x32 accumulator order [OT][2][16]
+// of the f32 image: the four rows of lane group g in out tile t are four consecutive floats, at x3_lane_off(g) +
+// x3_tile_off(t). Callers add the lane part once, so that the tile part folds into the ds_read offsets.
+__device__ __forceinline__ int x3_lane_off(int g) { return 16 * (g & 1) + 4 * (g >> 1); }
+__device__ __forceinline__ int x3_tile_off(int t) { return 32 * (t >> 1) + 8 * (t & 1); }
+
+// Thin heads on relu(x) in the 16x16 layout (the counterparts of lds_head / lds_head3): per sample half, a VALU dot
+// product over the lane's 4 rows of every tile, then the sum over the 4 lane groups (xor 16, xor 32). One tile at a time.
+// w: the head's weights + x3_lane_off(g).
+template <int OT, int NIN>
+__device__ __forceinline__ void x3_head(const f32x4 (&x)[NIN][2], const float* w, float (&out)[2]) {
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int t = 0; t < OT; ++t) {
+        const f32x4 wv = lds_read4(w + x3_tile_off(t));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float v0 = x[t][0][e], v1 = x[t][1][e];
+            asm("" : "+v"(v0), "+v"(v1));     // opaque copies (see lds_head)
+            s0 = fmaf(wv[e], relu_bits(v0), s0);
+            s1 = fmaf(wv[e], relu_bits(v1), s1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    s0 += __shfl_xor(s0, 16, 64);
+    s1 += __shfl_xor(s1, 16, 64);
+    out[0] = s0 + __shfl_xor(s0, 32, 64);
+    out[1] = s1 + __shfl_xor(s1, 32, 64);
+}
+template <int OT, int NIN>
+__device__ __forceinline__ void x3_head3(const f32x4 (&x)[NIN][2], const float* w, int stride, float (&out)[2][3]) {
+    float s[2][3] = {};
+#pragma unroll
+    for (int t = 0; t < OT; ++t) {
+        const float* p = w + x3_tile_off(t);
+        const f32x4 w0 = lds_read4(p), w1 = lds_read4(p + stride), w2 = lds_read4(p + 2 * stride);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                float v = x[t][n][e];
+                asm("" : "+v"(v));
+                v = relu_bits(v);
+                s[n][0] = fmaf(w0[e], v, s[n][0]);
+                s[n][1] = fmaf(w1[e], v, s[n][1]);
+                s[n][2] = fmaf(w2[e], v, s[n][2]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = s[n][c] + __shfl_xor(s[n][c], 16, 64);
+            out[n][c] = v + __shfl_xor(v, 32, 64);
+        }
+}
+
+// One tile-step at stream position POS (mod SPG, a constant after unrolling): the twelve MFMAs of out tile `acc`, product
+// by product smallest first, each for both sample halves (MFMA k = product k / 2, half k % 2). A 16x16x32 MFMA leaves 8 of
+// its 16 cycles for vector issue: about two instructions of any kind per gap. Behind MFMA k: side(k) (operand
+// preparation, bias tiles), then behind MFMA 0 the refill DMA and behind MFMAs 1..3 a fragment read of the tile-step two
+// ahead (an LDS load issued by side(0) or side(1) is older than those reads: waiting for it does not wait for them).
 template <class Side>
-__device__ __forceinline__ void x3_step(X3Ring& st, const int POS, f32x16& acc, const u32x4 (&b)[3], Side side) {
+__device__ __forceinline__ void x3_step(X3Ring& st, const int POS, f32x4 (&acc)[2], const u32x4 (&b)[2][3], Side side) {
     using C = X3Cfg;
     const int P = (POS - C::kSync + C::SPG) % C::SPG;              // position in the refill interval
+    const int AHEAD = (POS + 2) % C::SPG;
     u32x4 a[3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) { a[p] = st.f1[p]; st.f1[p] = st.f2[p]; }
     if (P == 0) st.boundary();
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_x3(acc, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (P < C::GPW) st.dma(P);
-    side(0);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_x3(acc, a[0], b[2]);
-    __builtin_amdgcn_sched_barrier(0);
-    st.f2[1] = st.frag(1);
-    side(1);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_x3(acc, a[2], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    st.f2[0] = st.frag(0);
-    side(2);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_x3(acc, a[0], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    st.f2[2] = st.frag(2);
-    st.advance();
-    side(3);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_x3(acc, a[1], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    side(4);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_x3(acc, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    side(5);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const int pr = k >> 1, n = k & 1;                          // a1b1, a0b2, a2b0, a0b1, a1b0, a0b0
+        const int pa = pr == 0 || pr == 4 ? 1 : pr == 2 ? 2 : 0;
+        const int pb = pr == 0 || pr == 3 ? 1 : pr == 1 ? 2 : 0;
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_x3(acc[n], a[pa], b[n][pb]);
+        __builtin_amdgcn_sched_barrier(0);
+        side(k);
+        if (k == 0 && P < C::GPW) st.dma(P);
+        if (k == 1) st.f2[1] = st.frag(AHEAD, 1);
+        if (k == 2) st.f2[0] = st.frag(AHEAD, 0);
+        if (k == 3) {
+            st.f2[2] = st.frag(AHEAD, 2);
+            if (AHEAD == C::SPG - 1) st.next_group();
+        }
+    }
     if (P == C::SPG - 1) st.group_issued();
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// One part of a layer: NS k16 steps over OT out tiles (NS * OT a whole number of ring groups, so every part starts at
-// stream position 0 mod SPG). bsrc(s, p, x): elements 2p, 2p+1 of step s's B operand as f32 (lazy ReLU / parked encoding).
-// Step s+1's operand is split during step s: pair p behind MFMAs 1, 3, 4, 5 of tile-step p (load; hi; mid; lo). Step 0's
-// cannot be early (its source is the layer before). hook(s, t): behind MFMA 2 of tile-step t of step s.
-template <int OT, int NS, class BSrc, class Hook>
-__device__ __forceinline__ void x3_part(X3Ring& st, f32x16 (&out)[X3Cfg::NT], BSrc bsrc, Hook hook) {
-    static_assert((NS * OT) % X3Cfg::SPG == 0 && OT >= 4, "a part is a whole number of ring groups; 4 pairs per step");
-    u32x4 b[3];
+// One part of a layer: NS k32 steps over OT out tiles (NS * OT a whole number of ring groups, so every part starts at
+// stream position 0 mod SPG). ld(s, n, p, e): element 2p + e of step s's B operand for sample half n as f32 (an
+// accumulator register, relu'd here when RELU, or a parked encoding value). Step s+1's operand is split during step s:
+// pair (n, p) = (t / 4, t % 4) in tile-step t < 8, at most two instructions per gap - load 0, load 1 behind MFMAs 0, 1;
+// ReLU behind 2, 3; then hi; extract hi; subtract; mid; extract mid; subtract; lo behind 4..10. Step 0's cannot be early
+// (its source is the layer before). hook(s, t, k): behind MFMAs k = 10, 11 of tile-step t of step s.
+template <int OT, int NS, bool RELU, class Ld, class Hook>
+__device__ __forceinline__ void x3_part(X3Ring& st, f32x4 (&out)[X3Cfg::OT][2], Ld ld, Hook hook) {
+    static_assert((NS * OT) % X3Cfg::SPG == 0 && OT >= 8, "a part is a whole number of ring groups; 8 pairs per step");
+    auto act = [](float v) { return RELU ? relu_bits(v) : v; };
+    auto bf2_f32 = [](unsigned q) { return (f32x2){__uint_as_float(q << 16), __uint_as_float(q & 0xffff0000u)}; };
+    u32x4 b[2][3];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        float x[2];
-        bsrc(0, p, x);
-        b[0][p] = cvt_bf2(x[0], x[1]);
-        sub_bf2(x[0], x[1], b[0][p]);
-        b[1][p] = cvt_bf2(x[0], x[1]);
-        sub_bf2(x[0], x[1], b[1][p]);
-        b[2][p] = cvt_bf2(x[0], x[1]);
-    }
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            f32x2 x = {act(ld(0, n, p, 0)), act(ld(0, n, p, 1))};
+            b[n][0][p] = cvt_bf2(x[0], x[1]);
+            x -= bf2_f32(b[n][0][p]);
+            b[n][1][p] = cvt_bf2(x[0], x[1]);
+            x -= bf2_f32(b[n][1][p]);
+            b[n][2][p] = cvt_bf2(x[0], x[1]);
+        }
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        u32x4 bn[3];
-        float xs[4][2];
+        u32x4 bn[2][3];
+        f32x2 xs[8], es[8];
 #pragma unroll
         for (int t = 0; t < OT; ++t) {
             auto side = [&](int k) {
-                if (s + 1 < NS && t < 4) {
-                    if (k == 1) bsrc(s + 1, t, xs[t]);
-                    if (k == 3) { bn[0][t] = cvt_bf2(xs[t][0], xs[t][1]); sub_bf2(xs[t][0], xs[t][1], bn[0][t]); }
-                    if (k == 4) { bn[1][t] = cvt_bf2(xs[t][0], xs[t][1]); sub_bf2(xs[t][0], xs[t][1], bn[1][t]); }
-                    if (k == 5) bn[2][t] = cvt_bf2(xs[t][0], xs[t][1]);
+                if (s + 1 < NS && t < 8) {
+                    const int n = t >> 2, p = t & 3;
+                    if (k == 0) xs[t][0] = ld(s + 1, n, p, 0);
+                    if (k == 1) xs[t][1] = ld(s + 1, n, p, 1);
+                    if (RELU && k == 2) xs[t][0] = relu_bits(xs[t][0]);
+                    if (RELU && k == 3) xs[t][1] = relu_bits(xs[t][1]);
+                    if (k == 4) bn[n][0][p] = cvt_bf2(xs[t][0], xs[t][1]);
+                    if (k == 5) es[t] = bf2_f32(bn[n][0][p]);
+                    if (k == 6) xs[t] -= es[t];
+                    if (k == 7) bn[n][1][p] = cvt_bf2(xs[t][0], xs[t][1]);
+                    if (k == 8) es[t] = bf2_f32(bn[n][1][p]);
+                    if (k == 9) xs[t] -= es[t];
+                    if (k == 10) bn[n][2][p] = cvt_bf2(xs[t][0], xs[t][1]);
                 }
-                if (k == 2) hook(s, t);
+                if (k >= 10) hook(s, t, k);
             };
             x3_step(st, (s * OT + t) % X3Cfg::SPG, out[t], b, side);
         }
         if (s + 1 < NS) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) b[p] = bn[p];
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                for (int p = 0; p < 3; ++p) b[n][p] = bn[n][p];
         }
     }
 }
@@ -272,24 +350,31 @@ template <int NT, int SKIP>
 __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, const void* img, int img_pieces) {
     static_assert(NT == X3Cfg::NT, "W = 256 only");
     using C = X3Cfg;
-    constexpr int OTV = NT / 2;
+    constexpr int OT = C::OT, OTV = OT / 2;
     // ONE object (see nerf_mlp_fwd_lds_kernel): ring first, then constants, then the parked encoding operands
     __shared__ __attribute__((aligned(16))) float smem[C::RP * kPiece + C::kConstMax + C::kParkFloats];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = lane >> 5, j = lane & 31;
+    const int h = lane >> 5, j = lane & 31;                             // the encoding's (half, sample) of this lane
+    const int g = lane >> 4, c = lane & 15;                             // lane group, sample in a 16-sample half
     const MlpLayout& L = a.lay;
     float* const ring0 = smem;
     float* const cst = smem + C::RP * kPiece;
-    float* const park = cst + C::kConstMax + wave * (64 * 4 * C::kParkQuads) + lane * 4;
+    float* const park_w = cst + C::kConstMax + wave * (64 * 4 * C::kParkQuads);
+    float* const park = park_w + lane * 4;
+    // the parked operand of (half n, lane group g) is the encoding lane 16n + c + 32(g & 1) wrote (pack_x3_kernel's k map)
+    const float* const park_rd = park_w + (c + 32 * (g & 1)) * 4 + (g >> 1) * 256;
     {   // constant area: biases (one piece per layer), alpha head, rgb head - from the f32 image
         const int n = (int)(L.total - L.b_off[0]);
-        const float* __restrict__ g = a.packed + L.b_off[0];
-        for (int i = tid * 4; i < n; i += 1024) *reinterpret_cast<f32x4*>(cst + i) = *reinterpret_cast<const f32x4*>(g + i);
+        const float* __restrict__ gm = a.packed + L.b_off[0];
+        for (int i = tid * 4; i < n; i += 1024) *reinterpret_cast<f32x4*>(cst + i) = *reinterpret_cast<const f32x4*>(gm + i);
     }
     __syncthreads();
     const float* const c_alpha = cst + (L.alpha_off - L.b_off[0]);
     const float* const c_rgb = cst + (L.rgb_off - L.b_off[0]);
+    int lane_off = x3_lane_off(g);
+    asm volatile("" : "+v"(lane_off));                                   // added once: the tile parts stay immediates
+    const float* const cst_g = cst + lane_off;
 
     X3Ring st;
     st.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(img), 0, img_pieces * (kPiece * 4), 0x00020000);
@@ -297,16 +382,22 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
     st.total = img_pieces; st.src = 0; st.slot = 0; st.rd = 0; st.wave = wave;
     st.start();
 
-    f32x16 P[NT], Q[NT];
-    auto bias_tile = [&](f32x16 (&dst)[NT], int l, int t) {             // dst[t] = bias of layer l, tile t (f32, in AGPRs)
-        const float* p = cst + l * kPiece + (t * 2 + h) * 16;
-        const f32x4 v0 = lds_read4(p), v1 = lds_read4(p + 4), v2 = lds_read4(p + 8), v3 = lds_read4(p + 12);
-        dst[t] = (f32x16){v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3],
-                          v2[0], v2[1], v2[2], v2[3], v3[0], v3[1], v3[2], v3[3]};
-        asm volatile("" : "+a"(dst[t]));
+    f32x4 P[OT][2], Q[OT][2];
+    // dst[i] = bias of layer l, tile i (f32, in AGPRs), as side work of two tile-steps: the LDS read into the first sample
+    // half behind MFMA 10 of tile-step t0, the register copy into the second behind MFMA 11 of tile-step t0 + 1 (when the
+    // read has landed: a copy right behind it would wait for it)
+    auto bias_tile = [&](f32x4 (&dst)[OT][2], int l, int i, int t0, int t, int k) {
+        if (t == t0 && k == 10) {
+            dst[i][0] = lds_read4(cst_g + l * kPiece + x3_tile_off(i));
+            asm volatile("" : "+a"(dst[i][0]));
+        }
+        if (t == t0 + 1 && k == 11) {
+            dst[i][1] = dst[i][0];
+            asm volatile("" : "+a"(dst[i][1]));
+        }
     };
 #pragma unroll
-    for (int t = 0; t < NT; ++t) bias_tile(P, 0, t);                    // later rounds: written during the views layer
+    for (int t = 0; t < OT; ++t) { bias_tile(P, 0, t, 0, 0, 10); bias_tile(P, 0, t, 0, 1, 11); }                    // later rounds: written during the views layer
 
     const int ntiles = (int)((a.M + 31) / 32);
     const int nrounds = (int)((ntiles + (long)gridDim.x * 4 - 1) / ((long)gridDim.x * 4));
@@ -331,30 +422,36 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
                 *reinterpret_cast<f32x4*>(park + (kEmbQuads + k) * 256) =
                     (f32x4){demb[4 * k], demb[4 * k + 1], demb[4 * k + 2], demb[4 * k + 3]};
         }
-        // k16 step s of a parked encoding: parked quads 2s, 2s+1 (f32 k-steps 8s .. 8s+7)
+        // k32 step u of a parked encoding from quad q0 on: element 2p + e is k-step 4Q + 2(p & 1) + e of quad
+        // Q = q0 + 4u + (g >> 1) + 2(p >> 1)
         auto b_park = [&](int q0) {
-            return [=](int s, int p, float (&x)[2]) {
-                const f32x2 v = *(lds_cf2*)(park + (q0 + 2 * s + (p >> 1)) * 256 + 2 * (p & 1));
-                x[0] = v[0];
-                x[1] = v[1];
+            return [=](int u, int n, int p, int e) {
+                return *(__attribute__((address_space(3))) const float*)(park_rd + n * 64 + (q0 + 4 * u + 2 * (p >> 1)) * 256 + 2 * (p & 1) + e);
             };
         };
-        auto no_hook = [](int, int) {};
+        // element 2p + e of k32 step u: register 2(p & 1) + e of tile 2u + (p >> 1)
+        auto b_acc = [](const f32x4 (&in)[OT][2]) {
+            return [&in](int u, int n, int p, int e) { return in[2 * u + (p >> 1)][n][2 * (p & 1) + e]; };
+        };
+        auto no_hook = [](int, int, int) {};
         // layer 0: 63 -> W into P (its bias is already there); Q (dead) receives the bias of layer 1 meanwhile
-        x3_part<NT, kEmbQuads / 2>(st, P, b_park(0), [&](int s, int t) { if (t == 4 || t == 6) bias_tile(Q, 1, 2 * s + (t - 4) / 2); });
+        x3_part<OT, kEmbQuads / 4, false>(st, P, b_park(0), [&](int u, int t, int k) {     // tile 8u + i: tile-steps 7 + i, 8 + i
+            for (int i = 0; i < 8; ++i) bias_tile(Q, 1, 8 * u + i, 7 + i, t, k);
+        });
 
-        float alpha = 0.f;
-        auto layer = [&](f32x16 (&in)[NT], f32x16 (&out)[NT], int l, bool may_skip, bool may_be_last) __attribute__((always_inline)) {
-            if (may_be_last && l == L.D) alpha = lds_head<NT>(in, c_alpha, h) + c_alpha[NT * 32];   // alpha_linear on relu(h)
-            if (may_skip && l == L.skip + 1) x3_part<NT, kEmbQuads / 2>(st, out, b_park(0), no_hook);   // cat([input_pts, h])
-            // input tile k is last read by the split of step 2k+1 (during step 2k): dead from step 2k+2 on
-            x3_part<NT, 2 * NT>(st, out,
-                [&](int s, int p, float (&x)[2]) {
-                    x[0] = relu_bits(in[s >> 1][8 * (s & 1) + 2 * p]);
-                    x[1] = relu_bits(in[s >> 1][8 * (s & 1) + 2 * p + 1]);
-                },
-                [&](int s, int t) { if (t == 4 && (s & 1) == 0 && s > 0) bias_tile(in, l + 1, s / 2 - 1); });
-            bias_tile(in, l + 1, NT - 1);
+        float alpha[2] = {0.f, 0.f};
+        auto layer = [&](f32x4 (&in)[OT][2], f32x4 (&out)[OT][2], int l, bool may_skip, bool may_be_last) __attribute__((always_inline)) {
+            if (may_be_last && l == L.D) {                                  // alpha_linear on relu(h)
+                x3_head<OT>(in, c_alpha + lane_off, alpha);
+                alpha[0] += c_alpha[NT * 32];
+                alpha[1] += c_alpha[NT * 32];
+            }
+            if (may_skip && l == L.skip + 1) x3_part<OT, kEmbQuads / 4, false>(st, out, b_park(0), no_hook);   // cat([input_pts, h])
+            // input tiles 2u, 2u+1 are last read by the split of step u (during step u-1): dead from step u on
+            x3_part<OT, NT, true>(st, out, b_acc(in), [&](int u, int t, int k) {
+                if (u > 0) { bias_tile(in, l + 1, 2 * u - 2, 8, t, k); bias_tile(in, l + 1, 2 * u - 1, 9, t, k); }
+                if (u == NT - 1) { bias_tile(in, l + 1, 2 * u, 10, t, k); bias_tile(in, l + 1, 2 * u + 1, 11, t, k); }
+            });
         };
 #pragma unroll 1
         for (int l = 1; l < L.D; l += 2) {                                  // D is even (host check): whole pairs
@@ -363,23 +460,23 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
         }
         // views_linears[0]: cat([feature, embedded dirs]) -> W/2 into Q's first tiles (no activation on the feature);
         // P receives the bias of the NEXT tile's layer 0 as its tiles die
-        x3_part<OTV, 2 * NT>(st, Q,
-            [&](int s, int p, float (&x)[2]) {
-                x[0] = P[s >> 1][8 * (s & 1) + 2 * p];
-                x[1] = P[s >> 1][8 * (s & 1) + 2 * p + 1];
-            },
-            [&](int s, int t) { if (t == 3 && (s & 1) == 0 && s > 0) bias_tile(P, 0, s / 2 - 1); });
-        bias_tile(P, 0, NT - 1);
-        x3_part<OTV, kDirQuads / 2>(st, Q, b_park(kEmbQuads), no_hook);
-        float rgb[3];                                                       // rgb_linear: W/2 -> 3
-        lds_head3<OTV>(Q, c_rgb, OTV * 32, h, rgb);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[c] += c_rgb[3 * OTV * 32 + c];
-        int je = j;
+        x3_part<OTV, NT, false>(st, Q, b_acc(P), [&](int u, int t, int k) {
+            if (u > 0) { bias_tile(P, 0, 2 * u - 2, 2, t, k); bias_tile(P, 0, 2 * u - 1, 3, t, k); }
+            if (u == NT - 1) { bias_tile(P, 0, 2 * u, 4, t, k); bias_tile(P, 0, 2 * u + 1, 5, t, k); }
+        });
+        x3_part<OTV, kDirQuads / 4, false>(st, Q, b_park(kEmbQuads), no_hook);
+        float rgb[2][3];                                                    // rgb_linear: W/2 -> 3
+        x3_head3<OTV>(Q, c_rgb + lane_off, OTV * 16, rgb);
+        // lane group n < 2 stores sample half n
+        const int n = g & 1;
+        int je = 16 * n + c;
         asm volatile("" : "+v"(je));
         const long sout = (long)tile * 32 + je;
-        if (h == 0 && sout < a.M && tile_own < ntiles)
-            reinterpret_cast<float4*>(a.raw)[sout] = make_float4(rgb[0], rgb[1], rgb[2], alpha);
+        if (g < 2 && sout < a.M && tile_own < ntiles)
+            reinterpret_cast<float4*>(a.raw)[sout] = make_float4((n ? rgb[1][0] : rgb[0][0]) + c_rgb[3 * OTV * 16 + 0],
+                                                                 (n ? rgb[1][1] : rgb[0][1]) + c_rgb[3 * OTV * 16 + 1],
+                                                                 (n ? rgb[1][2] : rgb[0][2]) + c_rgb[3 * OTV * 16 + 2],
+                                                                 n ? alpha[1] : alpha[0]);
     }
     lds_wait_vmcnt<0>();       // no LDS-DMA may be in flight when the workgroup's LDS is released
 }
