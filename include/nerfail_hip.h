@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 8
+#define NERFAIL_ABI_VERSION 9
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -454,6 +454,30 @@ int nerfail_adam_step(const nerfail_adam_tensor* tensors, int n_tensors, double 
 /* img2mse of the training loss (RH:9, RN:781-789): loss[0] = mean((x - y)^2) over n values by a fixed-order tree, and - when
  * dx is not NULL - dx[i] = 2 (x[i] - y[i]) / n, the gradient of that mean (one launch instead of ~9 torch kernels). */
 int nerfail_mse(const float* x, const float* y, int64_t n, float* loss, float* dx, void* stream);
+
+/* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
+
+/* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool
+ * (3-32-64-128-256-256-128-64 channels), fc1 1024->512 + ReLU, fc2 512->num_classes. Input x: [B,3,H,W] float32 NCHW;
+ * H and W must make the seventh stage 4 x 4 (766..893). Conv stages run on v_mfma_f32_32x32x2_f32; no atomics, results are
+ * bitwise reproducible.
+ *   pack:       params_host = HOST array of the 18 DEVICE parameter pointers in state_dict order (conv1.weight, conv1.bias,
+ *               ..., conv7.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias) -> packed (nerfail_cnn_packed_floats floats).
+ *   fwd:        logits [B,num_classes]; workspace (nerfail_cnn_workspace_bytes): every stage's pooled NHWC output and the FC
+ *               hidden layer, kept for the backward; masks (nerfail_cnn_mask_bytes): 2-bit pool argmax codes, or NULL for
+ *               inference only.
+ *   bwd_data:   d_x [B,3,H,W] (NCHW) from d_logits [B,num_classes], the forward's workspace and masks (weights frozen);
+ *               scratch: nerfail_cnn_bwd_scratch_bytes bytes. Inputs are not written: callable any number of times.
+ * The size helpers return 0 for unsupported shapes. */
+size_t nerfail_cnn_packed_floats(int num_classes);
+int nerfail_cnn_pack(const float* const* params_host, int num_classes, float* packed, void* stream);
+size_t nerfail_cnn_workspace_bytes(int B, int H, int W, int num_classes);
+size_t nerfail_cnn_mask_bytes(int B, int H, int W);
+size_t nerfail_cnn_bwd_scratch_bytes(int B, int H, int W);
+int nerfail_cnn_fwd(const float* packed, int num_classes, const float* x, int B, int H, int W, float* workspace,
+                    unsigned char* masks, float* logits, void* stream);
+int nerfail_cnn_bwd_data(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
+                         const float* d_logits, int B, int H, int W, float* scratch, float* d_x, void* stream);
 
 #ifdef __cplusplus
 }

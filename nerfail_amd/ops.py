@@ -323,3 +323,74 @@ def _(packed, packed_T, acts, d_raw, D, W, skip):
 
 ALL = ('ray_gen', 'composite', 'composite_bwd', 'sample_pdf', 'sample_fine', 'mlp_fwd', 'mlp_fwd_train', 'mlp_bwd', 'knn8', 'gauss_weight',
        'gauss_gather', 'gauss_gather_bwd', 'igsm_step')
+
+
+# ----------------------------------------------------------------------------------------------- MyCNN victim (model/MyModel.py:5-52)
+def _cnn_sizes(x, num_classes, keep_masks):
+    lib = _lib.load()
+    B, C3, H, W = x.shape
+    ws = lib.nerfail_cnn_workspace_bytes(B, H, W, num_classes)
+    if C3 != 3 or ws == 0:
+        raise ValueError('cnn_fwd: unsupported input %s (needs [B,3,H,W] with a 4 x 4 seventh stage, H and W in 766..893)'
+                         % (tuple(x.shape),))
+    return ws // 4, (lib.nerfail_cnn_mask_bytes(B, H, W) if keep_masks else 0)
+
+
+@custom_op(NS + '::cnn_fwd', mutates_args=(), device_types='cuda')
+def cnn_fwd(packed: Tensor, x: Tensor, num_classes: int, keep_masks: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """MyCNN forward: (logits [B,num_classes], workspace (saved activations), masks (pool argmax codes; empty unless
+    keep_masks)). packed = nerfail_amd.MyModel.MyCNN.packed(). Differentiable with respect to x when keep_masks is set."""
+    B, _, H, W = x.shape
+    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
+    ws = torch.empty((n_ws,), dtype=torch.float32, device=x.device)
+    masks = torch.empty((n_mask,), dtype=torch.uint8, device=x.device)
+    logits = torch.empty((B, num_classes), dtype=torch.float32, device=x.device)
+    _chk(_lib.load().nerfail_cnn_fwd(_lib.dev(packed), num_classes, _lib.dev(x, 'x'), B, H, W, _lib.dev(ws),
+                                     _lib.dev(masks) if keep_masks else None, _lib.dev(logits), _s()))
+    return logits, ws, masks
+
+
+@cnn_fwd.register_fake
+def _(packed, x, num_classes, keep_masks):
+    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
+    return (x.new_empty((x.shape[0], num_classes)), x.new_empty((n_ws,)), x.new_empty((n_mask,), dtype=torch.uint8))
+
+
+@custom_op(NS + '::cnn_bwd_data', mutates_args=(), device_types='cuda')
+def cnn_bwd_data(packed: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
+    """d loss / d x [B,3,H,W] of cnn_fwd from d loss / d logits and the forward's workspace and masks (weights frozen)."""
+    lib = _lib.load()
+    B, C = d_logits.shape
+    if masks.numel() == 0:
+        raise RuntimeError('cnn_bwd_data: the forward kept no masks (cnn_fwd with keep_masks=False)')
+    nb = lib.nerfail_cnn_bwd_scratch_bytes(B, H, W)
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
+    dx = torch.empty((B, 3, H, W), dtype=torch.float32, device=d_logits.device)
+    _chk(lib.nerfail_cnn_bwd_data(_lib.dev(packed), C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits), B, H, W,
+                                  _lib.dev(scratch), _lib.dev(dx), _s()))
+    return dx
+
+
+@cnn_bwd_data.register_fake
+def _(packed, workspace, masks, d_logits, H, W):
+    return d_logits.new_empty((d_logits.shape[0], 3, H, W))
+
+
+def _cnn_setup(ctx, inputs, output):
+    packed, x, num_classes, keep_masks = inputs
+    _, ws, masks = output
+    ctx.save_for_backward(packed, ws, masks)
+    ctx.hw = (x.shape[2], x.shape[3])
+    ctx.mark_non_differentiable(ws, masks)
+
+
+def _cnn_backward(ctx, g_logits, g_ws, g_masks):
+    packed, ws, masks = ctx.saved_tensors
+    if g_logits is None:
+        return None, None, None, None
+    return None, cnn_bwd_data(packed, ws, masks, g_logits.contiguous().float(), ctx.hw[0], ctx.hw[1]), None, None
+
+
+cnn_fwd.register_autograd(_cnn_backward, setup_context=_cnn_setup)
+
+CNN_OPS = ('cnn_fwd', 'cnn_bwd_data')
