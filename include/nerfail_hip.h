@@ -468,7 +468,26 @@ int nerfail_mse(const float* x, const float* y, int64_t n, float* loss, float* d
  *               inference only.
  *   bwd_data:   d_x [B,3,H,W] (NCHW) from d_logits [B,num_classes], the forward's workspace and masks (weights frozen);
  *               scratch: nerfail_cnn_bwd_scratch_bytes bytes. Inputs are not written: callable any number of times.
- * The size helpers return 0 for unsupported shapes. */
+ * The size helpers return 0 for unsupported shapes.
+ *
+ * Buffer contract (what tests/cnn_ref.py decodes; all buffers are plain caller-owned memory). Stage s = 0..6 has input
+ * hin x win (stage 0: H x W), Cout_s = 32, 64, 128, 256, 256, 128, 64 output channels and a pooled output of
+ * hp x wp = (hin - 2) / 2 x (win - 2) / 2 (floor), which is the next stage's input.
+ *   workspace:  stage s = 0..6 pooled output [B, hp_s, wp_s, Cout_s] (NHWC) float32, the stages back to back, then
+ *               hidden [B, 512] (fc1's output after the ReLU). fwd writes every element.
+ *   masks:      per stage [B, hp][ceil(wp / 8)][2][Cout] bytes, the stages back to back. The byte at
+ *               (b, pr, pc >> 3, pc & 1, ch) holds, at bits 2 * ((pc & 7) >> 1) and the one above, the window position
+ *               2 * dy + dx of pooled cell (pr, pc): the first maximum of the window wins, a NaN wins over any number (the
+ *               last NaN of a window). fwd writes every byte; the cells of a byte beyond wp are unspecified and never read.
+ *               bwd_data routes the gradient of a cell to the coded position unless the cell's workspace value is <= 0
+ *               (NaN passes), and gates d hidden where hidden <= 0.
+ *   scratch:    of bwd_data; contents unspecified on return.
+ *   packed:     regions in this order, each rounded up to 4 floats (the round-up's contents unspecified): per stage
+ *               s = 0..6 the forward weights [Cout][tap][Cin] (tap = 3 ky + kx; stage 0: [32][10 taps][4 channels], the
+ *               tenth tap and the fourth channel exactly 0), the bias [Cout], and for s >= 1 the backward weights
+ *               [Cin][tap][Cout] (taps not flipped); then conv1.weight as it is [32][3][9]; fc1T [1024][512] and fc1P
+ *               [512][1024], fc1.weight with its 1024 columns reordered from c * 16 + y * 4 + x to (y * 4 + x) * 64 + c
+ *               (NHWC), transposed and not; fc1.bias [512]; fc2.weight [num_classes][512]; fc2.bias [num_classes]. */
 size_t nerfail_cnn_packed_floats(int num_classes);
 int nerfail_cnn_pack(const float* const* params_host, int num_classes, float* packed, void* stream);
 size_t nerfail_cnn_workspace_bytes(int B, int H, int W, int num_classes);
