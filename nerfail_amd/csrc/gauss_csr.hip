@@ -294,9 +294,6 @@ __device__ __forceinline__ int seg_finish(SegLane<C>& st, const int lane, const 
 // banks; exactly 8 KB per wave = 5 workgroups per CU) and read back lane-consecutive; complete rows are collected in the same slice by ordinal and leave as one contiguous run of
 // full 16-byte-per-lane stores. Same products, same order of additions: the bits equal the direct route's.
 constexpr int kSegLdsSlots = kSegChunk;
-#ifndef NF_SEG_LDS_MULT
-#define NF_SEG_LDS_MULT 1      // (occupancy experiment: 2 halves the waves per CU)
-#endif
 
 template <int C, bool PACKED, bool W4 = true>
 __device__ __forceinline__ void seg_reduce_chunk(const long wg, const int lane, const long E, const int* __restrict__ row_of,
@@ -518,7 +515,7 @@ __global__ __launch_bounds__(256) void gauss_seg_reduce_views_kernel(SegViews a)
         if (i < a.nv && vb >= a.block_start[i]) v = i;                 // block_start ascends
     const long wg = (vb - a.block_start[v]) * 4 + (threadIdx.x >> 6);
     if (wg >= a.chunks[v]) return;                                     // wave-uniform
-    __shared__ float4 lds[4][kSegLdsSlots * NF_SEG_LDS_MULT];                            // one slice per wave, never shared: no barriers
+    __shared__ float4 lds[4][kSegLdsSlots];                            // one slice per wave, never shared: no barriers
     seg_reduce_chunk<1, true, W4>(wg, threadIdx.x & 63, a.E[v], a.chunk_ord[v], a.packed[v], a.w_sorted[v], a.g_pix[v], 0, a.val[v],
                                   a.n_rows[v], a.rec_row[v], a.rec_val[v], lds[threadIdx.x >> 6]);
 }

@@ -154,15 +154,13 @@ __device__ __forceinline__ void insert_key(Key (&fk)[8], Key k) {       // fk st
     }
 }
 
-#ifndef NF_KNN_BATCH
-#define NF_KNN_BATCH 8     // 1 (one load per candidate): 1.84 ms per 640 000-query view, 2: 1.61, 4: 1.37, 8: 1.27, 16: 1.33
-#endif
-// Candidates [b, e) of one contiguous cell range against the running top-8. NF_KNN_BATCH point loads are issued before the first
+constexpr int kScanBatch = 8;     // 1 (one load per candidate): 1.84 ms per 640 000-query view, 2: 1.61, 4: 1.37, 8: 1.27, 16: 1.33
+// Candidates [b, e) of one contiguous cell range against the running top-8. kScanBatch point loads are issued before the first
 // is examined (clamped index, so the loads are unconditional): the search is latency bound, one dependent 16-byte load
 // per candidate otherwise. The order in which candidates are examined does not matter: the key (d2, index) is total.
 __device__ __forceinline__ void scan_points(const float4* __restrict__ sorted, int b, int e, float qx, float qy, float qz,
                                             Key (&fk)[8], unsigned& examined) {
-    constexpr int U = NF_KNN_BATCH;
+    constexpr int U = kScanBatch;
     examined += (unsigned)(e - b);
     for (int p = b; p < e; p += U) {
         float4 pt[U];

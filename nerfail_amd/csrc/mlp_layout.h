@@ -213,13 +213,11 @@ __device__ __forceinline__ void load_bias(f32x16 (&acc)[OT], const float* __rest
 }
 
 // One part of a layer: NQ quads of 4 k-steps. Quad q's A fragments (one 16-byte load per out-tile and
-// lane) are requested PFQ (default NF_MLP_PF = 1) quads AHEAD of the 4*OT MFMAs that consume them, so ~2048 MFMA
+// lane) are requested PFQ (default kPrefetchQuads = 1) quads AHEAD of the 4*OT MFMAs that consume them, so ~2048 MFMA
 // cycles per quad of distance cover the L2 latency (one wave per SIMD: nothing else would hide it).
 // bsel(q, e) yields the B operand (a register of the previous layer / of the encoding) for k-step 4q+e;
 // q and e are compile-time constants after unrolling, so it is a plain register reference.
-#ifndef NF_MLP_PF
-#define NF_MLP_PF 1          // quads of A fragments in flight ahead of the one being multiplied
-#endif
+constexpr int kPrefetchQuads = 1;     // quads of A fragments in flight ahead of the one being multiplied (2: no change, see below)
 // What the exact-f32 forward kernel loses against the 154.8 TFLOP/s the bare MFMA loop sustains on this chip (clock
 // 2.387 GHz inside the kernel, no throttling - tools/clockprobe, tools/fwd_clock.py), measured by ablation
 // (round-1 experiment builds, see tools/README.md) at 1.57 M samples, 14.14 ms = 132 TFLOP/s:
@@ -234,7 +232,7 @@ __device__ __forceinline__ void load_bias(f32x16 (&acc)[OT], const float* __rest
 // barrier per layer: 16.2 ms - aligned waves miss L1 together, free-running ones already share it by drifting).
 // Tried against the layer-boundary shuffles: a two-layer loop body in which the two register arrays swap roles
 // (no copies, in-place ReLU): no change for inference (14.15 ms), 6 % slower with the training stores.
-template <int OT, int NQ, int PFQ = NF_MLP_PF, typename BSel>
+template <int OT, int NQ, int PFQ = kPrefetchQuads, typename BSel>
 __device__ __forceinline__ void mfma_part(f32x16 (&acc)[OT], const float* __restrict__ w, int lane, BSel bsel) {
     const f32x4* wp = reinterpret_cast<const f32x4*>(w) + lane;
     constexpr int PF = PFQ < NQ ? PFQ : (NQ > 1 ? NQ - 1 : 1), RING = PF + 1;
@@ -263,14 +261,14 @@ __device__ __forceinline__ void mfma_part(f32x16 (&acc)[OT], const float* __rest
     }
 }
 
-template <int OT, int NQ, int PFQ = NF_MLP_PF>
+template <int OT, int NQ, int PFQ = kPrefetchQuads>
 __device__ __forceinline__ void mfma_scalars(f32x16 (&acc)[OT], const float* __restrict__ w, int lane,
                                              const float (&bsrc)[4 * NQ]) {
     mfma_part<OT, NQ, PFQ>(acc, w, lane, [&](int q, int e) { return bsrc[4 * q + e]; });
 }
 
 // NT*4 quads whose B operands are the previous layer's accumulator registers
-template <int OT, int NT, int PFQ = NF_MLP_PF>
+template <int OT, int NT, int PFQ = kPrefetchQuads>
 __device__ __forceinline__ void mfma_acts(f32x16 (&acc)[OT], const float* __restrict__ w, int lane,
                                           const f32x16 (&in)[NT]) {
     mfma_part<OT, NT * 4, PFQ>(acc, w, lane, [&](int q, int e) { return in[q >> 2][4 * (q & 3) + e]; });
@@ -299,15 +297,11 @@ constexpr int kSlotCh = 16;                // floats between consecutive channel
 __device__ __forceinline__ int acc_lane_off(int lane) { return slot_pos(lane & 31) + (lane >> 5) * 4 * kSlotCh; }
 __device__ __forceinline__ constexpr int acc_reg_off(int r) { return ((r & 3) + 8 * (r >> 2)) * kSlotCh; }
 
-#ifndef NF_NT_STORE
-#define NF_NT_STORE 1
-#endif
 // One saved activation / gradient value: written once, read by a LATER kernel, 2 GB per pass. Stored non-temporal so
 // the stream does not push the 2.4 MB weight image (re-read by every workgroup for every tile) out of L2:
 // train-forward 16.1 -> 14.9 ms (f32) and 7.75 -> 7.15 ms (f16x3) at 1.57 M samples.
 __device__ __forceinline__ void slot_store(float* p, float v) {
-    if (NF_NT_STORE) __builtin_nontemporal_store(v, p);
-    else *p = v;
+    __builtin_nontemporal_store(v, p);
 }
 template <int NTILES>
 __device__ __forceinline__ void store_tiles(float* __restrict__ base, const f32x16 (&a)[NTILES], int lane) {

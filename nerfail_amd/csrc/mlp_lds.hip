@@ -8,7 +8,7 @@
 //     tile round from L2, a 64-register ring, 70 spilled registers; measured cost of that delivery: 6.5 % + 1 %.
 //   * here: the 4 waves of a workgroup share ONE copy of the stream. The packed image's weight range is copied piece by
 //     piece (1 KB = one wave-wide 16-byte access = the A fragments of one (quad, out-tile)) by LDS-DMA
-//     (global_load_lds_dwordx4: no VGPRs, no VALU) into a ring of RP pieces cut into S groups; wave w moves pieces
+//     (buffer_load_dwordx4 ... lds: no VGPRs, no VALU) into a ring of RP pieces cut into S groups; wave w moves pieces
 //     w, w+4, ... of every group. A group becomes readable at ONE s_barrier per group (after each wave's counted
 //     s_waitcnt vmcnt, which leaves the S-2 younger groups in flight); the slot freed at that barrier is refilled at
 //     once, the refill's DMA instructions interleaved with the following MFMAs. The stream never stops: it runs across
@@ -27,46 +27,15 @@
 
 namespace nerfail {
 
-#ifndef NF_LDS_SPREAD
-#define NF_LDS_SPREAD 1     // 1: one piece of side work per MFMA shadow (WRing::step, inference kernels); 0: round-2 form
-#endif
-#ifndef NF_LDS_VGPR_P
-#define NF_LDS_VGPR_P 1       // activation array P in arch VGPRs (VGPR-form MFMAs by inline asm; inference, W = 256); 0: both in AGPRs
-#endif
-#ifndef NF_LDS_RING_FIRST
-#define NF_LDS_RING_FIRST 1
-#endif
-#ifndef NF_LDS_BWD_SP1
-#define NF_LDS_BWD_SP1 1      // the backward-data ring kernel on the one-piece-of-side-work-per-shadow step form
-#endif
-#ifndef NF_LDS_TRAIN_NEWDMA
-#define NF_LDS_TRAIN_NEWDMA 1 // 1: the training kernel on the buffer-form / per-step refill as well
-#endif
-#ifndef NF_LDS_TRAIN_SP1
-#define NF_LDS_TRAIN_SP1 1    // the training forward on the one-piece-of-side-work-per-shadow step form too (round 6; 0: round-2 form)
-#endif
-#ifndef NF_LDS_TRAIN_K0
-#define NF_LDS_TRAIN_K0 8     // first MFMA of a quad's first step whose shadow carries an activation store (4 stores: K0 .. K0 + 3;
-                              // 8: behind the fragment reads of MFMAs 4..7 - measured 6.93 -> 6.89 ms at 786 432 samples; 4: round-3 position)
-#endif
-#ifndef NF_LDS_MID_SPLIT
-#define NF_LDS_MID_SPLIT 0  // 1: the next quad's operand preparation in two halves behind two MFMAs
-#endif
-#ifndef NF_LDS_DMA_BUF
-#define NF_LDS_DMA_BUF 1    // 1: LDS-DMA as buffer_load_dwordx4 ... lds (SGPR base + SGPR piece offset + one 32-bit lane offset)
-#endif                      //    0: global_load_lds_dwordx4 (a 64-bit address pair per lane)
-#ifndef NF_LDS_DMA_SPREAD
-#define NF_LDS_DMA_SPREAD 1 // 1: one refill DMA per step, spread over the group interval (W = 256 only; LdsCfg::kDmaSpread)
-#endif
-#ifndef NF_LDS_GPM
-#define NF_LDS_GPM 4        // pieces per ring group = NF_LDS_GPM * NT (4: one barrier per 4 quads of a W-wide layer)
-#endif
-
+constexpr int kGroupQuads = 4;      // pieces per ring group = kGroupQuads * NT (4: one barrier per 4 quads of a W-wide layer)
+// First MFMA of a quad's first step whose shadow carries an activation store of the training forward (4 stores: K0 .. K0 + 3).
+// 8: behind the fragment reads of MFMAs 4..7 - measured 6.93 -> 6.89 ms at 786 432 samples (4: the round-3 position).
+constexpr int kTrainStoreK0 = 8;
 
 template <int NT>
 struct LdsCfg {
     static constexpr int HS = NT >= 4 ? 4 : NT;                 // pieces (= out tiles) per step at full width
-    static constexpr int GP = NF_LDS_GPM * NT;                  // pieces per group
+    static constexpr int GP = kGroupQuads * NT;                 // pieces per group
     static constexpr int RP = 12 * NT;                          // ring pieces (96 KB at W = 256: 3 groups of 32)
     static constexpr int S = RP / GP;                           // groups in the ring
     static constexpr int GPW = GP / 4;                          // LDS-DMA instructions per wave and group
@@ -87,22 +56,20 @@ struct LdsCfg {
     // the workgroup each issuing 8 KB at the same moment the vector-memory path backs up and a DMA's issue outlasts the 64
     // cycles of the MFMA it stands behind. Needs every part of the net to run HS-piece steps (W = 256: 8 and 4 out tiles),
     // so that "step j of the interval" is a compile-time position everywhere in the stream.
-    static constexpr bool kDmaSpread = NF_LDS_DMA_SPREAD && NT == 8 && HS == 4 && (GP / HS) == GPW;
+    static constexpr bool kDmaSpread = NT == 8 && HS == 4 && (GP / HS) == GPW;
     static constexpr int SPG = GP / HS;                         // steps per group (full-width steps)
 };
 
-// The weight stream of one workgroup. Every member but fr / gsrc / rl is wave-uniform (SGPRs).
-// SP1: the step form with ONE piece of side work per MFMA shadow (round 5: inference and backward-data kernels; round 6: the
-// training forward too - with the buffer-form refill it no longer spills: 227 VGPRs, scratch 0).
-template <int NT, bool SP1 = false, bool NEWDMA = false>
+// The weight stream of one workgroup. Every member but fr / voff / rl is wave-uniform (SGPRs).
+// All three ring kernels (inference forward, training forward, backward-data) run the same form: the refill as
+// buffer_load_dwordx4 ... lds (round 5), one DMA per step where the geometry allows it (LdsCfg::kDmaSpread), and ONE piece of
+// side work per MFMA shadow in a four-tile step (round 5; round 6 for the training forward - with the buffer-form refill it no
+// longer spills: 227 VGPRs, scratch 0).
+template <int NT>
 struct WRing {
     using C = LdsCfg<NT>;
-    // NEWDMA (round 5): the refill as buffer_load ... lds, one DMA per step (LdsCfg::kDmaSpread). All three ring kernels use it
-    // (NF_LDS_TRAIN_NEWDMA = 0 restores the round-2 form of the training forward: global_load_lds in a burst behind the boundary step).
-    static constexpr bool kBufDma = NEWDMA && NF_LDS_DMA_BUF;
-    static constexpr bool kSpreadDma = NEWDMA && C::kDmaSpread;
-    const float* gsrc;       // packed + lane*4: this lane's 16 bytes of stream piece 0
-    __amdgpu_buffer_rsrc_t rsrc;   // the packed image as a raw buffer (NF_LDS_DMA_BUF)
+    static constexpr bool kSpreadDma = C::kDmaSpread;
+    __amdgpu_buffer_rsrc_t rsrc;   // the packed image as a raw buffer
     int voff;                // lane * 16: this lane's byte offset inside a piece
     float* ring;             // LDS ring base
     const float* rl;         // ring + lane*4
@@ -114,20 +81,17 @@ struct WRing {
     f32x4 fr[C::HS];         // fragments of the NEXT step (always C::HS pieces from rd; a narrower step uses the first ones)
 
     // This wave's i-th piece of the group being refilled. A wave moves GPW CONSECUTIVE pieces (consecutive in the image
-    // and in the ring), so one address pair serves four of them through the instruction's immediate offset (applied to
-    // the global AND the LDS address): per piece no address arithmetic at all - behind an MFMA that matters, the issue
+    // and in the ring), so one base serves four of them through the instruction's immediate offset (applied to the
+    // global AND the LDS address): per piece no address arithmetic at all - behind an MFMA that matters, the issue
     // of an LDS-DMA plus five scalar and one 64-bit vector instruction did not fit into the 64 cycles of its shadow.
+    // Buffer form (SGPR resource + SGPR piece offset + one 32-bit lane offset): global_load_lds_dwordx4 with its 64-bit
+    // address pair per lane did not fit that shadow either.
     template <int I>
     __device__ __forceinline__ void dma_at() const {
         constexpr int B4 = I / 4;                                // which block of 4 pieces (one base each)
         const int first = wave * C::GPW + 4 * B4;
-        if constexpr (kBufDma) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(ring + (slot * C::GP + first) * kPiece), 16, voff,
-                                                     (src + first) * (kPiece * 4), (I % 4) * kPiece * 4, 0);
-        } else {
-            __builtin_amdgcn_global_load_lds((glb_void_t*)(gsrc + (size_t)(src + first) * kPiece),
-                                             (lds_void_t*)(ring + (slot * C::GP + first) * kPiece), 16, (I % 4) * kPiece * 4, 0);
-        }
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(ring + (slot * C::GP + first) * kPiece), 16, voff,
+                                                 (src + first) * (kPiece * 4), (I % 4) * kPiece * 4, 0);
     }
     __device__ __forceinline__ void dma(int i) const {           // i is a constant after unrolling
         switch (i) {
@@ -154,7 +118,7 @@ struct WRing {
     // are older than EVERY operation of interval i. Hence N = GPW + X is exact, any N <= GPW + X is safe (waits for more than
     // necessary), and N > GPW + X would let a DMA of the group about to be read stay in flight. EXTRA must therefore be a LOWER
     // bound of the stores of every interval that ends in the part (lds_part derives it; it does not depend on the refill form
-    // nor on where inside a step the stores stand - NF_LDS_TRAIN_K0).
+    // nor on where inside a step the stores stand - kTrainStoreK0).
     template <int EXTRA = 0>
     __device__ __forceinline__ void boundary() const {
         static_assert((C::S - 2) * C::GPW + EXTRA <= 63, "vmcnt is a 6-bit counter");
@@ -191,8 +155,8 @@ struct WRing {
     // starts on an exposed ds_read), hoists a whole layer's lazy ReLUs to the front (259 spilled registers) and puts all
     // refill DMAs in front of the MFMAs. The prefetch sits BEHIND the first tile's 4 MFMAs: hipcc answers the first use of
     // `cur` with s_waitcnt lgkmcnt(0), which is free only while the reads of the NEXT step have not been issued yet.
-    // pre() runs before the MFMAs (work the step itself needs), mid() behind the first tile's MFMAs and the prefetch
-    // (work for LATER steps: the next quad's B operands).
+    // pre() runs before the MFMAs (work the step itself needs), mid() behind the prefetch, in an MFMA shadow of its own in a
+    // four-tile step (work for LATER steps: the next quad's B operands).
     // post(k) runs behind MFMA k of the step (training: ONE activation store per MFMA - four stores issued back to back
     // drained the matrix pipe: a global store takes about as long to issue as an MFMA runs).
     // J (kDmaSpread): position of this step in the refill interval that began at the last boundary (0 = the SYNC step itself):
@@ -200,8 +164,8 @@ struct WRing {
     // (J is a constant after unrolling, like dma()'s argument.)
     template <int HSP, bool SYNC, int EXTRA = 0, class PRE, class MID, class MF, class POST>
     __device__ __forceinline__ void step(const int J, PRE&& pre, MID&& mid, MF&& mf, POST&& post) {
-        constexpr bool SPREAD = kSpreadDma;
-        static_assert(!SPREAD || HSP == C::HS, "spread refill: full-width steps");
+        static_assert(!kSpreadDma || HSP == C::HS, "spread refill: full-width steps");
+        constexpr bool kFourTileStep = HSP == 4 && C::HS == 4;  // 16 MFMAs: every step at W = 256, the full-width steps at W = 128
         f32x4 cur[HSP];
 #pragma unroll
         for (int t = 0; t < HSP; ++t) cur[t] = fr[t];
@@ -211,15 +175,16 @@ struct WRing {
         __builtin_amdgcn_sched_barrier(0);
         pre();
         int k = 0;
-        if constexpr (SP1 && HSP == 4 && C::HS == 4) {
-            // Round 5: ONE piece of side work per MFMA shadow. The round-2 form put the whole prefetch (address arithmetic + four
+        if constexpr (kFourTileStep) {
+            // Round 5: ONE piece of side work per MFMA shadow. The round-2 form (the else branch, which still serves the narrow
+            // steps: the W/2-wide views parts at W = 128, all of W = 64) puts the whole prefetch (address arithmetic + four
             // ds_read_b128) and the next quad's operand preparation behind MFMA 3: ten-odd instructions whose issue takes longer
             // than the 64 cycles MFMA 4 needs the pipe for, so MFMA 5 started late (measured: tools/lds_steps.py). Here every
             // MFMA is pinned, tile-major (a dependent MFMA issues when its predecessor leaves the pipe), and its shadow carries at
             // most one of: a refill DMA (SYNC steps: behind MFMAs 0..GPW-1), one fragment read of the next step, the operand
             // preparation. The fragment reads start behind MFMA 3 at the earliest: the first use of `cur` is answered with
             // s_waitcnt lgkmcnt(0), free only while no read of the NEXT step has been issued.
-            constexpr int R0 = (SYNC && !SPREAD) ? (C::GPW > 4 ? C::GPW : 4) : 4;      // first MFMA whose shadow takes a fragment read
+            constexpr int R0 = (SYNC && !kSpreadDma) ? (C::GPW > 4 ? C::GPW : 4) : 4;  // first MFMA whose shadow takes a fragment read
             static_assert(R0 + 4 < 16, "fragment reads and operand preparation fit behind this step's MFMAs");
 #pragma unroll
             for (int t = 0; t < HSP; ++t) {
@@ -227,56 +192,37 @@ struct WRing {
                 for (int e = 0; e < 4; ++e) {
                     mf(t, e, cur[t][e]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (SPREAD ? k == 0 : (SYNC && k < C::GPW)) dma(SPREAD ? J : k);
+                    if (kSpreadDma ? k == 0 : (SYNC && k < C::GPW)) dma(kSpreadDma ? J : k);
                     post(k);
                     if (k >= R0 && k < R0 + 4) fr[k - R0] = lds_read4(rl + (rd + (k - R0)) * kPiece);
-#if NF_LDS_MID_SPLIT
-                    if (k == R0 + 4) mid(-2);                             // operands 0, 1 of the next quad
-                    if (k == R0 + 5) mid(-3);                             // operands 2, 3
-#else
-                    if (k == R0 + 4) mid(-1);
-#endif
+                    if (k == R0 + 4) mid();
                     __builtin_amdgcn_sched_barrier(0);
                     ++k;
                 }
             }
-
         } else {
 #pragma unroll
-        for (int t = 0; t < HSP; ++t) {
+            for (int t = 0; t < HSP; ++t) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                mf(t, e, cur[t][e]);
-                if (SPREAD ? k == 0 : (SYNC && k < C::GPW)) {   // burst form: one refill DMA behind each of the first MFMAs
-                    __builtin_amdgcn_sched_barrier(0);
-                    dma(SPREAD ? J : k);
-                    __builtin_amdgcn_sched_barrier(0);
+                for (int e = 0; e < 4; ++e) {
+                    mf(t, e, cur[t][e]);
+                    if (kSpreadDma ? k == 0 : (SYNC && k < C::GPW)) {   // burst form: one refill DMA behind each of the first MFMAs
+                        __builtin_amdgcn_sched_barrier(0);
+                        dma(kSpreadDma ? J : k);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    post(k);
+                    ++k;
                 }
-                post(k);
-                ++k;
-            }
-            if (NF_LDS_SPREAD == 2 && HSP == 4 && C::HS == 4) {     // the prefetch in two halves: behind tile 0 and behind tile 1
                 if (t == 0) {
                     __builtin_amdgcn_sched_barrier(0);
-                    fr[0] = lds_read4(rl + (rd + 0) * kPiece);
-                    fr[1] = lds_read4(rl + (rd + 1) * kPiece);
-                    __builtin_amdgcn_sched_barrier(0);
-                } else if (t == 1) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    fr[2] = lds_read4(rl + (rd + 2) * kPiece);
-                    fr[3] = lds_read4(rl + (rd + 3) * kPiece);
-                    mid(-1);
+                    prefetch();
+                    mid();
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            } else if (t == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                prefetch();
-                mid(-1);
-                __builtin_amdgcn_sched_barrier(0);
             }
         }
-        }
-        if constexpr (SPREAD) {
+        if constexpr (kSpreadDma) {
             if (J == C::SPG - 1) group_issued();
         } else if (SYNC) {
 #pragma unroll
@@ -348,23 +294,11 @@ __device__ __forceinline__ void lds_part(Ring& st, f32x16 (&acc)[NIN], Hook hook
                 }
             };
             auto pr = [&]() { if (sp == 0) hook(q); };
-            auto mid = [&](int e) {                                  // e < 0: all four operands of the next quad; else operand e only
-                if (sp == SPQ - 1 && q + 1 < NQ) {
-                    if (e == -1) bprep(q + 1, bq[q + 1]);
-                    else if (e < -1) {                               // halves: -2 -> operands 0, 1; -3 -> operands 2, 3
-                        float tmp[4];
-                        bprep(q + 1, tmp);
-                        const int e0 = e == -2 ? 0 : 2;
-                        bq[q + 1][e0] = tmp[e0];
-                        bq[q + 1][e0 + 1] = tmp[e0 + 1];
-                    } else {
-                        float tmp[4];                                // (the three unused elements are dead code after inlining)
-                        bprep(q + 1, tmp);
-                        bq[q + 1][e] = tmp[e];
-                    }
-                }
+            auto mid = [&]() {                                       // all four operands of the next quad
+                if (sp == SPQ - 1 && q + 1 < NQ) bprep(q + 1, bq[q + 1]);
             };
-            constexpr int K0 = 4 * HSP >= 8 ? (4 * HSP >= NF_LDS_TRAIN_K0 + 4 ? NF_LDS_TRAIN_K0 : 4) : 0;   // behind MFMAs 4..7 (a one-tile step has only 0..3)
+            // behind MFMAs kTrainStoreK0 .. + 3 of a four-tile step (a two-tile step has only 0..7: 4..7; a one-tile step 0..3)
+            constexpr int K0 = 4 * HSP >= 8 ? (4 * HSP >= kTrainStoreK0 + 4 ? kTrainStoreK0 : 4) : 0;
             auto post = [&](int k) {
                 if constexpr (!std::is_same<TStore, NoStore>::value) {
                     if (sp == 0 && k >= K0 && k < K0 + 4) {
@@ -439,18 +373,12 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_lds_kernel(MlpArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, j = lane & 31;
     const MlpLayout& L = a.lay;
-#if NF_LDS_RING_FIRST
     // the ring at offset 0: a step's four fragment reads are then ONE address (lane * 16 + ring piece * 1024) + immediates
     // 0 .. 3072 - with the ring behind the constants its last two reads fell outside the 16-bit offset and every step paid a
     // second vector add (580 per tile; vector instructions are never hidden beside the f32 MFMA)
     float* const ring0 = smem;
     float* const cst = smem + C::RP * kPiece;
     float* const park = cst + C::kConstMax + wave * (64 * 4 * C::kParkQuads) + lane * 4;
-#else
-    float* const cst = smem;
-    float* const park = smem + C::kConstMax + wave * (64 * 4 * C::kParkQuads) + lane * 4;
-    float* const ring0 = smem + C::kConstMax + C::kParkFloats;
-#endif
     {   // constant area: biases (one piece per layer), alpha head, rgb head
         const int n = (int)(L.total - L.b_off[0]);
         const float* __restrict__ g = a.packed + L.b_off[0];
@@ -460,8 +388,8 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_lds_kernel(MlpArgs a) {
     const float* const c_alpha = cst + (L.alpha_off - L.b_off[0]);
     const float* const c_rgb = cst + (L.rgb_off - L.b_off[0]);
 
-    WRing<NT, NF_LDS_SPREAD == 1 && (!TRAIN || NF_LDS_TRAIN_SP1), !TRAIN || NF_LDS_TRAIN_NEWDMA> st;
-    st.gsrc = a.packed + lane * 4; st.ring = ring0; st.rl = ring0 + lane * 4;
+    WRing<NT> st;
+    st.ring = ring0; st.rl = ring0 + lane * 4;
     st.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.packed, 0, (int)(L.w_total * 4), 0x00020000);   // raw buffer: the weight range
     st.voff = lane * 16;
     st.total = (int)(L.w_total / kPiece); st.src = 0; st.slot = 0; st.rd = 0; st.wave = wave;
@@ -472,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_lds_kernel(MlpArgs a) {
     // consumed its quads 4k..4k+3, so the 4 LDS reads + 16 accumulator writes of a bias tile hide between its MFMAs
     // instead of standing in front of the next layer (bias loads were 1 % of the register-streamed kernel).
     f32x16 P[NT], Q[NT];
-    constexpr bool VGP = NF_LDS_VGPR_P && !TRAIN && NT == 8;                             // array P in arch VGPRs (experiment)
+    constexpr bool VGP = !TRAIN && NT == 8;                // array P in arch VGPRs (VGPR-form MFMAs by inline asm; inference, W = 256)
     auto bias_tile = [&](f32x16 (&dst)[NT], int l, int t, const bool in_vgpr = false) {  // dst[t] = bias of layer l, tile t
         const float* p = cst + l * kPiece + (t * 2 + h) * 16;
         const f32x4 v0 = lds_read4(p), v1 = lds_read4(p + 4), v2 = lds_read4(p + 8), v3 = lds_read4(p + 12);
@@ -670,8 +598,8 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_bwd_data_lds_kernel(BwdArgs a
     for (int i = tid; i < 3 * OTV * 32; i += 256) c_rgb[i] = P[L.rgb_off + i];
     __syncthreads();
 
-    WRing<NT, NF_LDS_BWD_SP1, true> st;
-    st.gsrc = PT + lane * 4; st.ring = ring0; st.rl = ring0 + lane * 4;
+    WRing<NT> st;
+    st.ring = ring0; st.rl = ring0 + lane * 4;
     st.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)PT, 0, (int)(a.layT.total * 4), 0x00020000);
     st.voff = lane * 16;
     st.total = (int)(a.layT.total / kPiece); st.src = 0; st.slot = 0; st.rd = 0; st.wave = wave;

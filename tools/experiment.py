@@ -29,22 +29,24 @@ LDS_STEPS = [
      '    lds_wait_vmcnt<0>();       // no LDS-DMA may be in flight')]
 
 # name -> (source file, [(old, new), ...], extra compiler flags)
+# The shipped sources carry no compile-time A/B switches: a flag here may only name a macro that the patch text itself introduces.
+# The decided A/B arms of rounds 2-6 (refill form, step form, ring position, split operand preparation, K10 early index, K11
+# occupancy, dW buffer DMA) were removed from the sources by "Settle the compile-time A/B switches in the shipped kernels";
+# they can still be built from the parent of that commit.
 EXPERIMENTS = {
-    # round 4, K11: the per-wave LDS slice doubled = half the waves per CU (how much does the segmented reduce depend on occupancy?)
-    'seg_lds2': ('gauss_csr.hip', [], ['-DNF_SEG_LDS_MULT=2']),
     # (the round-2/3 ablations of the old entry-strided reduce - seg_noscan / _nogather / _noemit / _u16 / _u4 - went with that kernel)
-    'k10_early_index': ('gauss.hip', [], ['-DNF_K10_EARLY_INDEX=1']),   # (until round 6: 'k10_late_index' with =0, the product default)
     'lds_base': ('mlp_lds.hip', [], []),
-    'lds_gpm2': ('mlp_lds.hip', [], ['-DNF_LDS_GPM=2']),
+    # numeric knobs kept as instruments: ring group size (one barrier per 2 quads), position of the training forward's activation
+    # stores (4: round-3 position), point loads in flight in the 8-NN scan
+    'lds_gpm2': ('mlp_lds.hip', [('constexpr int kGroupQuads = 4;', 'constexpr int kGroupQuads = 2;')], []),
+    'lds_train_k4': ('mlp_lds.hip', [('constexpr int kTrainStoreK0 = 8;', 'constexpr int kTrainStoreK0 = 4;')], []),
+    'knn_batch4': ('knn_grid.hip', [('constexpr int kScanBatch = 8;', 'constexpr int kScanBatch = 4;')], []),
     'lds_noenc': ('mlp_lds.hip', [('        encode_sample(a, s, hh, emb, demb);\n',
                                    '        for (int i_ = 0; i_ < 4 * kEmbQuads; ++i_) emb[i_] = 0.25f * (float)(lane & 3) + (float)s * 1e-9f;\n'
                                    '        for (int i_ = 0; i_ < 4 * kDirQuads; ++i_) demb[i_] = 0.5f;\n')], []),
-    'lds_nodma': ('mlp_lds.hip', [('            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(ring + (slot * C::GP + first) * kPiece), 16, voff,\n'
-                                   '                                                     (src + first) * (kPiece * 4), (I % 4) * kPiece * 4, 0);\n',
-                                   '            asm volatile("" :: "s"(first));\n')], []),
-    'lds_dma_global': ('mlp_lds.hip', [], ['-DNF_LDS_DMA_BUF=0']),
-    'lds_dma_burst': ('mlp_lds.hip', [], ['-DNF_LDS_DMA_SPREAD=0']),
-    'lds_dma_global_burst': ('mlp_lds.hip', [], ['-DNF_LDS_DMA_BUF=0', '-DNF_LDS_DMA_SPREAD=0']),
+    'lds_nodma': ('mlp_lds.hip', [('        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(ring + (slot * C::GP + first) * kPiece), 16, voff,\n'
+                                   '                                                 (src + first) * (kPiece * 4), (I % 4) * kPiece * 4, 0);\n',
+                                   '        asm volatile("" :: "s"(first));\n')], []),
     'lds_nobarrier': ('mlp_lds.hip', [('        __builtin_amdgcn_s_barrier();\n        asm volatile("" ::: "memory");\n',
                                        '        asm volatile("" ::: "memory");\n')], []),
     # shader-clock stamps of one tile's phases -> raw[(block*4 + wave)] as 4 uint32 deltas (timing only, outputs destroyed)
@@ -69,8 +71,8 @@ EXPERIMENTS = {
     # [2] ring started, [3 + r] end of round r's tile (r < 12), [15] kernel end; [16 + i]: the shader clock (s_memtime) at the same
     # points i = 2, 3 + r, 15 (tools/lds_timeline.py; outputs destroyed)
     'lds_timeline': ('mlp_lds.hip', [
-        ('    const MlpLayout& L = a.lay;\n#if NF_LDS_RING_FIRST\n',
-         '    const MlpLayout& L = a.lay;\n    const unsigned long long tl0_ = wall_clock64();\n#if NF_LDS_RING_FIRST\n'),
+        ('    const MlpLayout& L = a.lay;\n    // the ring at offset 0:',
+         '    const MlpLayout& L = a.lay;\n    const unsigned long long tl0_ = wall_clock64();\n    // the ring at offset 0:'),
         ('    __syncthreads();\n    const float* const c_alpha = cst + (L.alpha_off - L.b_off[0]);\n',
          '    __syncthreads();\n    const unsigned long long tl1_ = wall_clock64();\n    const float* const c_alpha = cst + (L.alpha_off - L.b_off[0]);\n'),
         ('    st.start();\n\n    // Two activation arrays swap roles',
@@ -120,17 +122,6 @@ EXPERIMENTS = {
     # dumped at kernel end: raw[(block*4 + wave)*66 + lane] = stamp of step (idx - 64 + lane), [64] = idx
     'lds_steps': ('mlp_lds.hip', LDS_STEPS, ['-DNF_ST_LO=27776']),          # the last 64 steps of the last of 48 tiles (8192 x 192 samples)
     'lds_steps_l2': ('mlp_lds.hip', LDS_STEPS, ['-DNF_ST_LO=27340']),       # tile 47, steps 80..143 = pts_linears[2]
-    'lds_spread_steps_l2': ('mlp_lds.hip', LDS_STEPS, ['-DNF_LDS_SPREAD=1', '-DNF_ST_LO=27340']),
-    'lds_agpr_p': ('mlp_lds.hip', [], ['-DNF_LDS_VGPR_P=0']),
-    'lds_ring_last': ('mlp_lds.hip', [], ['-DNF_LDS_RING_FIRST=0']),
-    'bwd_sp0': ('mlp_lds.hip', [], ['-DNF_LDS_BWD_SP1=0']),
-    'lds_train_newdma': ('mlp_lds.hip', [], ['-DNF_LDS_TRAIN_NEWDMA=1']),
-    'lds_midsplit': ('mlp_lds.hip', [], ['-DNF_LDS_MID_SPLIT=1']),
-    # round 6: the training forward on the one-piece-of-side-work-per-shadow step form; activation stores behind MFMAs K0 .. K0 + 3
-    'lds_train_sp1': ('mlp_lds.hip', [], ['-DNF_LDS_TRAIN_SP1=1']),
-    'lds_train_sp1_k8': ('mlp_lds.hip', [], ['-DNF_LDS_TRAIN_SP1=1', '-DNF_LDS_TRAIN_K0=8']),
-    'lds_train_sp1_k12': ('mlp_lds.hip', [], ['-DNF_LDS_TRAIN_SP1=1', '-DNF_LDS_TRAIN_K0=12']),
-    'lds_train_k8': ('mlp_lds.hip', [], ['-DNF_LDS_TRAIN_K0=8']),
     # round 6, the ReLU bit masks of the training forward: the product appends a value's bit with v_cmp_lt_i32 + v_addc_co_u32
     # (bits arrive reversed, one v_bfrev per tile). lds_mask_med3 = the idiom of rounds 3-5 (v_med3_i32 + v_lshl_or_b32): the A/B
     # partner of profiles/r06_train_mask_ab.log (6.836 against 6.782 ms at 786 432 samples; same bits)
@@ -152,9 +143,6 @@ EXPERIMENTS = {
          '                        asm volatile("v_add_co_u32 %0, vcc, %0, %0\\n\\tv_cndmask_b32 %1, 0, %1, vcc" : "+v"(mcur_), "+v"(x_) : : "vcc");\n'
          '                        b[e] = x_;\n'
          '                    }\n')], []),
-    'lds_spread0': ('mlp_lds.hip', [], ['-DNF_LDS_SPREAD=0']),
-    'lds_spread2': ('mlp_lds.hip', [], ['-DNF_LDS_SPREAD=2']),
-    'lds_spread_steps': ('mlp_lds.hip', LDS_STEPS, ['-DNF_LDS_SPREAD=1', '-DNF_ST_LO=27776']),
     # clock probes of the register-streamed forward kernel and of the LDS-staged weight-gradient kernel (tools/fwd_clock.py,
     # tools/dw_balance.py read the stamps; outputs destroyed)
     'fwd_clock': ('mlp.hip', [
@@ -183,7 +171,6 @@ EXPERIMENTS = {
     # pricing of the weight-gradient step loop (mlp_dw.hip): no LDS-DMA / no per-step barrier / no LDS operand reads / no row sums
     'dw_nodma': ('mlp_dw.hip', [('        __builtin_amdgcn_global_load_lds((glb_void_t*)(base + voff[i]),\n                                         (lds_void_t*)(smem + rs * kDwStageFloats + (wave + 4 * i) * 256), 16, 0, 0);\n',
                                  '        asm volatile("" :: "v"(base + voff[i]), "s"(rs));\n')], []),
-    'dw_dma_buf': ('mlp_dw.hip', [], ['-DNF_DW_DMA_BUF=1']),
     'dw_nobarrier': ('mlp_dw.hip', [('                dw_wait_vmcnt<(NS - 3) * G>();                          // this wave\'s pieces of stage s+1 have landed\n                __builtin_amdgcn_s_barrier();',
                                      '                dw_wait_vmcnt<(NS - 3) * G>();                          // this wave\'s pieces of stage s+1 have landed\n')], []),
     'dw_nofetch': ('mlp_dw.hip', [('        R[p][t][hf] = *reinterpret_cast<const f32x4*>(sbase + off);\n', '        if (off == -12345) R[p][t][hf] = *reinterpret_cast<const f32x4*>(sbase + off);\n')], []),
