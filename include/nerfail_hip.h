@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 9
+#define NERFAIL_ABI_VERSION 10
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -497,6 +497,25 @@ int nerfail_cnn_fwd(const float* packed, int num_classes, const float* x, int B,
                     unsigned char* masks, float* logits, void* stream);
 int nerfail_cnn_bwd_data(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
                          const float* d_logits, int B, int H, int W, float* scratch, float* d_x, void* stream);
+
+/* ABI 10. bwd_data for R right-hand sides of ONE forward in one launch chain (DeepFool: the input gradients of up to 8 class
+ * logits of one view, where a batch-1 backward leaves most of the chip idle in the late stages). Slice r of d_x is, bit for
+ * bit, what nerfail_cnn_bwd_data returns for d_logits[r] with the same workspace and masks: the kernels are the same, run
+ * with one grid slice per (r, b), and no sum changes its order. nerfail_cnn_bwd_data is the R = 1 case.
+ *   R >= 1 and R * B <= 65535 (the grid's z dimension carries r * B + b); anything else is NERFAIL_EINVAL, and
+ *   nerfail_cnn_bwd_multi_scratch_bytes returns 0 for it as for an unsupported H x W.
+ * Buffer contract for R > 1 - what is indexed by the image b of the forward and what by the gradient slice r * B + b:
+ *   by b (B images, read only, exactly what nerfail_cnn_fwd wrote for B images):
+ *               workspace (every stage's pooled output, the FC hidden layer) and masks (pool argmax codes);
+ *   by r * B + b (R * B slices):
+ *               d_logits [R,B,num_classes] (read only), d_x [R,B,3,H,W] (every element written), and scratch
+ *               (nerfail_cnn_bwd_multi_scratch_bytes(R, B, H, W) bytes = R x the single backward's; every stage's gradient
+ *               lives there as [R * B, h, w, C] NHWC; contents unspecified on return).
+ * No allocation, no synchronisation, no atomics; inputs are never written, so the call may be repeated. */
+size_t nerfail_cnn_bwd_multi_scratch_bytes(int R, int B, int H, int W);
+int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
+                               const float* d_logits /* [R,B,num_classes] */, int R, int B, int H, int W, float* scratch,
+                               float* d_x /* [R,B,3,H,W] */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -577,6 +577,14 @@ class gauss_net(nn.Module):
         # True: a view that is named (view_ids=) and not yet resident is kept on the device after its first upload - the
         # reference-shaped loop (CPU tensors from a DataLoader every iteration) then pays PCIe once per view, not per step
         self.keep_views_resident = False
+        # logit_gradients' classifier part. None (default) = automatic: a native MyCNN victim gives the input gradients of all
+        # classes in ONE backward pass (MyCNN.input_gradients); every other classifier (timm models, a stock nn.Sequential)
+        # takes one autograd.grad per class. False: the per-class loop for MyCNN too. True: as None for MyCNN; for any other
+        # classifier one autograd.grad with is_grads_batched=True (legacy vmap: measured slower on the stock 800x800 CNN).
+        # Same bits every way. While the batched path is open the last forward's classifier input and raw logits are kept
+        # (with their graph, i.e. MyCNN's saved activations) until the next forward.
+        self.batched_classifier_backward = None
+        self._last_cla_in = self._last_cla = None
         self._eps_minmax = None      # device-side running [min, max] of x_rgb*alpha (GN:89-103), read lazily
 
     # -- resize of the cold tail: torchvision if present (as the reference), else the same bilinear op in torch
@@ -641,6 +649,10 @@ class gauss_net(nn.Module):
         if size is not None:
             cla_x_3channel = self._resize(cla_x_3channel, size)
         cla = self.model(cla_x_3channel)
+        if self._native_batched() and cla.grad_fn is not None:
+            self._last_cla_in, self._last_cla = cla_x_3channel, cla      # for logit_gradients()
+        else:
+            self._last_cla_in = self._last_cla = None
 
         def ori_logits(grad):
             o = ori_img() if callable(ori_img) else ori_img
@@ -679,6 +691,11 @@ class gauss_net(nn.Module):
         else:
             ori_cla, _ = ori_logits(True)
         return cla, ori_cla
+
+    def _native_batched(self):
+        """logit_gradients may take all class gradients from one MyCNN.input_gradients call."""
+        from .MyModel import MyCNN
+        return self.batched_classifier_backward is not False and isinstance(self.model, MyCNN)
 
     def _classifier_is_frozen(self):
         """The automatic logit cache's precondition: the classifier is a pure function of its input and nothing is being
@@ -724,9 +741,12 @@ class gauss_net(nn.Module):
     def logit_gradients(self, spatial_rgb, weight_and_index_list, x, x_rgba, cla, classes):
         """d cla[0, k] / d spatial_rgb for every k in `classes` (<= 8): tensor [len(classes), *spatial_rgb.shape].
 
-        `x, x_rgba, cla` are what forward() just returned for this spatial_rgb (graph still alive). The classifier is
-        differentiated down to x_rgba by stock PyTorch (one backward per class); the pixel<->3-D map - the part the reference pays len(classes) scatter passes for - is one
-        nerfail_gauss_bwd_view_multi call. Each slice is bitwise what autograd through forward() returns."""
+        `x, x_rgba, cla` are what forward() just returned for this spatial_rgb (graph still alive; `cla` may have gone through
+        further differentiable ops, as deepfool's bump). The classifier is differentiated down to x_rgba in one pass when it
+        is a native MyCNN (MyCNN.input_gradients: one multi-right-hand-side backward, then the cheap elementwise ops of the
+        cold tail per class), else by stock PyTorch with one backward per class (see batched_classifier_backward); the
+        pixel<->3-D map - the part the reference pays len(classes) scatter passes for - is one nerfail_gauss_bwd_view_multi
+        call. Each slice is bitwise what autograd through forward() returns."""
         if cla.shape[0] != 1:
             raise ValueError('logit_gradients differentiates one view at a time (deepfool runs at batch 1, AN:82)')
         classes = [int(k) for k in classes]
@@ -735,10 +755,19 @@ class gauss_net(nn.Module):
             raise ValueError('1..8 classes per call')
         sel = torch.zeros((C, 1, cla.shape[1]), dtype=cla.dtype, device=cla.device)
         sel[torch.arange(C), 0, torch.tensor(classes)] = 1.0
-        # classifier part (stock PyTorch / MIOpen): one backward per class. A single batched backward
-        # (is_grads_batched=True) is available with self.batched_classifier_backward = True; on the 800x800 victim CNN
-        # it measured slower (8.9 vs 7.9 ms for 8 classes), so it is off by default.
-        if getattr(self, 'batched_classifier_backward', False):
+        raw, cla_in = self._last_cla, self._last_cla_in
+        if self._native_batched() and raw is not None and _derives_from(cla, raw):
+            # native MyCNN: the class rows are taken back to the classifier's own logits (deepfool's `cla + bump`: unchanged),
+            # go through the classifier in ONE backward pass, and each is carried on to x_rgba through the cold tail's
+            # elementwise ops - the nodes autograd would run per class, on the same values
+            d_raw = sel if cla is raw else torch.stack([torch.autograd.grad(cla, raw, grad_outputs=sel[i], retain_graph=True)[0]
+                                                        for i in range(C)])
+            G = self.model.input_gradients(raw, d_raw)
+            J = torch.stack([torch.autograd.grad(cla_in, x_rgba, grad_outputs=G[i], retain_graph=True)[0] for i in range(C)])
+        # stock PyTorch / MIOpen: one backward per class. A single batched backward (is_grads_batched=True) is available
+        # with self.batched_classifier_backward = True; on the 800x800 stock CNN it measured slower (8.9 vs 7.9 ms for 8
+        # classes).
+        elif self.batched_classifier_backward is True:
             J = torch.autograd.grad(cla, x_rgba, grad_outputs=sel, retain_graph=True, is_grads_batched=True)[0]
         else:
             J = torch.stack([torch.autograd.grad(cla, x_rgba, grad_outputs=sel[i], retain_graph=True)[0] for i in range(C)])
@@ -758,6 +787,16 @@ class gauss_net(nn.Module):
         _lib.check(lib.nerfail_gauss_bwd_view_multi(_lib.dev(ori), _lib.dev(x_c), _lib.dev(J), C, ctypes.byref(st), n, P, eps,
                                                     _lib.dev(scratch), _lib.dev(out), _lib.stream()))
         return out.reshape((C,) + tuple(spatial_rgb.shape))
+
+
+def _derives_from(t, src, depth=4):
+    """`t` is `src` or was computed from it by at most `depth` autograd nodes."""
+    want, level = src.grad_fn, [t.grad_fn]
+    for _ in range(depth + 1):
+        if any(n is want for n in level):
+            return want is not None
+        level = [m for n in level if n is not None for m, _ in n.next_functions]
+    return False
 
 
 class _Compose(torch.autograd.Function):

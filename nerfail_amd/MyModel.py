@@ -4,7 +4,12 @@ Same submodules and parameter shapes, so a reference checkpoint (model/weights/m
 load_state_dict(strict=True): seven stages of 3x3 convolution + ReLU + 2x2 max-pool (3-32-64-128-256-256-128-64
 channels), fc1 1024 -> 512 + ReLU, fc2 512 -> num_classes. The forward and the gradient with respect to the input run on
 libnerfail_hip's cnn kernels (torch.ops.nerfail_mi.cnn_fwd). Weight gradients (training the classifier) are not
-implemented: the attack loops freeze it (AS:281-287), and forward raises if a parameter requires grad under grad mode."""
+implemented: the attack loops freeze it (AS:281-287), and forward raises if a parameter requires grad under grad mode.
+
+MyCNN.input_gradients(logits, d_logits) is the backward for several right-hand sides at once: the input gradients of R
+rows d_logits [R,B,num_classes] of ONE forward in one launch chain (torch.ops.nerfail_mi.cnn_bwd_data_multi), each slice
+bitwise what torch.autograd.grad through forward() gives for that row. DeepFool's inner loop takes the gradients of up to 8
+class logits of one view this way (gauss_net.logit_gradients)."""
 import ctypes
 
 import torch
@@ -34,10 +39,13 @@ class MyCNN(nn.Module):
             ps += [c.weight, c.bias]
         return ps + [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
 
+    def _key(self, ps):
+        return tuple((p.data_ptr(), p._version) for p in ps)
+
     def packed(self):
         """The MFMA weight image (nerfail_cnn_pack), rebuilt when any parameter moves or is written in place."""
         ps = self._params()
-        key = tuple((p.data_ptr(), p._version) for p in ps)
+        key = self._key(ps)
         if self._packed is None or key != self._packed_key:
             dev = ps[0].device
             lib = _lib.load()
@@ -66,3 +74,28 @@ class MyCNN(nn.Module):
         keep = torch.is_grad_enabled() and x.requires_grad
         logits, _, _ = ops.cnn_fwd(self.packed(), x, self.num_classes, keep)
         return logits
+
+    def input_gradients(self, logits, d_logits):
+        """d (sum(logits * d_logits[r])) / d x for every row r, [R,B,3,H,W], in ONE backward pass.
+
+        `logits` is the tensor a grad-enabled forward(x) of this module returned (x requiring grad: the forward that keeps its
+        pool masks), its graph still alive; `d_logits` is [R,B,num_classes]. The forward's workspace and masks are read off
+        that tensor's autograd node: nothing is copied and nothing is kept alive here. Slice r is bitwise
+        torch.autograd.grad(logits, x, d_logits[r], retain_graph=True)[0]."""
+        saved = ops.cnn_fwd_saved(logits)
+        if saved is None:
+            raise RuntimeError('MyCNN.input_gradients: `logits` is not the output of a mask-keeping forward of a MyCNN (a '
+                               'grad-enabled forward of an input that requires grad, its graph not yet freed)')
+        packed, ws, masks, (H, W) = saved
+        if self._packed is None or packed.data_ptr() != self._packed.data_ptr():
+            raise RuntimeError('MyCNN.input_gradients: `logits` did not come from the last weight image of this module '
+                               '(another module\'s forward, or the parameters were written and repacked since)')
+        if self._key(self._params()) != self._packed_key:
+            raise RuntimeError('MyCNN.input_gradients: a parameter was written or moved since the forward that returned '
+                               '`logits`; run the forward again')
+        if not isinstance(d_logits, torch.Tensor) or d_logits.dim() != 3 or tuple(d_logits.shape[1:]) != tuple(logits.shape):
+            raise ValueError('MyCNN.input_gradients: d_logits must be [R,%d,%d] (got %s)'
+                             % (logits.shape[0], logits.shape[1], tuple(getattr(d_logits, 'shape', ()))))
+        if d_logits.shape[0] < 1:
+            raise ValueError('MyCNN.input_gradients: d_logits holds no right-hand side (R = 0)')
+        return ops.cnn_bwd_data_multi(packed, ws, masks, _lib.f32c(d_logits, logits.device), H, W)

@@ -13,6 +13,10 @@
 // A k-unit is 8 k-values: lane half h reads 4 consecutive channels with one ds_read_b128 for each operand, and the unit runs
 // 4 MFMAs per (m-tile, n-tile) pair. No atomics: every output element is written by one lane, sums run in a fixed order.
 // Stage 1's backward (N = 3) and the FC head are small VALU kernels.
+//
+// Multi-RHS backward (nerfail_cnn_bwd_data_multi): R gradients of ONE forward. The backward kernels run one grid slice per
+// (r, b): slice g = r * B + b indexes every gradient buffer (d logits, gp, out, d x), image b = g % B indexes what the
+// forward kept (act, gmask, hidden). R = 1 is the single backward; the order of every sum does not depend on R.
 #include "common.h"
 
 namespace nerfail {
@@ -125,6 +129,7 @@ struct ConvArgs {
     const float* act;          // backward: pooled output (NHWC)
     const unsigned char* gmask;// backward: argmax codes of the forward
     int hin, win, hp, wp;      // stage input and pooled output sizes
+    int B;                     // backward: images of the forward (grid z = r * B + b covers the R right-hand sides)
 };
 
 template <int MODE>
@@ -140,30 +145,31 @@ __device__ __forceinline__ int tap_ofs(int mode, int tap, int tw) {
 
 // Stage one CC-channel slice of the un-pooled, ReLU-masked output gradient at conv positions (gy0 + r, gx0 + c) into LDS
 // (row stride XS floats); positions outside [0, 2 hp) x [0, 2 wp) get 0 (rows and columns the floor pool dropped, halo).
+// gp is read at gradient slice g, act and gmask at image b.
 template <int KC, int CC, int TH, int TW, int XS>
 __device__ __forceinline__ void stage_grad(float* xs, const float* __restrict__ gp, const float* __restrict__ act,
-                                           const unsigned char* __restrict__ gmask, int b, int hp, int wp, int gy0, int gx0,
-                                           int c0) {
+                                           const unsigned char* __restrict__ gmask, int g, int b, int hp, int wp, int gy0,
+                                           int gx0, int c0) {
     const int n8 = npc8(wp);
     for (int idx = threadIdx.x; idx < TH * TW * (CC / 4); idx += 256) {
         const int q4 = idx % (CC / 4), p = idx / (CC / 4);
         const int oy = gy0 + p / TW, ox = gx0 + p % TW;
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (oy >= 0 && ox >= 0 && oy < 2 * hp && ox < 2 * wp) {
             const int pr = oy >> 1, pc = ox >> 1, q = ((oy & 1) << 1) | (ox & 1);
-            const size_t cell = ((size_t)b * hp + pr) * wp + pc;
+            const size_t cell = ((size_t)b * hp + pr) * wp + pc, gcell = ((size_t)g * hp + pr) * wp + pc;
             const int ch = c0 + 4 * q4;
-            const float4 gv = *reinterpret_cast<const float4*>(gp + cell * KC + ch);
+            const float4 gv = *reinterpret_cast<const float4*>(gp + gcell * KC + ch);
             const float4 av = *reinterpret_cast<const float4*>(act + cell * KC + ch);
             const unsigned mk = *reinterpret_cast<const unsigned*>(
                 gmask + ((((size_t)b * hp + pr) * n8 + (pc >> 3)) * 2 + (pc & 1)) * KC + ch);
             const int sh = 2 * ((pc & 7) >> 1);
-            g.x = (((mk >> sh) & 3u) == (unsigned)q && !(av.x <= 0.f)) ? gv.x : 0.f;
-            g.y = (((mk >> (8 + sh)) & 3u) == (unsigned)q && !(av.y <= 0.f)) ? gv.y : 0.f;
-            g.z = (((mk >> (16 + sh)) & 3u) == (unsigned)q && !(av.z <= 0.f)) ? gv.z : 0.f;
-            g.w = (((mk >> (24 + sh)) & 3u) == (unsigned)q && !(av.w <= 0.f)) ? gv.w : 0.f;
+            v.x = (((mk >> sh) & 3u) == (unsigned)q && !(av.x <= 0.f)) ? gv.x : 0.f;
+            v.y = (((mk >> (8 + sh)) & 3u) == (unsigned)q && !(av.y <= 0.f)) ? gv.y : 0.f;
+            v.z = (((mk >> (16 + sh)) & 3u) == (unsigned)q && !(av.z <= 0.f)) ? gv.z : 0.f;
+            v.w = (((mk >> (24 + sh)) & 3u) == (unsigned)q && !(av.w <= 0.f)) ? gv.w : 0.f;
         }
-        *reinterpret_cast<float4*>(xs + p * XS + 4 * q4) = g;
+        *reinterpret_cast<float4*>(xs + p * XS + 4 * q4) = v;
     }
 }
 
@@ -181,7 +187,8 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, h = lane >> 5;
-    const int b = blockIdx.z, n0 = blockIdx.y * NT * 32;
+    const int g = blockIdx.z, b = MODE == 2 ? g % a.B : g;      // gradient slice / image (forward: the same)
+    const int n0 = blockIdx.y * NT * 32;
     int ty0, tx0, gy0, gx0;                                     // tile origin: output units / LDS tile in global coordinates
     if (MODE == 2) {
         const int nx = (a.win + 31) / 32;
@@ -245,7 +252,7 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
                 *reinterpret_cast<float4*>(xs + p * XS) = v;
             }
         } else {
-            stage_grad<KC, CC, TH, TW, XS>(xs, a.gp, a.act, a.gmask, b, a.hp, a.wp, gy0, gx0, c0);
+            stage_grad<KC, CC, TH, TW, XS>(xs, a.gp, a.act, a.gmask, g, b, a.hp, a.wp, gy0, gx0, c0);
         }
         // ---- B tile: ws[n][tap * CC + c] = w[(n0 + n)][tap][c0 + c]
         for (int idx = tid; idx < NT * 32 * TAPS * (CC / 4); idx += 256) {
@@ -300,7 +307,7 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int x = tx0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                        if (x < a.win) a.out[(((size_t)b * a.hin + y) * a.win + x) * NC + co] = acc[mt][nt][i];
+                        if (x < a.win) a.out[(((size_t)g * a.hin + y) * a.win + x) * NC + co] = acc[mt][nt][i];
                     }
                 }
             } else {
@@ -309,20 +316,20 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
                     const float bias = a.bias[co];
                     unsigned code = 0;
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
+                    for (int w4 = 0; w4 < 4; ++w4) {
                         float best = -INFINITY;
                         int bi = 0;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {           // window position j = (dy, dx) row-major; ATen's rule: first max, NaN wins
-                            float v = acc[mt][nt][4 * g + j] + bias;
+                            float v = acc[mt][nt][4 * w4 + j] + bias;
                             v = v < 0.f ? 0.f : v;              // ReLU (NaN stays NaN)
                             if (v > best || __builtin_isnan(v)) {
                                 best = v;
                                 bi = j;
                             }
                         }
-                        code |= (unsigned)bi << (2 * g);
-                        const int pc = tx0 + 2 * g + h;
+                        code |= (unsigned)bi << (2 * w4);
+                        const int pc = tx0 + 2 * w4 + h;
                         if (pc < a.wp) a.out[(((size_t)b * a.hp + pr) * a.wp + pc) * NC + co] = best;
                     }
                     if (a.mask)
@@ -337,12 +344,12 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
 // tile, the masked output gradient of the 18 x 18 footprint x 32 channels in LDS, weights read wave-uniformly. Writes NCHW.
 __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict__ w1raw, const float* __restrict__ gp,
                                                         const float* __restrict__ act, const unsigned char* __restrict__ gmask,
-                                                        float* __restrict__ dx, int hin, int win, int hp, int wp) {
+                                                        float* __restrict__ dx, int hin, int win, int hp, int wp, int B) {
     constexpr int TH = 18, TW = 18, CC = 32, XS = CC + 4;
     __shared__ __attribute__((aligned(16))) float xs[TH * TW * XS];
     const int nx = (win + 15) / 16;
-    const int ty0 = (blockIdx.x / nx) * 16, tx0 = (blockIdx.x % nx) * 16, b = blockIdx.z;
-    stage_grad<32, CC, TH, TW, XS>(xs, gp, act, gmask, b, hp, wp, ty0 - 2, tx0 - 2, 0);
+    const int ty0 = (blockIdx.x / nx) * 16, tx0 = (blockIdx.x % nx) * 16, gs = blockIdx.z, b = gs % B;
+    stage_grad<32, CC, TH, TW, XS>(xs, gp, act, gmask, gs, b, hp, wp, ty0 - 2, tx0 - 2, 0);
     __syncthreads();
     const int ly = threadIdx.x / 16, lx = threadIdx.x % 16;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
@@ -365,7 +372,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
     }
     const int y = ty0 + ly, x = tx0 + lx;
     if (y < hin && x < win) {
-        const size_t plane = (size_t)hin * win, o = (size_t)b * 3 * plane + (size_t)y * win + x;
+        const size_t plane = (size_t)hin * win, o = (size_t)gs * 3 * plane + (size_t)y * win + x;
         dx[o] = s0;
         dx[o + plane] = s1;
         dx[o + 2 * plane] = s2;
@@ -400,30 +407,31 @@ __global__ __launch_bounds__(512) void fc_fwd_kernel(const float* __restrict__ x
     }
 }
 
-// d hidden = (fc2^T d logits) gated by hidden > 0 (NaN passes, as threshold_backward), d x = fc1^T d hidden in NHWC order
+// d hidden = (fc2^T d logits) gated by hidden > 0 (NaN passes, as threshold_backward), d x = fc1^T d hidden in NHWC order.
+// One workgroup per gradient slice g = r * B + b: d logits and d x at g, hidden at image b.
 __global__ __launch_bounds__(1024) void fc_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ hidden,
-                                                      const float* __restrict__ fc1P, const float* __restrict__ w2, int C,
+                                                      const float* __restrict__ fc1P, const float* __restrict__ w2, int C, int B,
                                                       float* __restrict__ dx) {
     __shared__ float dh[kHidden];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int g = blockIdx.x, b = g % B, t = threadIdx.x;
     if (t < kHidden) {
         float s = 0.f;
-        for (int c = 0; c < C; ++c) s = fmaf(dlogits[(size_t)b * C + c], w2[(size_t)c * kHidden + t], s);
+        for (int c = 0; c < C; ++c) s = fmaf(dlogits[(size_t)g * C + c], w2[(size_t)c * kHidden + t], s);
         dh[t] = hidden[(size_t)b * kHidden + t] <= 0.f ? 0.f : s;
     }
     __syncthreads();
     float s = 0.f;
     for (int o = 0; o < kHidden; ++o) s = fmaf(fc1P[(size_t)o * kFlat + t], dh[o], s);
-    dx[(size_t)b * kFlat + t] = s;
+    dx[(size_t)g * kFlat + t] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launches
 template <int MODE, int KC, int NC, int NT, int CC>
-static int launch_conv(const ConvArgs& a, int B, hipStream_t st, const char* name) {
+static int launch_conv(const ConvArgs& a, int Z, hipStream_t st, const char* name) {   // Z: grid slices (B, or R * B)
     unsigned tiles;
     if (MODE == 2) tiles = (unsigned)(((a.win + 31) / 32) * ((a.hin + 7) / 8));
     else tiles = (unsigned)(((a.wp + 7) / 8) * ((a.hp + 7) / 8));
-    conv_stage_kernel<MODE, KC, NC, NT, CC><<<dim3(tiles, NC / (NT * 32), B), dim3(256), 0, st>>>(a);
+    conv_stage_kernel<MODE, KC, NC, NT, CC><<<dim3(tiles, NC / (NT * 32), Z), dim3(256), 0, st>>>(a);
     NF_LAUNCHED(name);
     return 0;
 }
@@ -440,14 +448,14 @@ static int conv_fwd_stage(int s, const ConvArgs& a, int B, hipStream_t st) {
     }
 }
 
-static int conv_bwd_stage(int s, const ConvArgs& a, int B, hipStream_t st) {   // s >= 1: KC = Cout, NC = Cin
+static int conv_bwd_stage(int s, const ConvArgs& a, int Z, hipStream_t st) {   // s >= 1: KC = Cout, NC = Cin
     switch (s) {
-        case 1: return launch_conv<2, 64, 32, 1, 16>(a, B, st, "cnn_conv_bwd_s2");
-        case 2: return launch_conv<2, 128, 64, 2, 16>(a, B, st, "cnn_conv_bwd_s3");
-        case 3: return launch_conv<2, 256, 128, 2, 16>(a, B, st, "cnn_conv_bwd_s4");
-        case 4: return launch_conv<2, 256, 256, 2, 16>(a, B, st, "cnn_conv_bwd_s5");
-        case 5: return launch_conv<2, 128, 256, 2, 16>(a, B, st, "cnn_conv_bwd_s6");
-        default: return launch_conv<2, 64, 128, 2, 16>(a, B, st, "cnn_conv_bwd_s7");
+        case 1: return launch_conv<2, 64, 32, 1, 16>(a, Z, st, "cnn_conv_bwd_s2");
+        case 2: return launch_conv<2, 128, 64, 2, 16>(a, Z, st, "cnn_conv_bwd_s3");
+        case 3: return launch_conv<2, 256, 128, 2, 16>(a, Z, st, "cnn_conv_bwd_s4");
+        case 4: return launch_conv<2, 256, 256, 2, 16>(a, Z, st, "cnn_conv_bwd_s5");
+        case 5: return launch_conv<2, 128, 256, 2, 16>(a, Z, st, "cnn_conv_bwd_s6");
+        default: return launch_conv<2, 64, 128, 2, 16>(a, Z, st, "cnn_conv_bwd_s7");
     }
 }
 
@@ -561,28 +569,34 @@ extern "C" int nerfail_cnn_fwd(const float* packed, int num_classes, const float
     return 0;
 }
 
-extern "C" int nerfail_cnn_bwd_data(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
-                                    const float* d_logits, int B, int H, int W, float* scratch, float* d_x, void* stream) {
+// True when R right-hand sides of a B-image forward fit the grid's z dimension (R * B <= 65535).
+static bool multi_ok(int R, int B) { return R >= 1 && B >= 1 && R <= 65535 && B <= 65535 && (long long)R * B <= 65535; }
+
+extern "C" size_t nerfail_cnn_bwd_multi_scratch_bytes(int R, int B, int H, int W) {
     Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
-                   d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
+    if (!multi_ok(R, B) || !dims_of(H, W, d)) return 0;
+    return (act_floats(d, 0, R * B) + act_floats(d, 1, R * B)) * sizeof(float);
+}
+
+// The backward launch chain for R right-hand sides of one B-image forward (arguments already validated).
+static int bwd_data_launch(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
+                           const float* d_logits, int R, int B, int H, int W, const Dims& d, float* scratch, float* d_x,
+                           void* stream) {
     const PackLayout L = pack_layout(num_classes);
     hipStream_t st = as_stream(stream);
+    const int Z = R * B;                                         // gradient slices: the grid's z (FC head: x) dimension
     const float* acts[kStages];
     const unsigned char* mks[kStages];
     const float* p = workspace;
     const unsigned char* q = masks;
-    for (int s = 0; s < kStages; ++s) {
+    for (int s = 0; s < kStages; ++s) {                          // what the forward kept: B images
         acts[s] = p;
         mks[s] = q;
         p += act_floats(d, s, B);
         q += mask_bytes_of(d, s, B);
     }
-    float* bufs[2] = {scratch, scratch + act_floats(d, 0, B)};   // [0] holds stage outputs 6, 4, 2, 0; [1] stage outputs 5, 3, 1
-    fc_bwd_kernel<<<dim3(B), dim3(kFlat), 0, st>>>(d_logits, p, packed + L.fc1P, packed + L.w2, num_classes, bufs[0]);
+    float* bufs[2] = {scratch, scratch + act_floats(d, 0, Z)};   // [0] holds stage outputs 6, 4, 2, 0; [1] stage outputs 5, 3, 1
+    fc_bwd_kernel<<<dim3(Z), dim3(kFlat), 0, st>>>(d_logits, p, packed + L.fc1P, packed + L.w2, num_classes, B, bufs[0]);
     NF_LAUNCHED("cnn_fc_bwd");
     for (int s = kStages - 1; s >= 1; --s) {
         ConvArgs a = {};
@@ -595,12 +609,37 @@ extern "C" int nerfail_cnn_bwd_data(const float* packed, int num_classes, const 
         a.win = d.win[s];
         a.hp = d.hin[s + 1];
         a.wp = d.win[s + 1];
-        int rc = conv_bwd_stage(s, a, B, st);
+        a.B = B;
+        int rc = conv_bwd_stage(s, a, Z, st);
         if (rc) return rc;
     }
     const unsigned tiles = (unsigned)(((W + 15) / 16) * ((H + 15) / 16));
-    conv1_bwd_kernel<<<dim3(tiles, 1, B), dim3(256), 0, st>>>(packed + L.w1raw, bufs[0], acts[0], mks[0], d_x, H, W, d.hin[1],
-                                                             d.win[1]);
+    conv1_bwd_kernel<<<dim3(tiles, 1, Z), dim3(256), 0, st>>>(packed + L.w1raw, bufs[0], acts[0], mks[0], d_x, H, W, d.hin[1],
+                                                             d.win[1], B);
     NF_LAUNCHED("cnn_conv1_bwd");
     return 0;
+}
+
+// The single backward is the R = 1 case: the same kernels, the same grid, the same bits.
+extern "C" int nerfail_cnn_bwd_data(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
+                                    const float* d_logits, int B, int H, int W, float* scratch, float* d_x, void* stream) {
+    Dims d;
+    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
+    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
+    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
+    NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
+                   d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
+    return bwd_data_launch(packed, num_classes, workspace, masks, d_logits, 1, B, H, W, d, scratch, d_x, stream);
+}
+
+extern "C" int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
+                                          const float* d_logits, int R, int B, int H, int W, float* scratch, float* d_x,
+                                          void* stream) {
+    Dims d;
+    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
+    NF_REQUIRE(multi_ok(R, B), "R and B must be >= 1 with R * B <= 65535 (one grid slice per right-hand side and image)");
+    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
+    NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
+                   d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
+    return bwd_data_launch(packed, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
 }

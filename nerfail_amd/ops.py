@@ -376,11 +376,40 @@ def _(packed, workspace, masks, d_logits, H, W):
     return d_logits.new_empty((d_logits.shape[0], 3, H, W))
 
 
+@custom_op(NS + '::cnn_bwd_data_multi', mutates_args=(), device_types='cuda')
+def cnn_bwd_data_multi(packed: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
+    """cnn_bwd_data for R right-hand sides of ONE cnn_fwd in one launch chain: d_logits [R,B,num_classes] ->
+    [R,B,3,H,W], slice r bitwise cnn_bwd_data(..., d_logits[r], ...). workspace and masks are that forward's (B images)."""
+    lib = _lib.load()
+    if d_logits.dtype != torch.float32:
+        raise TypeError('cnn_bwd_data_multi: d_logits must be float32 (got %s)' % d_logits.dtype)
+    if d_logits.dim() != 3:
+        raise ValueError('cnn_bwd_data_multi: d_logits must be [R,B,num_classes] (got %s)' % (tuple(d_logits.shape),))
+    R, B, C = d_logits.shape
+    if masks.numel() == 0:
+        raise RuntimeError('cnn_bwd_data_multi: the forward kept no masks (cnn_fwd with keep_masks=False)')
+    nb = lib.nerfail_cnn_bwd_multi_scratch_bytes(R, B, H, W)
+    if nb == 0 or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C) or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W):
+        raise ValueError('cnn_bwd_data_multi: unsupported d_logits %s for a %d x %d forward (needs R >= 1, R * B <= 65535 and '
+                         'the workspace and masks of a forward of B images)' % (tuple(d_logits.shape), H, W))
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
+    dx = torch.empty((R, B, 3, H, W), dtype=torch.float32, device=d_logits.device)
+    _chk(lib.nerfail_cnn_bwd_data_multi(_lib.dev(packed), C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits, 'd_logits'), R, B, H, W,
+                                        _lib.dev(scratch), _lib.dev(dx), _s()))
+    return dx
+
+
+@cnn_bwd_data_multi.register_fake
+def _(packed, workspace, masks, d_logits, H, W):
+    return d_logits.new_empty((d_logits.shape[0], d_logits.shape[1], 3, H, W))
+
+
 def _cnn_setup(ctx, inputs, output):
     packed, x, num_classes, keep_masks = inputs
     _, ws, masks = output
     ctx.save_for_backward(packed, ws, masks)
     ctx.hw = (x.shape[2], x.shape[3])
+    ctx.is_cnn_fwd = True                     # how cnn_fwd_saved() knows this node
     ctx.mark_non_differentiable(ws, masks)
 
 
@@ -393,4 +422,18 @@ def _cnn_backward(ctx, g_logits, g_ws, g_masks):
 
 cnn_fwd.register_autograd(_cnn_backward, setup_context=_cnn_setup)
 
-CNN_OPS = ('cnn_fwd', 'cnn_bwd_data')
+
+def cnn_fwd_saved(logits):
+    """(packed, workspace, masks, (H, W)) that the cnn_fwd call which returned `logits` saved for its backward: read off the
+    tensor's autograd node, so nothing is copied and nothing outlives the graph. None when `logits` is not the direct output
+    of a differentiable cnn_fwd, or when its graph was already freed (a backward without retain_graph)."""
+    node = getattr(logits, 'grad_fn', None)
+    if node is None or not getattr(node, 'is_cnn_fwd', False):
+        return None
+    try:
+        packed, ws, masks = node.saved_tensors
+    except RuntimeError:
+        return None
+    return packed, ws, masks, node.hw
+
+CNN_OPS = ('cnn_fwd', 'cnn_bwd_data', 'cnn_bwd_data_multi')

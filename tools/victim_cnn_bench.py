@@ -1,6 +1,12 @@
 """Native (nerfail_amd.MyModel.MyCNN, csrc/cnn.hip) vs stock PyTorch (MIOpen) MyCNN victim, in one session on one GPU:
 forward and forward + input backward at B = 8, 800x800; the NeRFail-S end-to-end iteration and the DeepFool inner loop with
-each victim (the legs of bench_sections.attack_bench). Prints one JSON object. Usage: python tools/victim_cnn_bench.py [--out F]"""
+each victim (the legs of bench_sections.attack_bench). Prints one JSON object. Usage: python tools/victim_cnn_bench.py [--out F]
+
+--multi: only the legs of the multi-right-hand-side backward (nerfail_cnn_bwd_data_multi), three rounds with the arms
+alternated inside each round: the native backward of 8 one-hot rows of one 800x800 forward as eight cnn_bwd_data calls and as
+one cnn_bwd_data_multi call, the single backward at B = 8 beside them (the same MFMA work), and the DeepFool inner loop with
+the MIOpen victim, the native victim forced to one backward per class (batched_classifier_backward = False) and the native
+victim on the automatic setting."""
 import json
 import os
 import sys
@@ -92,15 +98,77 @@ def attack_legs(dev, victims, iters=5):
     return out
 
 
+def deepfool_ms_per_iter(net, inputs):
+    from nerfail_amd.deepfool import deepfool
+    runs = []
+    for _ in range(3):
+        t = time.time()
+        _, n_it, _, _, _ = deepfool(inputs, 1.0, net, num_classes=8, max_iter=6, m1=1e6, m2=30)
+        torch.cuda.synchronize()
+        runs.append((time.time() - t) / max(n_it, 1))
+    return float(np.median(runs)) * 1e3
+
+
+def multi_legs(dev, victims, rounds=3):
+    """The arms of the multi-RHS backward, alternated inside each of `rounds` rounds; per arm the list of per-round values."""
+    import nerfail_amd.ops as O
+    from nerfail_amd.GaussNet import gauss_net
+    from nerfail_amd.deepfool import deepfool
+    m = victims['native']
+    H, W = BS.H, BS.W
+    x = torch.rand((8, 3, H, W), device=dev) * 255
+    _, ws1, mk1 = O.cnn_fwd(m.packed(), x[:1].contiguous(), 8, True)
+    _, ws8, mk8 = O.cnn_fwd(m.packed(), x, 8, True)
+    eye = torch.eye(8, device=dev).reshape(8, 1, 8).contiguous()
+    rows = [eye[k].contiguous() for k in range(8)]
+    d8 = torch.eye(8, device=dev)
+
+    def eight_single():
+        for k in range(8):
+            O.cnn_bwd_data(m.packed(), ws1, mk1, rows[k], H, W)
+
+    def one_multi():
+        O.cnn_bwd_data_multi(m.packed(), ws1, mk1, eye, H, W)
+
+    def single_b8():
+        O.cnn_bwd_data(m.packed(), ws8, mk8, d8, H, W)
+    wi, ori, s_init = BS._attack_inputs(dev, 1, seed=0)
+    inputs = (s_init, wi[:1], ori[:1])
+    nets = {}
+    for name, victim, mode in (('miopen', victims['miopen'], None), ('native_per_class', m, False), ('native_auto', m, None)):
+        net = gauss_net(dev, 0.02, victim, 'my_model', epsilon=None)
+        net.cache_ori_cla = False
+        net.batched_classifier_backward = mode
+        deepfool(inputs, 1.0, net, num_classes=8, max_iter=2, m1=1e6, m2=30)        # warm-up of every shape
+        nets[name] = net
+    torch.cuda.synchronize()
+    out = {'backward_b1_8rhs_eight_cnn_bwd_data_ms': [], 'backward_b1_8rhs_one_cnn_bwd_data_multi_ms': [],
+           'backward_b8_single_cnn_bwd_data_ms': []}
+    out.update({'deepfool_inner_loop_%s_ms_per_iter' % k: [] for k in nets})
+    for _ in range(rounds):
+        out['backward_b1_8rhs_eight_cnn_bwd_data_ms'].append(timed(eight_single) * 1e3)
+        out['backward_b1_8rhs_one_cnn_bwd_data_multi_ms'].append(timed(one_multi) * 1e3)
+        out['backward_b8_single_cnn_bwd_data_ms'].append(timed(single_b8) * 1e3)
+        for k, net in nets.items():
+            out['deepfool_inner_loop_%s_ms_per_iter' % k].append(deepfool_ms_per_iter(net, inputs))
+    out['ranges'] = {k: [min(v), max(v)] for k, v in out.items()}
+    out['note'] = ('per arm: one value per round, arms alternated inside a round; backward legs: median of 5 blocks of 10 calls, '
+                   'backward only, from one kept forward; deepfool legs: median of 3 runs of <= 6 iterations, one view')
+    return out
+
+
 def main():
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     stock = BS.victim_cnn(8).to(dev).requires_grad_(False).eval()
     victims = {'miopen': stock, 'native': native_victim(stock)}
     res = {'device': torch.cuda.get_device_name(0), 'batch': 8, 'size': [BS.H, BS.W]}
-    res.update(classifier_legs(dev, victims))
-    if '--classifier-only' not in sys.argv:
-        res.update(attack_legs(dev, victims))
+    if '--multi' in sys.argv:
+        res.update(multi_legs(dev, victims))
+    else:
+        res.update(classifier_legs(dev, victims))
+        if '--classifier-only' not in sys.argv:
+            res.update(attack_legs(dev, victims))
     line = json.dumps(res)
     print(line)
     if '--out' in sys.argv:
