@@ -13,7 +13,7 @@
 //     32 samples x all W channels (128 accumulator registers in + 128 out at W = 256, which is why
 //     the kernel runs one wave per SIMD with the 512-entry unified VGPR/AGPR file).
 //   * The k order a layer consumes is therefore "whatever the previous accumulator layout holds";
-//     the weights are re-packed ONCE (nerfail_mlp_pack) into that k order and into the A-fragment
+//     the weights are re-packed ONCE (nerfail_mlp_pack, mlp_pack.hip) into that k order and into the A-fragment
 //     lane order, so each weight read is one fully coalesced 16-byte-per-lane load covering 4 MFMA
 //     k-steps. The 2.4 MB image stays L2-resident; all waves stream it in the same order.
 //   * Positional encoding is computed per lane in registers: MFMA step s of the encoding part needs,
@@ -31,174 +31,6 @@ bool mlp_x3_covers(const MlpLayout& L, int W);                                  
 size_t mlp_x3_bytes(const MlpLayout& L, int W);
 int pack_mlp_x3(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s);
 int launch_mlp_x3(const MlpArgs& a, const void* img, int W, hipStream_t s);
-
-// ------------------------------------------------------------------------------------- packing
-// One launch per MFMA layer: writes the A-fragment image [quad][tile][lane][4] and the bias image.
-__global__ void pack_layer_kernel(const float* __restrict__ w, const float* __restrict__ b, int out_f, int in_f,
-                                  int OT, int NT, int emb_col0, int h_col0, int dir_col0, float* __restrict__ wq,
-                                  float* __restrict__ bq, int total_w) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < OT * 32) {   // bias image [OT][2][16]
-        const int t = g / 32, hh = (g / 16) & 1, r = g & 15;
-        const int ch = 32 * t + acc_channel(r, hh);
-        bq[g] = (ch < out_f) ? b[ch] : 0.f;
-    }
-    if (g >= total_w) return;
-    const int e = g & 3, lane = (g >> 2) & 63, rest = g >> 8;
-    const int t = rest % OT;
-    int q = rest / OT;
-    const int hh = lane >> 5, row = 32 * t + (lane & 31);
-    int col = -1;
-    if (emb_col0 >= 0) {
-        if (q < kEmbQuads) { const int c = enc_channel(4 * q + e, hh, 10); col = c < 0 ? -1 : emb_col0 + c; q = -1; }
-        else q -= kEmbQuads;
-    }
-    if (q >= 0 && h_col0 >= 0) {
-        if (q < NT * 4) { const int s = 4 * q + e; col = h_col0 + 32 * (s / 16) + acc_channel(s % 16, hh); q = -1; }
-        else q -= NT * 4;
-    }
-    if (q >= 0 && dir_col0 >= 0) {
-        const int c = enc_channel(4 * q + e, hh, 4); col = c < 0 ? -1 : dir_col0 + c;
-    }
-    wq[g] = (row < out_f && col >= 0) ? w[(long)row * in_f + col] : 0.f;
-}
-
-// All MFMA layers in ONE launch (the image is re-packed after every optimizer step): a table of per-layer
-// descriptors passed by value; a block works on one layer (blockIdx.y), grid-striding over its elements.
-struct PackLayerDesc {
-    const float* w; const float* b;
-    int out_f, in_f, OT, emb0, h0, dir0, total_w;
-    unsigned w_off, b_off;
-};
-struct PackTable { int n, NT; PackLayerDesc l[NERFAIL_MAX_DEPTH + 2]; };
-
-__global__ void pack_all_layers_kernel(PackTable t, float* __restrict__ packed) {
-    const PackLayerDesc& d = t.l[blockIdx.y];
-    const int n = d.total_w > d.OT * 32 ? d.total_w : d.OT * 32;
-    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += gridDim.x * blockDim.x) {
-        if (g < d.OT * 32) {
-            const int tt = g / 32, hh = (g / 16) & 1, r = g & 15;
-            const int ch = 32 * tt + acc_channel(r, hh);
-            packed[d.b_off + g] = (ch < d.out_f) ? d.b[ch] : 0.f;
-        }
-        if (g >= d.total_w) continue;
-        const int e = g & 3, lane = (g >> 2) & 63, rest = g >> 8;
-        const int tt = rest % d.OT;
-        int q = rest / d.OT;
-        const int hh = lane >> 5, row = 32 * tt + (lane & 31);
-        int col = -1;
-        if (d.emb0 >= 0) {
-            if (q < kEmbQuads) { const int c = enc_channel(4 * q + e, hh, 10); col = c < 0 ? -1 : d.emb0 + c; q = -1; }
-            else q -= kEmbQuads;
-        }
-        if (q >= 0 && d.h0 >= 0) {
-            if (q < t.NT * 4) { const int s_ = 4 * q + e; col = d.h0 + 32 * (s_ / 16) + acc_channel(s_ % 16, hh); q = -1; }
-            else q -= t.NT * 4;
-        }
-        if (q >= 0 && d.dir0 >= 0) {
-            const int c = enc_channel(4 * q + e, hh, 4); col = c < 0 ? -1 : d.dir0 + c;
-        }
-        packed[d.w_off + g] = (row < d.out_f && col >= 0) ? d.w[(long)row * d.in_f + col] : 0.f;
-    }
-}
-
-// alpha image [NT][2][16] + bias, rgb image [3][OTV][2][16] + 3 biases
-__global__ void pack_heads_kernel(const float* __restrict__ aw, const float* __restrict__ ab,
-                                  const float* __restrict__ rw, const float* __restrict__ rb, int W,
-                                  float* __restrict__ aq, float* __restrict__ rq) {
-    const int NT = W / 32, OTV = NT / 2;
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < NT * 32) {
-        const int t = g / 32, hh = (g / 16) & 1, r = g & 15;
-        aq[g] = aw[32 * t + acc_channel(r, hh)];
-    } else if (g < NT * 32 + 4) {
-        aq[g] = (g == NT * 32) ? ab[0] : 0.f;
-    }
-    if (g < 3 * OTV * 32) {
-        const int c = g / (OTV * 32), rem = g % (OTV * 32);
-        const int t = rem / 32, hh = (rem / 16) & 1, r = rem & 15;
-        rq[g] = rw[c * (W / 2) + 32 * t + acc_channel(r, hh)];
-    } else if (g < 3 * OTV * 32 + 4) {
-        const int c = g - 3 * OTV * 32;
-        rq[g] = (c < 3) ? rb[c] : 0.f;
-    }
-}
-
-// Training re-packs BOTH images (forward + transposed) after every optimizer step: 1 + 1 + (D + 1) launches of ~5 us each
-// per network were 1.3 % of a training step. One launch instead: blockIdx.y walks the forward layers, then the heads,
-// then the transposed layers ([quad][in-tile t][lane (i = l&31 -> input channel 32t+i, h = l>>5)][e]:
-// W[o = out channel of k-step 4q+e in half h][col0 + 32t + i], as pack_layer_T_kernel in mlp_bwd.hip).
-struct PackTDesc { const float* w; int out_f, in_f, col0, total; unsigned off; };
-struct PackTrainTable {
-    PackTable fwd;
-    int nT, W;
-    const float* aw; const float* ab; const float* rw; const float* rb;
-    unsigned alpha_off, rgb_off;
-    PackTDesc t[NERFAIL_MAX_DEPTH + 2];
-};
-__global__ void pack_train_kernel(PackTrainTable t, float* __restrict__ packed, float* __restrict__ packedT) {
-    const int job = blockIdx.y, NT = t.fwd.NT;
-    const int stride = gridDim.x * blockDim.x, g0 = blockIdx.x * blockDim.x + threadIdx.x;
-    if (job < t.fwd.n) {
-        const PackLayerDesc& d = t.fwd.l[job];
-        const int n = d.total_w > d.OT * 32 ? d.total_w : d.OT * 32;
-        for (int g = g0; g < n; g += stride) {
-            if (g < d.OT * 32) {
-                const int tt = g / 32, hh = (g / 16) & 1, r = g & 15;
-                const int ch = 32 * tt + acc_channel(r, hh);
-                packed[d.b_off + g] = (ch < d.out_f) ? d.b[ch] : 0.f;
-            }
-            if (g >= d.total_w) continue;
-            const int e = g & 3, lane = (g >> 2) & 63, rest = g >> 8;
-            const int tt = rest % d.OT;
-            int q = rest / d.OT;
-            const int hh = lane >> 5, row = 32 * tt + (lane & 31);
-            int col = -1;
-            if (d.emb0 >= 0) {
-                if (q < kEmbQuads) { const int c = enc_channel(4 * q + e, hh, 10); col = c < 0 ? -1 : d.emb0 + c; q = -1; }
-                else q -= kEmbQuads;
-            }
-            if (q >= 0 && d.h0 >= 0) {
-                if (q < NT * 4) { const int s_ = 4 * q + e; col = d.h0 + 32 * (s_ / 16) + acc_channel(s_ % 16, hh); q = -1; }
-                else q -= NT * 4;
-            }
-            if (q >= 0 && d.dir0 >= 0) {
-                const int c = enc_channel(4 * q + e, hh, 4); col = c < 0 ? -1 : d.dir0 + c;
-            }
-            packed[d.w_off + g] = (row < d.out_f && col >= 0) ? d.w[(long)row * d.in_f + col] : 0.f;
-        }
-    } else if (job == t.fwd.n) {
-        const int W = t.W, OTV = NT / 2;
-        float* __restrict__ aq = packed + t.alpha_off;
-        float* __restrict__ rq = packed + t.rgb_off;
-        for (int g = g0; g < NT * 32 + 4 || g < 3 * OTV * 32 + 4; g += stride) {
-            if (g < NT * 32) {
-                const int tt = g / 32, hh = (g / 16) & 1, r = g & 15;
-                aq[g] = t.aw[32 * tt + acc_channel(r, hh)];
-            } else if (g < NT * 32 + 4) {
-                aq[g] = (g == NT * 32) ? t.ab[0] : 0.f;
-            }
-            if (g < 3 * OTV * 32) {
-                const int c = g / (OTV * 32), rem = g % (OTV * 32);
-                const int tt = rem / 32, hh = (rem / 16) & 1, r = rem & 15;
-                rq[g] = t.rw[c * (W / 2) + 32 * tt + acc_channel(r, hh)];
-            } else if (g < 3 * OTV * 32 + 4) {
-                const int c = g - 3 * OTV * 32;
-                rq[g] = (c < 3) ? t.rb[c] : 0.f;
-            }
-        }
-    } else {
-        const PackTDesc& d = t.t[job - t.fwd.n - 1];
-        for (int g = g0; g < d.total; g += stride) {
-            const int e = g & 3, lane = (g >> 2) & 63, rest = g >> 8;
-            const int tt = rest % NT, q = rest / NT;
-            const int s_ = 4 * q + e, hh = lane >> 5;
-            const int o = 32 * (s_ / 16) + acc_channel(s_ % 16, hh);
-            const int i = 32 * tt + (lane & 31);
-            packedT[d.off + g] = (o < d.out_f) ? d.w[(long)o * d.in_f + d.col0 + i] : 0.f;
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------- device side
 template <int NT, bool TRAIN>
@@ -341,15 +173,7 @@ static bool use_lds_kernel(const MlpArgs& a) {
 
 static int launch_mlp(const MlpArgs& a, int W, hipStream_t s) {
     if (use_lds_kernel(a)) return launch_mlp_lds(a, W, s);
-    const long ntiles = (a.M + 31) / 32;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cus) blocks = cus;      // persistent: one 4-wave workgroup per CU, one wave per SIMD
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(mlp_grid_blocks((a.M + 31) / 32)), block(256);      // persistent: one 4-wave workgroup per CU
     const bool train = a.acts != nullptr;
     switch (W) {
         case 256: if (train) nerf_mlp_fwd_kernel<8, true><<<grid, block, 0, s>>>(a); else nerf_mlp_fwd_kernel<8, false><<<grid, block, 0, s>>>(a); break;
@@ -383,107 +207,38 @@ extern "C" int nerfail_mlp_fwd_select(int which) {
     return prev;
 }
 
-extern "C" size_t nerfail_mlp_packed_floats(int D, int W, int skip) {
-    MlpLayout L;
-    return make_layout(D, W, skip, L) ? (size_t)L.total : 0;
+// The forward entry points differ in the form of their input only: sample points + one view direction per ray (pts), an
+// already embedded batch (xemb), or packed rays + depths (rays: the points are formed inside the kernel, pts = o + d * z,
+// RN:381 / :399, instead of being read from a [M,3] tensor that the sampling kernels wrote). `in0` / `in1` are the two input
+// pointers of that form (xemb has one), `acts` asks for the training forward, `use_x3` for the bf16x3 selection with image `x3`.
+enum MlpInput { kInPts, kInEmbedded, kInRays };
+#define MLP_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return NERFAIL_EINVAL; } } while (0)
+static int mlp_fwd_entry(const char* fn, MlpInput form, const float* packed, bool use_x3, const void* x3, int D, int W, int skip,
+                         const float* in0, const float* in1, int64_t M, int spr, float* raw, float* acts, bool need_acts, void* stream) {
+    MLP_REQUIRE(M >= 0, form == kInRays ? "n_rays is negative" : "M is negative");
+    MLP_REQUIRE(form == kInEmbedded || spr >= 1, "samples_per_ray must be positive");
+    MlpArgs a;
+    MLP_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
+    if (form == kInRays) M *= spr;
+    if (M == 0) return NERFAIL_OK;
+    MLP_REQUIRE(packed != nullptr && in0 != nullptr && (form == kInEmbedded || in1 != nullptr) && raw != nullptr &&
+                (!need_acts || acts != nullptr), "NULL pointer");
+    a.packed = packed; a.raw = raw; a.acts = acts; a.M = M; a.spr = form == kInEmbedded ? 1 : spr;
+    a.pts = form == kInPts ? in0 : nullptr; a.viewdirs = form == kInPts ? in1 : nullptr;
+    a.xemb = form == kInEmbedded ? in0 : nullptr;
+    a.rays = form == kInRays ? in0 : nullptr; a.z = form == kInRays ? in1 : nullptr;
+    return use_x3 ? launch_mlp_x3_or(a, x3, W, as_stream(stream)) : launch_mlp(a, W, as_stream(stream));
 }
-
-static int fill_pack_table(const nerfail_mlp_params* p, MlpLayout& L, PackTable& tab) {
-    NF_REQUIRE(p->input_ch == kPtsCh && p->input_ch_views == kDirCh, "only multires=10 / multires_views=4 (63 + 27 channels)");
-    NF_REQUIRE(make_layout(p->D, p->W, p->skip, L), "unsupported (D, W): W in {64,128,256}, 2 <= D <= 16");
-    for (int i = 0; i < p->D; ++i) NF_REQUIRE(p->pts_w[i] != nullptr && p->pts_b[i] != nullptr, "pts_linears pointer is NULL");
-    NF_REQUIRE(p->views_w && p->views_b && p->feature_w && p->feature_b && p->alpha_w && p->alpha_b && p->rgb_w && p->rgb_b,
-               "head pointer is NULL");
-    const int W = p->W, NT = L.NT, OTV = NT / 2;
-    tab.n = p->D + 2; tab.NT = NT;
-    for (int l = 0; l <= p->D + 1; ++l) {
-        const bool emb = l <= p->D - 1 && layer_has_emb(l, L.skip);
-        PackLayerDesc& d = tab.l[l];
-        d.OT = NT; d.emb0 = -1; d.h0 = -1; d.dir0 = -1;
-        if (l < p->D) {
-            d.w = p->pts_w[l]; d.b = p->pts_b[l]; d.out_f = W;
-            d.in_f = (l == 0) ? kPtsCh : (emb ? W + kPtsCh : W);
-            if (emb) d.emb0 = 0;
-            if (l > 0) d.h0 = emb ? kPtsCh : 0;
-        } else if (l == p->D) {
-            d.w = p->feature_w; d.b = p->feature_b; d.out_f = W; d.in_f = W; d.h0 = 0;
-        } else {
-            d.w = p->views_w; d.b = p->views_b; d.out_f = W / 2; d.in_f = W + kDirCh; d.OT = OTV; d.h0 = 0; d.dir0 = W;
-        }
-        d.total_w = (int)L.w_count[l];
-        d.w_off = L.w_off[l]; d.b_off = L.b_off[l];
-    }
-    return NERFAIL_OK;
-}
-
-extern "C" int nerfail_mlp_pack(const nerfail_mlp_params* p, float* packed, void* stream) {
-    NF_REQUIRE(p != nullptr && packed != nullptr, "NULL pointer");
-    MlpLayout L;
-    PackTable tab;
-    const int rc = fill_pack_table(p, L, tab);
-    if (rc != NERFAIL_OK) return rc;
-    hipStream_t s = as_stream(stream);
-    const int W = p->W, NT = L.NT, OTV = NT / 2;
-    pack_all_layers_kernel<<<dim3(64, (unsigned)tab.n), dim3(256), 0, s>>>(tab, packed);
-    NF_LAUNCHED("pack_all_layers_kernel");
-    const int nh = (NT * 32 + 4) > (3 * OTV * 32 + 4) ? (NT * 32 + 4) : (3 * OTV * 32 + 4);
-    pack_heads_kernel<<<dim3((nh + 255) / 256), dim3(256), 0, s>>>(p->alpha_w, p->alpha_b, p->rgb_w, p->rgb_b, W,
-                                                                  packed + L.alpha_off, packed + L.rgb_off);
-    NF_LAUNCHED("pack_heads_kernel");
-    return NERFAIL_OK;
-}
-
-extern "C" int nerfail_mlp_pack_train(const nerfail_mlp_params* p, float* packed, float* packedT, void* stream) {
-    NF_REQUIRE(p != nullptr && packed != nullptr && packedT != nullptr, "NULL pointer");
-    MlpLayout L;
-    PackTrainTable t;
-    const int rc = fill_pack_table(p, L, t.fwd);
-    if (rc != NERFAIL_OK) return rc;
-    MlpLayoutT T;
-    make_layout_T(p->D, L.NT, T);
-    const int W = p->W, NT = L.NT;
-    t.W = W; t.aw = p->alpha_w; t.ab = p->alpha_b; t.rw = p->rgb_w; t.rb = p->rgb_b;
-    t.alpha_off = L.alpha_off; t.rgb_off = L.rgb_off;
-    t.nT = 0;
-    for (int l = 1; l <= p->D + 1; ++l) {
-        PackTDesc& d = t.t[t.nT++];
-        if (l < p->D) {
-            const bool emb = layer_has_emb(l, L.skip);
-            d.w = p->pts_w[l]; d.out_f = W; d.in_f = emb ? W + kPtsCh : W; d.col0 = emb ? kPtsCh : 0;
-        } else if (l == p->D) {
-            d.w = p->feature_w; d.out_f = W; d.in_f = W; d.col0 = 0;
-        } else {
-            d.w = p->views_w; d.out_f = W / 2; d.in_f = W + kDirCh; d.col0 = 0;
-        }
-        d.total = (int)(((l == p->D + 1) ? (NT / 2) * 4 : NT * 4) * NT * 256);
-        d.off = T.w_off[l];
-    }
-    pack_train_kernel<<<dim3(32, (unsigned)(t.fwd.n + 1 + t.nT)), dim3(256), 0, as_stream(stream)>>>(t, packed, packedT);
-    NF_LAUNCHED("pack_train_kernel");
-    return NERFAIL_OK;
-}
+#undef MLP_REQUIRE
 
 extern "C" int nerfail_mlp_fwd(const float* packed, int D, int W, int skip, const float* pts, const float* viewdirs,
                                int64_t M, int samples_per_ray, float* raw, void* stream) {
-    NF_REQUIRE(M >= 0, "M is negative");
-    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && pts != nullptr && viewdirs != nullptr && raw != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = pts; a.viewdirs = viewdirs; a.xemb = nullptr; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = nullptr; a.M = M; a.spr = samples_per_ray;
-    return launch_mlp(a, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInPts, packed, false, nullptr, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_embedded(const float* packed, int D, int W, int skip, const float* x, int64_t M, float* raw,
                                         void* stream) {
-    NF_REQUIRE(M >= 0, "M is negative");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && x != nullptr && raw != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = x; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = nullptr; a.M = M; a.spr = 1;
-    return launch_mlp(a, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInEmbedded, packed, false, nullptr, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
 }
 
 extern "C" size_t nerfail_mlp_train_acts_floats(int D, int W, int64_t M) {
@@ -494,30 +249,12 @@ extern "C" size_t nerfail_mlp_train_acts_floats(int D, int W, int64_t M) {
 
 extern "C" int nerfail_mlp_fwd_train(const float* packed, int D, int W, int skip, const float* pts, const float* viewdirs,
                                      int64_t M, int samples_per_ray, float* raw, float* acts, void* stream) {
-    NF_REQUIRE(M >= 0, "M is negative");
-    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && pts != nullptr && viewdirs != nullptr && raw != nullptr && acts != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = pts; a.viewdirs = viewdirs; a.xemb = nullptr; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = acts; a.M = M; a.spr = samples_per_ray;
-    return launch_mlp(a, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInPts, packed, false, nullptr, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, acts, true, stream);
 }
 
-// north-star form of the two entry points above: the sample points are formed inside the kernel from the packed rays and the
-// depths (pts = o + d * z, RN:381 / :399) instead of being read from a [M,3] tensor that the sampling kernels wrote.
 extern "C" int nerfail_mlp_fwd_rays(const float* packed, int D, int W, int skip, const float* rays, const float* z_vals,
                                     int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
-    NF_REQUIRE(n_rays >= 0, "n_rays is negative");
-    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    const int64_t M = n_rays * samples_per_ray;
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && rays != nullptr && z_vals != nullptr && raw != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = nullptr; a.rays = rays; a.z = z_vals; a.raw = raw; a.acts = acts;
-    a.M = M; a.spr = samples_per_ray;
-    return launch_mlp(a, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInRays, packed, false, nullptr, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
 }
 
 // ---- bf16x3 inference (mlp_x3.hip): the weight stream split once into three bf16 planes; each entry point takes both images
@@ -535,37 +272,15 @@ extern "C" int nerfail_mlp_pack_x3(const float* packed, int D, int W, int skip, 
 
 extern "C" int nerfail_mlp_fwd_x3(const float* packed, const void* x3, int D, int W, int skip, const float* pts,
                                   const float* viewdirs, int64_t M, int samples_per_ray, float* raw, void* stream) {
-    NF_REQUIRE(M >= 0, "M is negative");
-    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && pts != nullptr && viewdirs != nullptr && raw != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = pts; a.viewdirs = viewdirs; a.xemb = nullptr; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = nullptr; a.M = M; a.spr = samples_per_ray;
-    return launch_mlp_x3_or(a, x3, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInPts, packed, true, x3, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_embedded_x3(const float* packed, const void* x3, int D, int W, int skip, const float* x, int64_t M,
                                            float* raw, void* stream) {
-    NF_REQUIRE(M >= 0, "M is negative");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && x != nullptr && raw != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = x; a.rays = nullptr; a.z = nullptr; a.raw = raw; a.acts = nullptr; a.M = M; a.spr = 1;
-    return launch_mlp_x3_or(a, x3, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInEmbedded, packed, true, x3, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_rays_x3(const float* packed, const void* x3, int D, int W, int skip, const float* rays,
                                        const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
-    NF_REQUIRE(n_rays >= 0, "n_rays is negative");
-    NF_REQUIRE(samples_per_ray >= 1, "samples_per_ray must be positive");
-    MlpArgs a;
-    NF_REQUIRE(make_layout(D, W, skip, a.lay), "unsupported (D, W)");
-    const int64_t M = n_rays * samples_per_ray;
-    if (M == 0) return NERFAIL_OK;
-    NF_REQUIRE(packed != nullptr && rays != nullptr && z_vals != nullptr && raw != nullptr, "NULL pointer");
-    a.packed = packed; a.pts = nullptr; a.viewdirs = nullptr; a.xemb = nullptr; a.rays = rays; a.z = z_vals; a.raw = raw; a.acts = acts;
-    a.M = M; a.spr = samples_per_ray;
-    return launch_mlp_x3_or(a, x3, W, as_stream(stream));
+    return mlp_fwd_entry(__func__, kInRays, packed, true, x3, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
 }

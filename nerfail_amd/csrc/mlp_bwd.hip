@@ -5,8 +5,9 @@
 //
 //  1. nerf_mlp_bwd_data_kernel: the backward-data chain dX = W^T dZ, register resident exactly like the
 //     forward: dZ of a layer sits in the accumulator layout (sample on the lane, channel on the register), which
-//     is the B operand of the next (earlier) layer's MFMA with A = a 32-row slab of W^T (packed once by
-//     nerfail_mlp_pack_T). ReLU masks come from the saved post-ReLU activations (h > 0 <=> pre-activation > 0).
+//     is the B operand of the next (earlier) layer's MFMA with A = a 32-row slab of W^T (packed by
+//     nerfail_mlp_pack_T / nerfail_mlp_pack_train, mlp_pack.hip). ReLU masks come from the saved post-ReLU activations
+//     (h > 0 <=> pre-activation > 0).
 //     Every dZ is stored (fragment layout) for kernel 2. No gradient w.r.t. points/dirs is needed (RN:394 detaches
 //     z_samples; rays are data), so the chain stops at layer 1.
 //
@@ -15,20 +16,6 @@
 #include "mlp_layout.h"
 
 namespace nerfail {
-
-// ------------------------------------------------------------------------------------- W^T packing
-// [quad][in-tile t][lane (i = l&31 -> input channel 32t+i, h = l>>5)][e]: W[o = out channel of k-step 4q+e in half h][col0 + 32t + i]
-__global__ void pack_layer_T_kernel(const float* __restrict__ w, int out_f, int in_f, int col0, int NT, int total,
-                                    float* __restrict__ wq) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    const int e = g & 3, lane = (g >> 2) & 63, rest = g >> 8;
-    const int t = rest % NT, q = rest / NT;
-    const int s = 4 * q + e, hh = lane >> 5;
-    const int o = 32 * (s / 16) + acc_channel(s % 16, hh);
-    const int i = 32 * t + (lane & 31);
-    wq[g] = (o < out_f) ? w[(long)o * in_f + col0 + i] : 0.f;
-}
 
 // ------------------------------------------------------------------------------------- backward data
 template <int NT>
@@ -117,18 +104,6 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_bwd_data_kernel(BwdArgs a) {
     }
 }
 
-
-static int cu_count() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        else cus = 256;
-    }
-    return cus;
-}
-
 }  // namespace nerfail
 
 using namespace nerfail;
@@ -147,47 +122,10 @@ extern "C" int nerfail_mlp_bwd_select(int which) {
     return prev;
 }
 
-extern "C" size_t nerfail_mlp_packed_T_floats(int D, int W, int skip) {
-    MlpLayout L;
-    if (!make_layout(D, W, skip, L)) return 0;
-    MlpLayoutT T;
-    make_layout_T(D, L.NT, T);
-    return (size_t)T.total;
-}
-
 extern "C" size_t nerfail_mlp_train_dz_floats(int D, int W, int64_t M) {
     MlpLayout L;
     if (!make_layout(D, W, -1, L) || M < 0) return 0;
     return (size_t)((M + 31) / 32) * make_train_layout(D, W).z_slots * 1024;
-}
-
-extern "C" int nerfail_mlp_pack_T(const nerfail_mlp_params* p, float* packedT, void* stream) {
-    NF_REQUIRE(p != nullptr && packedT != nullptr, "NULL pointer");
-    MlpLayout L;
-    NF_REQUIRE(make_layout(p->D, p->W, p->skip, L), "unsupported (D, W)");
-    MlpLayoutT T;
-    make_layout_T(p->D, L.NT, T);
-    hipStream_t s = as_stream(stream);
-    const int W = p->W, NT = L.NT;
-    for (int l = 1; l <= p->D + 1; ++l) {
-        const float* w;
-        int out_f, in_f, col0 = 0;
-        if (l < p->D) {
-            NF_REQUIRE(p->pts_w[l] != nullptr, "pts_linears pointer is NULL");
-            const bool emb = layer_has_emb(l, L.skip);
-            w = p->pts_w[l]; out_f = W; in_f = emb ? W + kPtsCh : W; col0 = emb ? kPtsCh : 0;
-        } else if (l == p->D) {
-            NF_REQUIRE(p->feature_w != nullptr, "feature_linear pointer is NULL");
-            w = p->feature_w; out_f = W; in_f = W;
-        } else {
-            NF_REQUIRE(p->views_w != nullptr, "views_linears pointer is NULL");
-            w = p->views_w; out_f = W / 2; in_f = W + kDirCh;
-        }
-        const int total = (int)(((l == p->D + 1) ? (NT / 2) * 4 : NT * 4) * NT * 256);
-        pack_layer_T_kernel<<<dim3((total + 255) / 256), dim3(256), 0, s>>>(w, out_f, in_f, col0, NT, total, packedT + T.w_off[l]);
-        NF_LAUNCHED("pack_layer_T_kernel");
-    }
-    return NERFAIL_OK;
 }
 
 extern "C" int nerfail_mlp_bwd_data(const float* packed, const float* packedT, int D, int W, int skip, const float* d_raw,
@@ -211,14 +149,11 @@ extern "C" int nerfail_mlp_bwd_data2(const float* packed0, const float* packedT0
     a.tl = make_train_layout(D, W);
     a.packed = packed0; a.packedT = packedT0; a.packed2 = packed1; a.packedT2 = packedT1; a.split = (M0 + 31) / 32;
     a.d_raw = d_raw; a.acts = acts; a.dz = dz; a.M = M;
-    const long ntiles = (M + 31) / 32;
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cu_count()) blocks = cu_count();
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(mlp_grid_blocks((M + 31) / 32)), block(256);
     hipStream_t s = as_stream(stream);
     a.blocks0 = 0;
     // W = 256, even depth <= 8: the LDS-ring form (mlp_lds.hip); g_bwd_select / NERFAIL_BWD_KERNEL=reg forces the register form
-    if (g_bwd_select != 1 && W == 256 && !(D & 1) && D >= 2 && D <= 8) return launch_bwd_data_lds(a, W, cu_count(), s);
+    if (g_bwd_select != 1 && W == 256 && !(D & 1) && D >= 2 && D <= 8) return launch_bwd_data_lds(a, W, s);
     if (g_bwd_select == 2) { set_error("nerfail_mlp_bwd_data: the LDS-ring kernel does not cover this shape"); return NERFAIL_EINVAL; }
     switch (W) {
         case 256: nerf_mlp_bwd_data_kernel<8><<<grid, block, 0, s>>>(a); break;

@@ -637,17 +637,6 @@ __global__ void dw_zero_kernel(ZeroTable t) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0.f;
 }
 
-static int cu_count_dw() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        else cus = 256;
-    }
-    return cus;
-}
-
 }  // namespace nerfail
 
 using namespace nerfail;
@@ -760,7 +749,7 @@ int plan_dw(int D, int W, int skip, int64_t M0, const nerfail_mlp_params* g0, in
             }
     }
     ka.ngroups = ng; ca.ngroups = ng;
-    long wgs = cu_count_dw();
+    long wgs = mlp_cu_count();
     const long min_units = (long)kTileNs[bf16x3 ? 1 : 0][0] * 4;       // at least ~4 full-layer tiles per workgroup
     if (wgs > ka.cum[ng] / min_units) wgs = ka.cum[ng] / min_units > 0 ? ka.cum[ng] / min_units : 1;
     P.wgs = (int)wgs;
@@ -841,7 +830,7 @@ int launch_dw_reg(int D, int W, int skip, const float* acts, const float* dz, in
         a.group_cost[g] = c;
         a.cum[g + 1] = a.cum[g] + (long)c * a.ntiles;
     }
-    long wgs = cu_count_dw();
+    long wgs = mlp_cu_count();
     if (wgs > a.cum[a.ngroups] / 16) wgs = a.cum[a.ngroups] / 16 > 0 ? a.cum[a.ngroups] / 16 : 1;   // tiny problems
     nerf_mlp_bwd_weights_kernel<<<dim3((unsigned)wgs), dim3(256), 0, stream>>>(a);
     NF_LAUNCHED("nerf_mlp_bwd_weights_kernel");

@@ -82,82 +82,39 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo
 }
 
 // ------------------------------------------------------------------------------------- packing
-// one thread per (k16-step, tile, lane, element j) of ONE layer: writes hi and lo halfs of W[row][col] * 2^10.
-// spc = steps per chunk (1: OT == NT, 2: OT == NT/2); chunk bytes = NT*2 KB either way.
-__global__ void pack_f16_layer_kernel(const float* __restrict__ w, int out_f, int in_f, int OT, int NT, int emb_col0,
-                                      int h_col0, int dir_col0, _Float16* __restrict__ img, int total) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    const int j = g & 7, lane = (g >> 3) & 63, rest = g >> 9;
-    const int t = rest % OT;
-    const int step = rest / OT;
-    int ks = step;
-    const int hh = lane >> 5, row = 32 * t + (lane & 31);
-    int col = -1;
-    if (emb_col0 >= 0) {
-        if (ks < kEmbK16) { const int c = enc_channel(8 * ks + j, hh, 10); col = c < 0 ? -1 : emb_col0 + c; ks = -1; }
-        else ks -= kEmbK16;
-    }
-    if (ks >= 0 && h_col0 >= 0) {
-        if (ks < 2 * NT) { col = h_col0 + 32 * (ks >> 1) + acc_channel(8 * (ks & 1) + j, hh); ks = -1; }
-        else ks -= 2 * NT;
-    }
-    if (ks >= 0 && dir_col0 >= 0) {
-        const int c = enc_channel(8 * ks + j, hh, 4); col = c < 0 ? -1 : dir_col0 + c;
-    }
-    const float v = (row < out_f && col >= 0) ? w[(long)row * in_f + col] * kWScale : 0.f;
+// hi and lo fp16 halfs of v * 2^10 -> img[0] and img[512] (the lo fragment follows its hi fragment)
+__device__ __forceinline__ void store_split(_Float16* __restrict__ img, float w) {
+    const float v = w * kWScale;
     const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    // image position: chunk = step / spc; inside the chunk [step % spc][t][hi|lo][lane][j]
-    const int spc = NT / OT;
-    const long chunk = step / spc;
-    const long in_chunk = ((long)(step % spc) * OT + t) * 2;
-    const long base = (chunk * NT * 2 + in_chunk) * 512 + (lane * 8 + j);    // halfs
-    img[base] = hi;
-    img[base + 512] = lo;
+    img[0] = hi;
+    img[512] = (_Float16)(v - (float)hi);
 }
 
-// the whole image in ONE launch: per-layer descriptors by value, a block row (blockIdx.y) per layer
-struct PackF16Desc { const float* w; int out_f, in_f, OT, emb0, h0, dir0, total; unsigned long dst_halfs; };
+// the whole image in ONE launch: per-layer descriptors by value, a block row (blockIdx.y) per layer; one element per
+// (k16-step ks, tile, lane, j) = k-step 8*ks + j of weight_column(). A layer has NT / OT steps per chunk (1 or 2: the views
+// layer), chunk bytes = NT*2 KB either way; inside the chunk [step % spc][tile][hi|lo][lane][j].
+struct PackF16Desc { MlpLayerDesc d; int total; unsigned long dst_halfs; };
 struct PackF16Table { int n, NT; PackF16Desc l[NERFAIL_MAX_DEPTH + 2]; };
 
 __global__ void pack_f16_all_kernel(PackF16Table t, _Float16* __restrict__ image) {
-    const PackF16Desc& d = t.l[blockIdx.y];
-    _Float16* __restrict__ img = image + d.dst_halfs;
-    const int NT = t.NT, OT = d.OT;
-    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < d.total; g += gridDim.x * blockDim.x) {
+    const MlpLayerDesc& d = t.l[blockIdx.y].d;
+    _Float16* __restrict__ img = image + t.l[blockIdx.y].dst_halfs;
+    const int NT = t.NT, OT = d.OT, spc = NT / OT;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < t.l[blockIdx.y].total; g += gridDim.x * blockDim.x) {
         const int j = g & 7, lane = (g >> 3) & 63, rest = g >> 9;
-        const int tt = rest % OT;
-        const int step = rest / OT;
-        int ks = step;
-        const int hh = lane >> 5, row = 32 * tt + (lane & 31);
-        int col = -1;
-        if (d.emb0 >= 0) {
-            if (ks < kEmbK16) { const int c = enc_channel(8 * ks + j, hh, 10); col = c < 0 ? -1 : d.emb0 + c; ks = -1; }
-            else ks -= kEmbK16;
-        }
-        if (ks >= 0 && d.h0 >= 0) {
-            if (ks < 2 * NT) { col = d.h0 + 32 * (ks >> 1) + acc_channel(8 * (ks & 1) + j, hh); ks = -1; }
-            else ks -= 2 * NT;
-        }
-        if (ks >= 0 && d.dir0 >= 0) {
-            const int c = enc_channel(8 * ks + j, hh, 4); col = c < 0 ? -1 : d.dir0 + c;
-        }
-        const float v = (row < d.out_f && col >= 0) ? d.w[(long)row * d.in_f + col] * kWScale : 0.f;
-        const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)(v - (float)hi);
-        const int spc = NT / OT;
+        const int tt = rest % OT, step = rest / OT;
+        const int row = 32 * tt + (lane & 31);
+        const int col = weight_column(d.emb0, d.h0, d.dir0, NT, 8 * step + j, lane >> 5);
         const long chunk = step / spc;
         const long in_chunk = ((long)(step % spc) * OT + tt) * 2;
-        const long base = (chunk * NT * 2 + in_chunk) * 512 + (lane * 8 + j);
-        img[base] = hi;
-        img[base + 512] = lo;
+        store_split(img + (chunk * NT * 2 + in_chunk) * 512 + (lane * 8 + j),
+                    (row < d.out_f && col >= 0) ? d.w[(long)row * d.in_f + col] : 0.f);
     }
 }
 
 // ------------------------------------------------------------------------------------- forward kernel
 struct F16Args {
-    const float* packed;        // fp32 image of mlp.hip: biases and the alpha / rgb head weights
+    const float* packed;        // fp32 image (mlp_pack.hip): biases and the alpha / rgb head weights
     const u32x4* img;           // fp16 hi/lo image
     const float* pts;
     const float* viewdirs;
@@ -474,22 +431,16 @@ static void make_f16_layout_T(int D, int NT, F16LayoutT& L) {
     L.total_chunks = c;
 }
 
-// one thread per (k16-step, in-tile, lane, j): A[row = input channel 32t + lane&31][k = out channel of slot (ks, hh, j)]
-__global__ void pack_f16_layer_T_kernel(const float* __restrict__ w, int out_f, int in_f, int col0, int NT,
-                                        _Float16* __restrict__ img, int total) {
+// one thread per (k16-step, in-tile, lane, j): A[row = input channel 32t + lane&31][k = out channel of k-step 8*ks + j]
+__global__ void pack_f16_layer_T_kernel(MlpLayerDesc d, int NT, _Float16* __restrict__ img, int total) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
     const int j = g & 7, lane = (g >> 3) & 63, rest = g >> 9;
     const int t = rest % NT, ks = rest / NT;
-    const int hh = lane >> 5;
-    const int o = 32 * (ks >> 1) + acc_channel(8 * (ks & 1) + j, hh);
+    const int o = hidden_channel(8 * ks + j, lane >> 5);
     const int i = 32 * t + (lane & 31);
-    const float v = (o < out_f) ? w[(long)o * in_f + col0 + i] * kWScale : 0.f;
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    const long base = ((long)ks * NT * 2 + (long)t * 2) * 512 + (lane * 8 + j);
-    img[base] = hi;
-    img[base + 512] = lo;
+    store_split(img + ((long)ks * NT * 2 + (long)t * 2) * 512 + (lane * 8 + j),
+                (o < d.out_f) ? d.w[(long)o * d.in_f + d.h0 + i] : 0.f);
 }
 
 struct F16BwdArgs {
@@ -661,10 +612,11 @@ extern "C" size_t nerfail_mlp_f16_image_bytes(int D, int W, int skip) {
 extern "C" int nerfail_mlp_pack_f16(const nerfail_mlp_params* p, void* image, void* stream) {
     NF_REQUIRE(p != nullptr && image != nullptr, "NULL pointer");
     NF_REQUIRE(p->input_ch == kPtsCh && p->input_ch_views == kDirCh, "only multires=10 / multires_views=4 (63 + 27 channels)");
+    MlpLayout M;
     F16Layout L;
-    NF_REQUIRE(make_f16_layout(p->D, p->W, p->skip, L), "unsupported (D, W)");
+    NF_REQUIRE(make_layout(p->D, p->W, p->skip, M) && make_f16_layout(p->D, p->W, p->skip, L), "unsupported (D, W)");
     hipStream_t s = as_stream(stream);
-    const int W = p->W, NT = L.NT, OTV = NT / 2;
+    const int NT = L.NT;
     {   // padding chunks must be zero (they are streamed, never multiplied, but keep the image deterministic)
         hipError_t e = hipMemsetAsync(image, 0, (size_t)L.total_chunks * NT * 2 * 64 * 16, s);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
@@ -672,28 +624,10 @@ extern "C" int nerfail_mlp_pack_f16(const nerfail_mlp_params* p, void* image, vo
     PackF16Table tab;
     tab.n = p->D + 2; tab.NT = NT;
     for (int l = 0; l <= p->D + 1; ++l) {
-        const bool emb = l <= p->D - 1 && layer_has_emb(l, L.skip);
-        PackF16Desc& d = tab.l[l];
-        d.OT = NT; d.emb0 = -1; d.h0 = -1; d.dir0 = -1;
-        if (l < p->D) {
-            NF_REQUIRE(p->pts_w[l] != nullptr, "pts_linears pointer is NULL");
-            d.w = p->pts_w[l]; d.out_f = W;
-            d.in_f = (l == 0) ? kPtsCh : (emb ? W + kPtsCh : W);
-            if (emb) d.emb0 = 0;
-            if (l > 0) d.h0 = emb ? kPtsCh : 0;
-        } else if (l == p->D) {
-            NF_REQUIRE(p->feature_w != nullptr, "feature_linear pointer is NULL");
-            d.w = p->feature_w; d.out_f = W; d.in_f = W; d.h0 = 0;
-        } else {
-            NF_REQUIRE(p->views_w != nullptr, "views_linears pointer is NULL");
-            d.w = p->views_w; d.out_f = W / 2; d.in_f = W + kDirCh; d.OT = OTV; d.h0 = 0; d.dir0 = W;
-        }
-        int k16 = 0;
-        if (d.emb0 >= 0) k16 += kEmbK16;
-        if (d.h0 >= 0) k16 += 2 * NT;
-        if (d.dir0 >= 0) k16 += kDirK16;
-        d.total = k16 * d.OT * 512;                      // one element per (k16-step, tile, lane, j)
-        d.dst_halfs = (unsigned long)L.chunk0[l] * NT * 2 * 512;
+        const MlpLayerDesc d = mlp_layer(p, M, l);
+        NF_REQUIRE(d.w != nullptr, mlp_layer_null_msg(M, l));
+        const int k16 = (d.emb0 >= 0 ? kEmbK16 : 0) + (d.h0 >= 0 ? 2 * NT : 0) + (d.dir0 >= 0 ? kDirK16 : 0);
+        tab.l[l] = {d, k16 * d.OT * 512, (unsigned long)L.chunk0[l] * NT * 2 * 512};     // one element per (k16-step, tile, lane, j)
     }
     pack_f16_all_kernel<<<dim3(64, (unsigned)tab.n), dim3(256), 0, s>>>(tab, reinterpret_cast<_Float16*>(image));
     NF_LAUNCHED("pack_f16_all_kernel");
@@ -701,15 +635,7 @@ extern "C" int nerfail_mlp_pack_f16(const nerfail_mlp_params* p, void* image, vo
 }
 
 static int launch_f16(F16Args& a, int W, hipStream_t s) {
-    const long ntiles = (a.M + 31) / 32;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cus) blocks = cus;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(mlp_grid_blocks((a.M + 31) / 32)), block(256);
     const size_t lds = 0;                                           // ring and parking lot are static LDS of the kernel
     const bool train = a.acts != nullptr;
     switch (W) {
@@ -759,31 +685,19 @@ extern "C" size_t nerfail_mlp_f16_image_T_bytes(int D, int W, int skip) {
 
 extern "C" int nerfail_mlp_pack_f16_T(const nerfail_mlp_params* p, void* image, void* stream) {
     NF_REQUIRE(p != nullptr && image != nullptr, "NULL pointer");
+    MlpLayout M;
     F16Layout L;
-    NF_REQUIRE(make_f16_layout(p->D, p->W, p->skip, L), "unsupported (D, W)");
+    NF_REQUIRE(make_layout(p->D, p->W, p->skip, M) && make_f16_layout(p->D, p->W, p->skip, L), "unsupported (D, W)");
     F16LayoutT T;
     make_f16_layout_T(p->D, L.NT, T);
-    hipStream_t s = as_stream(stream);
-    const int W = p->W, NT = L.NT;
-    for (int part = 0; part <= p->D; ++part) {
-        const float* w;
-        int out_f, in_f, col0 = 0;
-        if (part == 0) {
-            NF_REQUIRE(p->views_w != nullptr, "views_linears pointer is NULL");
-            w = p->views_w; out_f = W / 2; in_f = W + kDirCh;
-        } else if (part == 1) {
-            NF_REQUIRE(p->feature_w != nullptr, "feature_linear pointer is NULL");
-            w = p->feature_w; out_f = W; in_f = W;
-        } else {
-            const int l = p->D - 1 - (part - 2);           // pts layer D-1 .. 1
-            NF_REQUIRE(p->pts_w[l] != nullptr, "pts_linears pointer is NULL");
-            const bool emb = layer_has_emb(l, L.skip);
-            w = p->pts_w[l]; out_f = W; in_f = emb ? W + kPtsCh : W; col0 = emb ? kPtsCh : 0;
-        }
-        const int k16 = (part == 0) ? 2 * (NT / 2) : 2 * NT;
-        const int total = k16 * NT * 512;
-        pack_f16_layer_T_kernel<<<dim3((total + 255) / 256), dim3(256), 0, s>>>(
-            w, out_f, in_f, col0, NT, reinterpret_cast<_Float16*>(image) + (size_t)T.chunk0[part] * NT * 2 * 512, total);
+    const int NT = L.NT;
+    for (int part = 0; part <= p->D; ++part) {               // backward order: views, feature, pts layer D-1 .. 1
+        const int l = p->D + 1 - part;
+        const MlpLayerDesc d = mlp_layer(p, M, l);
+        NF_REQUIRE(d.w != nullptr, mlp_layer_null_msg(M, l));
+        const int total = 2 * d.OT * NT * 512;               // 2 k16-steps per out tile
+        pack_f16_layer_T_kernel<<<dim3((total + 255) / 256), dim3(256), 0, as_stream(stream)>>>(
+            d, NT, reinterpret_cast<_Float16*>(image) + (size_t)T.chunk0[part] * NT * 2 * 512, total);
         NF_LAUNCHED("pack_f16_layer_T_kernel");
     }
     return NERFAIL_OK;
@@ -802,15 +716,7 @@ extern "C" int nerfail_mlp_bwd_data_f16(const float* packed, const void* imageT,
     a.tl = make_train_layout(D, W);
     a.packed = packed; a.imgT = reinterpret_cast<const u32x4*>(imageT); a.d_raw = d_raw; a.acts = acts; a.dz = dz; a.M = M;
     a.total_chunks = T.total_chunks;
-    const long ntiles = (M + 31) / 32;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cus) blocks = cus;
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(mlp_grid_blocks((M + 31) / 32)), block(256);
     const size_t lds = (size_t)2 * a.lay.NT * 2 * 64 * 16;
     hipStream_t s = as_stream(stream);
     switch (W) {

@@ -22,7 +22,27 @@ __host__ __device__ inline int enc_channel(int s, int h, int bands) {
 // Channel of a 32-channel accumulator tile held in register r of lane half h (32x32 C/D layout).
 __host__ __device__ inline int acc_channel(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// Packed f32 image (nerfail_mlp_pack), in 1 KB "pieces" of 256 floats:
+// Output channel of k-step s of a hidden part in lane half h: the accumulator tiles of the producing layer, 16 steps per
+// tile. The k map of the TRANSPOSED weight images (W^T: k = out channel) and the hidden part of the forward map below.
+__host__ __device__ inline int hidden_channel(int s, int h) { return 32 * (s / 16) + acc_channel(s % 16, h); }
+// THE forward column map, the contract between every weight packer and every MLP kernel: the nn.Linear column that k-step s
+// of a layer multiplies in lane half h, -1 = zero padding. A layer's k-steps are its encoding part (32 steps, present when
+// emb0 >= 0), its hidden part (16*NT steps, h0 >= 0) and its view-direction part (16 steps, dir0 >= 0), in this order;
+// emb0 / h0 / dir0 = first column of that part in the weight matrix (MlpLayerDesc below).
+__host__ __device__ inline int weight_column(int emb0, int h0, int dir0, int NT, int s, int h) {
+    if (emb0 >= 0) {
+        if (s < 4 * kEmbQuads) { const int c = enc_channel(s, h, 10); return c < 0 ? -1 : emb0 + c; }
+        s -= 4 * kEmbQuads;
+    }
+    if (h0 >= 0) {
+        if (s < 16 * NT) return h0 + hidden_channel(s, h);
+        s -= 16 * NT;
+    }
+    if (dir0 >= 0) { const int c = enc_channel(s, h, 4); return c < 0 ? -1 : dir0 + c; }
+    return -1;
+}
+
+// Packed f32 image (nerfail_mlp_pack, mlp_pack.hip), in 1 KB "pieces" of 256 floats:
 //   [0, w_total)        the WEIGHT STREAM: layer after layer in consumption order (pts_linears 0..D-1, feature_linear,
 //                       views_linears), each layer [quad][out-tile][lane][4] = A fragments, one piece per (quad, tile);
 //                       padded at the end to a whole number of ring groups (4*NT pieces) - the LDS-streaming forward
@@ -68,6 +88,44 @@ static bool make_layout(int D, int W, int skip, MlpLayout& L) {
     return true;
 }
 
+// Layer l of the MFMA stack as every packer sees it: [0..D-1] pts_linears, [D] feature_linear, [D+1] views_linears[0].
+// OT = 32-row out tiles; emb0 / h0 / dir0 as weight_column() takes them (the transposed packers read h0 as the first column
+// of the part they transpose). Describes the layer; what a packer refuses (NULL tensors, ...) is the packer's business.
+struct MlpLayerDesc { const float* w; const float* b; int out_f, in_f, OT, emb0, h0, dir0; };
+static inline MlpLayerDesc mlp_layer(const nerfail_mlp_params* p, const MlpLayout& L, int l) {
+    const int W = 32 * L.NT;
+    MlpLayerDesc d = {p->feature_w, p->feature_b, W, W, L.NT, -1, 0, -1};
+    if (l < L.D) {
+        const bool emb = layer_has_emb(l, L.skip);
+        d.w = p->pts_w[l]; d.b = p->pts_b[l];
+        d.emb0 = emb ? 0 : -1;
+        d.h0 = l == 0 ? -1 : (emb ? kPtsCh : 0);
+        d.in_f = (emb ? kPtsCh : 0) + (l == 0 ? 0 : W);
+    } else if (l == L.D + 1) {
+        d.w = p->views_w; d.b = p->views_b; d.out_f = W / 2; d.in_f = W + kDirCh; d.OT = L.NT / 2; d.dir0 = W;
+    }
+    return d;
+}
+static inline const char* mlp_layer_null_msg(const MlpLayout& L, int l) {
+    return l < L.D ? "pts_linears pointer is NULL" : (l == L.D ? "feature_linear pointer is NULL" : "views_linears pointer is NULL");
+}
+
+// Launch geometry of every persistent MLP kernel: one 4-wave workgroup (4 tiles of 32 samples per round) per CU, one wave per
+// SIMD, never more workgroups than rounds. The CU count is asked once per process.
+inline int mlp_cu_count() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+        else cus = 256;
+    }
+    return cus;
+}
+inline unsigned mlp_grid_blocks(long ntiles) {
+    const long blocks = (ntiles + 3) / 4;
+    return (unsigned)(blocks > mlp_cu_count() ? mlp_cu_count() : blocks);
+}
 
 // ---- training buffers: [32-sample tile][slot][32 channels][32 samples] ("channel-major tiles") -----------
 // A "slot" is one 32-channel x 32-sample tile, 4 KB, element (channel c, sample j) at float offset c*32 + j.
@@ -198,7 +256,7 @@ struct BwdArgs {
     MlpLayoutT layT;
     TrainLayout tl;
 };
-int launch_bwd_data_lds(const BwdArgs& a, int W, int cus, hipStream_t s);      // mlp_lds.hip; NERFAIL_EINVAL when the shape is not covered
+int launch_bwd_data_lds(const BwdArgs& a, int W, hipStream_t s);      // mlp_lds.hip; NERFAIL_EINVAL when the shape is not covered
 
 // ---- device helpers shared by the forward and backward kernels -------------------------------------------
 template <int OT>

@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_bwd_data_lds_kernel(BwdArgs a
     lds_wait_vmcnt<0>();       // (the ring's last DMAs have landed before the LDS is released)
 }
 
-int launch_bwd_data_lds(const BwdArgs& a, int W, int cus, hipStream_t s) {
+int launch_bwd_data_lds(const BwdArgs& a, int W, hipStream_t s) {
     using C = LdsCfg<8>;
     const long ntiles = (a.M + 31) / 32, t0 = a.split, t1 = ntiles - a.split;
     if (W != 256 || (a.lay.D & 1) || a.lay.D < 2 || a.lay.D > C::kMaxDepth || (a.layT.total / kPiece) % C::GP != 0 ||
@@ -723,8 +723,7 @@ int launch_bwd_data_lds(const BwdArgs& a, int W, int cus, hipStream_t s) {
         return NERFAIL_EINVAL;
     }
     // workgroups per network in proportion to its tiles (at least one where there are tiles, whole 4-tile rounds)
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cus) blocks = cus;
+    long blocks = mlp_grid_blocks(ntiles);
     long b0 = t1 == 0 ? blocks : (t0 == 0 ? 0 : (blocks * t0 + ntiles / 2) / ntiles);
     if (t0 > 0 && b0 < 1) b0 = 1;
     if (t1 > 0 && b0 > blocks - 1) b0 = blocks - 1;
@@ -766,18 +765,11 @@ static int launch_lds(const MlpArgs& a, unsigned blocks, hipStream_t s) {
 
 int launch_mlp_lds(const MlpArgs& a, int W, hipStream_t s) {
     if (a.M >= (1L << 36)) { set_error("nerfail_mlp_fwd: M must be below 2^36 samples per call"); return NERFAIL_EINVAL; }
-    const long ntiles = (a.M + 31) / 32;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cus) blocks = cus;      // persistent: one 4-wave workgroup per CU, one wave per SIMD
+    const unsigned blocks = mlp_grid_blocks((a.M + 31) / 32);      // persistent: one 4-wave workgroup per CU
     switch (W) {
-        case 256: return launch_lds<8>(a, (unsigned)blocks, s);
-        case 128: return launch_lds<4>(a, (unsigned)blocks, s);
-        case 64: return launch_lds<2>(a, (unsigned)blocks, s);
+        case 256: return launch_lds<8>(a, blocks, s);
+        case 128: return launch_lds<4>(a, blocks, s);
+        case 64: return launch_lds<2>(a, blocks, s);
         default: set_error("nerfail_mlp_fwd: unsupported W"); return NERFAIL_EINVAL;
     }
 }

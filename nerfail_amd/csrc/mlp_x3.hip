@@ -505,15 +505,7 @@ int launch_mlp_x3(const MlpArgs& a, const void* img, int W, hipStream_t s) {
     X3Layout X;
     if (!mlp_x3_covers(a.lay, W) || !make_x3_layout(a.lay, W, X)) { set_error("nerf_mlp_fwd_x3_kernel: shape not covered (W = 256, even D <= 8)"); return NERFAIL_EINVAL; }
     if (a.M >= (1L << 36)) { set_error("nerfail_mlp_fwd: M must be below 2^36 samples per call"); return NERFAIL_EINVAL; }
-    const long ntiles = (a.M + 31) / 32;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    long blocks = (ntiles + 3) / 4;
-    if (blocks > cus) blocks = cus;      // persistent: one 4-wave workgroup per CU, one wave per SIMD
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(mlp_grid_blocks((a.M + 31) / 32)), block(256);      // persistent: one 4-wave workgroup per CU
     const int skip_layer = a.lay.skip >= 0 ? a.lay.skip + 1 : -1;
     if (skip_layer < 0) nerf_mlp_fwd_x3_kernel<8, 0><<<grid, block, 0, s>>>(a, img, (int)X.pieces);
     else if (skip_layer & 1) nerf_mlp_fwd_x3_kernel<8, 1><<<grid, block, 0, s>>>(a, img, (int)X.pieces);

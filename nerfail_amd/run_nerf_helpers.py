@@ -135,21 +135,8 @@ class NeRF(nn.Module):
         n = lib.nerfail_mlp_packed_floats(self.D, self.W, self._skip())
         if n == 0:
             raise NotImplementedError('unsupported NeRF shape D=%d W=%d (W in {64,128,256})' % (self.D, self.W))
-        mp = _lib.MlpParams()
-        mp.D, mp.W, mp.input_ch, mp.input_ch_views, mp.skip = self.D, self.W, self.input_ch, self.input_ch_views, self._skip()
         keep = []
-
-        def ptr(t):
-            t = _lib.f32c(t)
-            keep.append(t)
-            return t.data_ptr()
-        for i, l in enumerate(self.pts_linears):
-            mp.pts_w[i] = ptr(l.weight)
-            mp.pts_b[i] = ptr(l.bias)
-        mp.views_w, mp.views_b = ptr(self.views_linears[0].weight), ptr(self.views_linears[0].bias)
-        mp.feature_w, mp.feature_b = ptr(self.feature_linear.weight), ptr(self.feature_linear.bias)
-        mp.alpha_w, mp.alpha_b = ptr(self.alpha_linear.weight), ptr(self.alpha_linear.bias)
-        mp.rgb_w, mp.rgb_b = ptr(self.rgb_linear.weight), ptr(self.rgb_linear.bias)
+        mp = self._mlp_params(keep)
         buf = torch.empty((n,), dtype=torch.float32, device=params[0].device)
         _lib.check(lib.nerfail_mlp_pack(mp, _lib.dev(buf), _lib.stream()))
         self._packed, self._packed_key = buf, key
