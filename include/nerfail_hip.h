@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 10
+#define NERFAIL_ABI_VERSION 11
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -516,6 +516,33 @@ size_t nerfail_cnn_bwd_multi_scratch_bytes(int R, int B, int H, int W);
 int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
                                const float* d_logits /* [R,B,num_classes] */, int R, int B, int H, int W, float* scratch,
                                float* d_x /* [R,B,3,H,W] */, void* stream);
+
+/* ABI 11. Weight gradients: everything a training step of the classifier needs from one backward pass. Runs
+ * nerfail_cnn_bwd_data's chain (the same kernels, grids and arguments) keeping every stage's pooled gradient, then forms the
+ * gradient of all 18 parameters. Conv stages: dW[co][ci][ky][kx] = sum over b and conv pixels (y, x) of
+ * G[b,y,x,co] X[b,y+ky,x+kx,ci] and db[co] = sum G[b,y,x,co], with G the un-pooled gradient (the pooled gradient at the coded
+ * window position unless the cell's workspace value is <= 0; NaN passes) and X the stage input, on v_mfma_f32_32x32x2_f32
+ * (exact f32 products, f32 accumulate). The pixel range is split over workgroups into partial slabs that a second kernel adds
+ * in a fixed order: no float atomics, every output written by one lane, two calls give the same bits.
+ *   x:          the forward's input [B,3,H,W] (stage 1's dW reads it); workspace, masks: what nerfail_cnn_fwd wrote (masks
+ *               kept); d_logits [B,num_classes]. None of them is written.
+ *   d_x:        [B,3,H,W] or NULL. When given, bit for bit what nerfail_cnn_bwd_data writes for the same inputs.
+ *   d_params:   nerfail_cnn_grad_floats(num_classes) floats, nn.Module layout in state-dict order, each region starting on a
+ *               multiple of 4 floats (16 bytes): conv1.weight [32][3][3][3], conv1.bias [32], ..., conv7.weight [64][128][3][3],
+ *               conv7.bias [64], fc1.weight [512][1024] (columns c * 16 + y * 4 + x, PyTorch's flatten order), fc1.bias [512],
+ *               fc2.weight [num_classes][512], fc2.bias [num_classes]. Every parameter's floats are overwritten (nothing is
+ *               accumulated); the floats that round a region up to a multiple of 4 are never written.
+ *   scratch:    nerfail_cnn_bwd_weights_scratch_bytes(B, H, W, num_classes) bytes, any contents on entry. On return, as
+ *               floats: for s = 0..6 back to back the gradient with respect to stage s's POOLED output,
+ *               [B, hp_s, wp_s, Cout_s] NHWC (the layout and sizes of the workspace's stage outputs; stage 6's is fc1's input
+ *               gradient), then d hidden [B, 512] (gated: 0 where hidden <= 0), then the partial slabs (contents
+ *               unspecified). Every element of the seven gradients and of d hidden is written.
+ * The size helpers return 0 for unsupported arguments. No allocation, no synchronisation; callable any number of times. */
+size_t nerfail_cnn_grad_floats(int num_classes);
+size_t nerfail_cnn_bwd_weights_scratch_bytes(int B, int H, int W, int num_classes);
+int nerfail_cnn_bwd_weights(const float* packed, int num_classes, const float* x, const float* workspace,
+                            const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch,
+                            float* d_params, float* d_x /* or NULL */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,16 @@
 Same submodules and parameter shapes, so a reference checkpoint (model/weights/my_model_<n>_best.pth) loads with
 load_state_dict(strict=True): seven stages of 3x3 convolution + ReLU + 2x2 max-pool (3-32-64-128-256-256-128-64
 channels), fc1 1024 -> 512 + ReLU, fc2 512 -> num_classes. The forward and the gradient with respect to the input run on
-libnerfail_hip's cnn kernels (torch.ops.nerfail_mi.cnn_fwd). Weight gradients (training the classifier) are not
-implemented: the attack loops freeze it (AS:281-287), and forward raises if a parameter requires grad under grad mode.
+libnerfail_hip's cnn kernels (torch.ops.nerfail_mi.cnn_fwd).
+
+Training is opt-in: MyCNN(num_classes, trainable=True). A default-constructed module is the frozen victim of the attack loops
+(AS:281-287): its forward raises if a parameter requires grad under grad mode. With trainable=True such a forward keeps its
+pool masks and the backward fills every parameter's .grad (and x.grad when x requires grad) from ONE pass of
+torch.ops.nerfail_mi.cnn_bwd_weights: native HIP weight gradients without float atomics, bitwise reproducible; a parameter
+with requires_grad=False gets None. model_train.py's loop (cross-entropy, SGD with momentum) runs on it unchanged. The weight
+image is rebuilt when a parameter's version moves, so every optimizer.step() is followed by one repack (18 small launches) in
+the next forward. Under torch.no_grad(), with all parameters frozen, in input_gradients() and in DeepFool a trainable module
+behaves exactly like a default one.
 
 MyCNN.input_gradients(logits, d_logits) is the backward for several right-hand sides at once: the input gradients of R
 rows d_logits [R,B,num_classes] of ONE forward in one launch chain (torch.ops.nerfail_mi.cnn_bwd_data_multi), each slice
@@ -20,8 +28,9 @@ from . import ops
 
 
 class MyCNN(nn.Module):
-    def __init__(self, num_classes=24):
+    def __init__(self, num_classes=24, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         chans = (3, 32, 64, 128, 256, 256, 128, 64)
         for i in range(7):
             setattr(self, 'conv%d' % (i + 1), nn.Conv2d(chans[i], chans[i + 1], 3))
@@ -69,8 +78,10 @@ class MyCNN(nn.Module):
         if not x.is_contiguous():
             raise ValueError('MyCNN: the input must be a contiguous NCHW tensor')
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError('MyCNN: weight gradients are not implemented - freeze the classifier (requires_grad_(False)) '
-                               'or run under torch.no_grad()')
+            if self.trainable:
+                return ops.CnnTrainFn.apply(self, x, *self._params())
+            raise RuntimeError('MyCNN: weight gradients are not enabled on this module - construct it with trainable=True, freeze '
+                               'the classifier (requires_grad_(False)) or run under torch.no_grad()')
         keep = torch.is_grad_enabled() and x.requires_grad
         logits, _, _ = ops.cnn_fwd(self.packed(), x, self.num_classes, keep)
         return logits

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must be imported first: libnerfail_hip.so binds to 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFAIL_HIP_LIB') or os.path.join(_HERE, 'lib', 'libnerfail_hip.so')   # override: A/B builds (tools/ablate.py)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_DEPTH = 16
 DW_BF16X3, DW_ACCUMULATE = 1, 2          # flags of nerfail_mlp_bwd_weights
 RAY_FLOATS = 11
@@ -122,6 +122,9 @@ SIGNATURES = {
     'nerfail_cnn_bwd_data': (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     'nerfail_cnn_bwd_multi_scratch_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     'nerfail_cnn_bwd_data_multi': (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'nerfail_cnn_grad_floats': (ctypes.c_size_t, [c_i]),
+    'nerfail_cnn_bwd_weights_scratch_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    'nerfail_cnn_bwd_weights': (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
 }
 
 

@@ -1,6 +1,6 @@
 // The MyCNN victim classifier (model/MyModel.py:5-52): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool,
-// 3-32-64-128-256-256-128-64 channels, then fc1 1024->512 + ReLU + fc2 512->C. Forward and the gradient with respect to the
-// input (weights frozen) on gfx950.
+// 3-32-64-128-256-256-128-64 channels, then fc1 1024->512 + ReLU + fc2 512->C. Forward, the gradient with respect to the
+// input, and the gradients with respect to the 18 parameters (nerfail_cnn_bwd_weights) on gfx950.
 //
 // Conv stages: implicit GEMM on v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulate). Activations are NHWC between
 // stages; stage 1 reads the module's NCHW input directly (3 channels padded to 4, K = 9 taps x 4 = 36 padded to 40).
@@ -17,6 +17,23 @@
 // Multi-RHS backward (nerfail_cnn_bwd_data_multi): R gradients of ONE forward. The backward kernels run one grid slice per
 // (r, b): slice g = r * B + b indexes every gradient buffer (d logits, gp, out, d x), image b = g % B indexes what the
 // forward kept (act, gmask, hidden). R = 1 is the single backward; the order of every sum does not depend on R.
+//
+// Weight gradients (nerfail_cnn_bwd_weights): dW[co][ci][tap] = sum over conv pixels p of G[p][co] X[p + tap][ci], the third
+// implicit GEMM on the same MFMA: M = Cout, N = (tap, Cin), and the contraction runs over the conv pixels of the batch. G is
+// the un-pooled gated gradient stage_grad() forms, X the stage input. Both LDS tiles are [pixel][channel], as the other two
+// directions keep them, and NO transposed copy is made: a lane's A element is (m = lane % 32, k = lane / 32) = (channel,
+// pixel), so the 32 lanes of a half-wave read 32 CONSECUTIVE CHANNELS of one pixel with one ds_read_b32 (bank-conflict
+// free), half-wave h the pixel next to it; the same for B at the pixel shifted by the tap. A wave owns one 32 x 32 (Cout, Cin)
+// block with all nine taps (9 accumulators = 144 registers): ten LDS reads feed nine MFMAs. The pixel range is split over
+// workgroups in whole 4 x 16 tiles of the FULL (hin - 2) x (win - 2) conv grid (rows and columns the floor pool dropped are
+// zeros in G; a tile pixel past the grid gets B = 0 and positions outside the image are zeros in X: never a read outside
+// either, and exactly ATen's set of products, so a NaN in X shows in the same taps); every workgroup writes its partial
+// [Cout][tap][Cin] slab to scratch and reduce_slabs_kernel adds the slabs in a fixed order (blocks of 16). No float atomics:
+// every output is written by one lane, the slab count depends on the shapes only, two runs give the same bits.
+// Stage 1 (Cin = 3, NCHW input) is an MFMA tile as well: M = 32 = Cout, N = (ci, tap) = 27 padded to 32 with zero B values,
+// one wave per two rows of an 8 x 32 pixel tile, the four waves' accumulators added in LDS in wave order.
+// Bias gradients: the sum of the gated pooled gradient over the pooled cells (db_kernel), through the same slabs. FC head:
+// VALU kernels, one thread per output, the batch summed in order; dW1's columns come out in PyTorch's c * 16 + y * 4 + x.
 #include "common.h"
 
 namespace nerfail {
@@ -146,12 +163,12 @@ __device__ __forceinline__ int tap_ofs(int mode, int tap, int tw) {
 // Stage one CC-channel slice of the un-pooled, ReLU-masked output gradient at conv positions (gy0 + r, gx0 + c) into LDS
 // (row stride XS floats); positions outside [0, 2 hp) x [0, 2 wp) get 0 (rows and columns the floor pool dropped, halo).
 // gp is read at gradient slice g, act and gmask at image b.
-template <int KC, int CC, int TH, int TW, int XS>
+template <int KC, int CC, int TH, int TW, int XS, int NTHR = 256>
 __device__ __forceinline__ void stage_grad(float* xs, const float* __restrict__ gp, const float* __restrict__ act,
                                            const unsigned char* __restrict__ gmask, int g, int b, int hp, int wp, int gy0,
                                            int gx0, int c0) {
     const int n8 = npc8(wp);
-    for (int idx = threadIdx.x; idx < TH * TW * (CC / 4); idx += 256) {
+    for (int idx = threadIdx.x; idx < TH * TW * (CC / 4); idx += NTHR) {
         const int q4 = idx % (CC / 4), p = idx / (CC / 4);
         const int oy = gy0 + p / TW, ox = gx0 + p % TW;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -465,6 +482,319 @@ static size_t workspace_floats(const Dims& d, int B) {
     return n + (size_t)B * kHidden;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- weight gradients
+// Stages >= 2: a tile is 4 x 16 conv pixels (k-steps of two pixels side by side: lane half h takes pixel 2 j + h), stage 1:
+// 8 x 32. A slab is `tps` consecutive tiles of the (image, tile row, tile column) order; the last slab may be shorter.
+constexpr int kDwTH = 4, kDwTW = 16, kDw1TH = 8, kDw1TW = 32;
+constexpr int kDwWorkgroups = 1024;                             // slabs x channel blocks aimed at per stage
+constexpr size_t kDwPartFloats = (size_t)16 << 20;              // cap of the partial-slab region (64 MB)
+
+struct DwArgs {
+    const float* in;           // stage input: NHWC [B, hin, win, Cin], stage 1: the module's NCHW input
+    const float* gp;           // d pooled output of the stage (NHWC)
+    const float* act;          // pooled output (NHWC)
+    const unsigned char* gmask;
+    float* part;               // partial slabs
+    int hin, win, hp, wp;
+    int ntx, nty, ntiles, tps; // tiles per image row / column, tiles of the batch, tiles per slab
+};
+
+// KC = Cout (M), NC = Cin (N, times nine taps); WM x WN waves, wave (wm, wn) owns Cout block co0 + 32 wm, Cin block ci0 + 32 wn.
+// part: [slab][Cout][tap][Cin].
+template <int KC, int NC, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN) void conv_dw_kernel(DwArgs a) {
+    constexpr int NTHR = 64 * WM * WN, MCH = 32 * WM, NCH = 32 * WN, TH = kDwTH, TW = kDwTW, XH = TH + 2, XW = TW + 2;
+    constexpr int GS = MCH + 4, XS = NCH + 4;                   // LDS row strides (floats): 16-byte rows, half-waves 4 banks apart
+    static_assert(KC % MCH == 0 && NC % NCH == 0, "channel blocks");
+    __shared__ __attribute__((aligned(16))) float gs[TH * TW * GS];
+    __shared__ __attribute__((aligned(16))) float xt[XH * XW * XS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 31, h = lane >> 5, wm = wave % WM, wn = wave / WM;
+    const int co0 = (blockIdx.y % (KC / MCH)) * MCH, ci0 = (blockIdx.y / (KC / MCH)) * NCH;
+    const int slab = blockIdx.x;
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+
+    const int t0 = slab * a.tps, t1 = min(t0 + a.tps, a.ntiles);
+    for (int t = t0; t < t1; ++t) {
+        const int per = a.nty * a.ntx, b = t / per, r = t % per;
+        const int gy0 = (r / a.ntx) * TH, gx0 = (r % a.ntx) * TW;
+        __syncthreads();
+        stage_grad<KC, MCH, TH, TW, GS, NTHR>(gs, a.gp, a.act, a.gmask, b, b, a.hp, a.wp, gy0, gx0, co0);
+        for (int idx = tid; idx < XH * XW * (NCH / 4); idx += NTHR) {
+            const int q4 = idx % (NCH / 4), p = idx / (NCH / 4);
+            const int gy = gy0 + p / XW, gx = gx0 + p % XW;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (gy < a.hin && gx < a.win)
+                v = *reinterpret_cast<const float4*>(a.in + (((size_t)b * a.hin + gy) * a.win + gx) * NC + ci0 + 4 * q4);
+            *reinterpret_cast<float4*>(xt + p * XS + 4 * q4) = v;
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int py = 0; py < TH; ++py) {                       // (one row per trip: the unrolled tile keeps 120 operands live)
+            const float* ga = gs + (py * TW + h) * GS + wm * 32 + n;
+            const float* xa = xt + (py * XW + h) * XS + wn * 32 + n;
+            const bool rowok = gy0 + py < a.hin - 2;
+#pragma unroll
+            for (int j = 0; j < TW / 2; ++j) {
+                // a pixel past the conv grid contributes no product at all (G is 0 there, but 0 x NaN would not be)
+                const bool ok = rowok && gx0 + 2 * j + h < a.win - 2;
+                const float av = ga[2 * j * GS];
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) {
+                    const float bv = xa[((tap / 3) * XW + tap % 3 + 2 * j) * XS];
+                    acc[tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, ok ? bv : 0.f, acc[tap], 0, 0, 0);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int co = co0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            a.part[(((size_t)slab * KC + co) * 9 + tap) * NC + ci0 + wn * 32 + n] = acc[tap][i];
+        }
+}
+
+// Stage 1: M = 32 output channels, N = 27 (ci, tap) columns padded to 32 (B = 0 there), wave w takes rows 2w, 2w + 1 of the
+// 8 x 32 tile. part: [slab][32 co][32 n], n = ci * 9 + tap (conv1.weight's own order).
+__global__ __launch_bounds__(256) void conv1_dw_kernel(DwArgs a) {
+    constexpr int TH = kDw1TH, TW = kDw1TW, XH = TH + 2, XW = TW + 2, XP = XH * XW, GS = 36;
+    __shared__ __attribute__((aligned(16))) float gs[TH * TW * GS];
+    __shared__ float xt[3 * XP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, h = lane >> 5;
+    const bool live = n < 27;
+    const int bofs = live ? (n / 9) * XP + ((n % 9) / 3) * XW + n % 3 : 0;
+    const int slab = blockIdx.x;
+    const size_t plane = (size_t)a.hin * a.win;
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+
+    const int t0 = slab * a.tps, t1 = min(t0 + a.tps, a.ntiles);
+    for (int t = t0; t < t1; ++t) {
+        const int per = a.nty * a.ntx, b = t / per, r = t % per;
+        const int gy0 = (r / a.ntx) * TH, gx0 = (r % a.ntx) * TW;
+        __syncthreads();
+        stage_grad<32, 32, TH, TW, GS>(gs, a.gp, a.act, a.gmask, b, b, a.hp, a.wp, gy0, gx0, 0);
+        for (int idx = tid; idx < 3 * XP; idx += 256) {
+            const int c = idx / XP, p = idx % XP;
+            const int gy = gy0 + p / XW, gx = gx0 + p % XW;
+            xt[idx] = (gy < a.hin && gx < a.win) ? a.in[((size_t)b * 3 + c) * plane + (size_t)gy * a.win + gx] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < TW; ++j) {                          // 64 pixels of the wave's two rows, two per k-step
+            const int py = 2 * wave + (2 * j) / TW, px = (2 * j) % TW + h;
+            const float av = gs[(py * TW + px) * GS + n];
+            const bool ok = live && gy0 + py < a.hin - 2 && gx0 + px < a.win - 2;   // (past the conv grid: no product)
+            const float bv = ok ? xt[bofs + py * XW + px] : 0.f;
+            acc[j & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[j & 1], 0, 0, 0);
+        }
+    }
+    __syncthreads();                                            // gs becomes [4 waves][32 co][32 n]
+#pragma unroll
+    for (int i = 0; i < 16; ++i) gs[(wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * h) * 32 + n] = acc[0][i] + acc[1][i];
+    __syncthreads();
+    for (int idx = tid; idx < 1024; idx += 256)
+        a.part[(size_t)slab * 1024 + idx] = ((gs[idx] + gs[1024 + idx]) + gs[2048 + idx]) + gs[3072 + idx];
+}
+
+// db: the gated pooled gradient (act <= 0 -> 0, NaN passes) summed over `cps` pooled cells per workgroup. part: [slab][C].
+template <int C>
+__global__ __launch_bounds__(256) void db_kernel(const float* __restrict__ gp, const float* __restrict__ act,
+                                                 float* __restrict__ part, size_t cells, int cps) {
+    constexpr int Q = C / 4, L = 256 / Q;
+    __shared__ __attribute__((aligned(16))) float red[L * C];
+    const int q = threadIdx.x % Q, l = threadIdx.x / Q;
+    const size_t c0 = (size_t)blockIdx.x * cps, c1 = min(c0 + (size_t)cps, cells);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (size_t cell = c0 + l; cell < c1; cell += L) {
+        const float4 gv = *reinterpret_cast<const float4*>(gp + cell * C + 4 * q);
+        const float4 av = *reinterpret_cast<const float4*>(act + cell * C + 4 * q);
+        s.x += av.x <= 0.f ? 0.f : gv.x;
+        s.y += av.y <= 0.f ? 0.f : gv.y;
+        s.z += av.z <= 0.f ? 0.f : gv.z;
+        s.w += av.w <= 0.f ? 0.f : gv.w;
+    }
+    *reinterpret_cast<float4*>(red + l * C + 4 * q) = s;
+    __syncthreads();
+    if (threadIdx.x < C) {
+        float t = 0.f;
+        for (int k = 0; k < L; ++k) t += red[k * C + threadIdx.x];
+        part[(size_t)blockIdx.x * C + threadIdx.x] = t;
+    }
+}
+
+// dst = the S slabs added in a fixed order, sixteen at a time. One thread per slab element i < n.
+// mode 0: dst[i]; mode 1: slab [Cout][tap][NC] -> dst [Cout][NC][tap]; mode 2: slab [32][32] -> dst [32][27].
+__global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restrict__ part, int S, int n, int NC, int mode,
+                                                           float* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float total = 0.f;
+    for (int s0 = 0; s0 < S; s0 += 16) {
+        float g = 0.f;
+        const int s1 = min(s0 + 16, S);
+        for (int s = s0; s < s1; ++s) g += part[(size_t)s * n + i];
+        total += g;
+    }
+    if (mode == 0) {
+        dst[i] = total;
+    } else if (mode == 1) {
+        const int ci = i % NC, t = (i / NC) % 9, co = i / (9 * NC);
+        dst[((size_t)co * NC + ci) * 9 + t] = total;
+    } else if (i % 32 < 27) {
+        dst[(i / 32) * 27 + i % 32] = total;
+    }
+}
+
+// d hidden [B][512] = (fc2^T d logits) gated by hidden > 0 (NaN passes): fc_bwd_kernel's first half, kept.
+__global__ __launch_bounds__(512) void fc_dh_kernel(const float* __restrict__ dlogits, const float* __restrict__ hidden,
+                                                    const float* __restrict__ w2, int C, float* __restrict__ dh) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s = fmaf(dlogits[(size_t)b * C + c], w2[(size_t)c * kHidden + t], s);
+    dh[(size_t)b * kHidden + t] = hidden[(size_t)b * kHidden + t] <= 0.f ? 0.f : s;
+}
+
+// fc1.weight [512][1024] (column c * 16 + yx reads the NHWC stage-7 output at yx * 64 + c: pack_fc1_kernel's permutation
+// inverted), fc1.bias, fc2.weight [C][512], fc2.bias: one thread per output, the batch summed in order.
+__global__ __launch_bounds__(256) void fc_dw_kernel(const float* __restrict__ dlogits, const float* __restrict__ hidden,
+                                                    const float* __restrict__ dh, const float* __restrict__ x7, int B, int C,
+                                                    float* __restrict__ dW1, float* __restrict__ db1, float* __restrict__ dW2,
+                                                    float* __restrict__ db2) {
+    const int n1 = kHidden * kFlat, n2 = C * kHidden;
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    float s = 0.f;
+    if (i < n1) {
+        const int o = i / kFlat, col = i % kFlat, j = (col % 16) * 64 + col / 16;
+        for (int b = 0; b < B; ++b) s = fmaf(dh[(size_t)b * kHidden + o], x7[(size_t)b * kFlat + j], s);
+        dW1[i] = s;
+    } else if ((i -= n1) < kHidden) {
+        for (int b = 0; b < B; ++b) s += dh[(size_t)b * kHidden + i];
+        db1[i] = s;
+    } else if ((i -= kHidden) < n2) {
+        const int c = i / kHidden, u = i % kHidden;
+        for (int b = 0; b < B; ++b) s = fmaf(dlogits[(size_t)b * C + c], hidden[(size_t)b * kHidden + u], s);
+        dW2[i] = s;
+    } else if ((i -= n2) < C) {
+        for (int b = 0; b < B; ++b) s += dlogits[(size_t)b * C + i];
+        db2[i] = s;
+    }
+}
+
+// ---- host side of the weight gradients
+struct GradLayout {                                             // d_params (floats): nn.Module layout, state-dict order
+    size_t w[kStages + 2], b[kStages + 2], total;               // 7, 8: fc1, fc2
+};
+static GradLayout grad_layout(int C) {
+    GradLayout L;
+    size_t o = 0;
+    for (int s = 0; s < kStages; ++s) {
+        L.w[s] = o; o += up4((size_t)stage_cout(s) * stage_cin(s) * 9);
+        L.b[s] = o; o += up4(stage_cout(s));
+    }
+    L.w[7] = o; o += (size_t)kHidden * kFlat;
+    L.b[7] = o; o += kHidden;
+    L.w[8] = o; o += up4((size_t)C * kHidden);
+    L.b[8] = o; o += up4(C);
+    L.total = o;
+    return L;
+}
+
+struct DwPlan {
+    int ntx, nty, ntiles, tps, slabs, ny;                       // ny: channel blocks (grid y)
+    size_t out;                                                 // floats of one slab
+    int db_cps, db_slabs;
+};
+static DwPlan dw_plan(const Dims& d, int s, int B) {
+    DwPlan p;
+    const int th = s == 0 ? kDw1TH : kDwTH, tw = s == 0 ? kDw1TW : kDwTW;
+    p.nty = (d.hin[s] - 2 + th - 1) / th;
+    p.ntx = (d.win[s] - 2 + tw - 1) / tw;
+    p.ntiles = B * p.nty * p.ntx;
+    p.ny = s == 0 ? 1 : (stage_cout(s) / 64) * (stage_cin(s) / (stage_cin(s) >= 64 ? 64 : 32));
+    p.out = s == 0 ? 1024 : (size_t)stage_cout(s) * 9 * stage_cin(s);
+    size_t want = (size_t)(kDwWorkgroups + p.ny - 1) / p.ny;
+    if (want > kDwPartFloats / p.out) want = kDwPartFloats / p.out;
+    if (want > (size_t)p.ntiles) want = (size_t)p.ntiles;
+    if (want < 1) want = 1;
+    p.tps = (int)((p.ntiles + want - 1) / want);
+    p.slabs = (p.ntiles + p.tps - 1) / p.tps;
+    const size_t cells = (size_t)B * d.hin[s + 1] * d.win[s + 1];
+    p.db_cps = (int)((cells + 255) / 256);
+    p.db_slabs = (int)((cells + p.db_cps - 1) / p.db_cps);
+    return p;
+}
+
+struct DwScratch {                                              // scratch of nerfail_cnn_bwd_weights (floats)
+    size_t gpool[kStages], dh, part, total;
+};
+static DwScratch dw_scratch(const Dims& d, int B) {
+    DwScratch L;
+    size_t o = 0, m = 0;
+    for (int s = 0; s < kStages; ++s) {
+        L.gpool[s] = o; o += up4(act_floats(d, s, B));
+        const DwPlan p = dw_plan(d, s, B);
+        const size_t a = (size_t)p.slabs * p.out, c = (size_t)p.db_slabs * stage_cout(s);
+        m = a > m ? a : m;
+        m = c > m ? c : m;
+    }
+    L.dh = o; o += up4((size_t)B * kHidden);
+    L.part = o; o += up4(m);
+    L.total = o;
+    return L;
+}
+
+template <int KC, int NC, int WM, int WN>
+static int launch_dw(const DwArgs& a, const DwPlan& p, hipStream_t st, const char* name) {
+    conv_dw_kernel<KC, NC, WM, WN><<<dim3((unsigned)p.slabs, (unsigned)p.ny), dim3(64 * WM * WN), 0, st>>>(a);
+    NF_LAUNCHED(name);
+    return 0;
+}
+
+static int conv_dw_stage(int s, const DwArgs& a, const DwPlan& p, hipStream_t st) {
+    switch (s) {
+        case 0:
+            conv1_dw_kernel<<<dim3((unsigned)p.slabs), dim3(256), 0, st>>>(a);
+            NF_LAUNCHED("cnn_conv_dw_s1");
+            return 0;
+        case 1: return launch_dw<64, 32, 2, 1>(a, p, st, "cnn_conv_dw_s2");
+        case 2: return launch_dw<128, 64, 2, 2>(a, p, st, "cnn_conv_dw_s3");
+        case 3: return launch_dw<256, 128, 2, 2>(a, p, st, "cnn_conv_dw_s4");
+        case 4: return launch_dw<256, 256, 2, 2>(a, p, st, "cnn_conv_dw_s5");
+        case 5: return launch_dw<128, 256, 2, 2>(a, p, st, "cnn_conv_dw_s6");
+        default: return launch_dw<64, 128, 2, 2>(a, p, st, "cnn_conv_dw_s7");
+    }
+}
+
+static int db_stage(int s, const float* gp, const float* act, float* part, size_t cells, const DwPlan& p, hipStream_t st) {
+    const dim3 g((unsigned)p.db_slabs), t(256);
+    switch (stage_cout(s)) {
+        case 32: db_kernel<32><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
+        case 64: db_kernel<64><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
+        case 128: db_kernel<128><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
+        default: db_kernel<256><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
+    }
+    NF_LAUNCHED("cnn_db");
+    return 0;
+}
+
+static int reduce_slabs(const float* part, int S, size_t n, int NC, int mode, float* dst, hipStream_t st) {
+    reduce_slabs_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(part, S, (int)n, NC, mode, dst);
+    NF_LAUNCHED("cnn_reduce_slabs");
+    return 0;
+}
+
 }  // namespace cnn
 }  // namespace nerfail
 
@@ -642,4 +972,111 @@ extern "C" int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, 
     NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
                    d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
     return bwd_data_launch(packed, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- weight gradients
+extern "C" size_t nerfail_cnn_grad_floats(int num_classes) {
+    if (num_classes < 1 || num_classes > 4096) return 0;
+    return grad_layout(num_classes).total;
+}
+
+extern "C" size_t nerfail_cnn_bwd_weights_scratch_bytes(int B, int H, int W, int num_classes) {
+    Dims d;
+    if (B < 1 || B > 65535 || num_classes < 1 || num_classes > 4096 || !dims_of(H, W, d)) return 0;
+    return dw_scratch(d, B).total * sizeof(float);
+}
+
+// The backward-data chain of nerfail_cnn_bwd_data (the same kernels, grids and arguments: the same bits) with every stage's
+// pooled gradient kept in its own region, then the FC head's and every stage's weight and bias gradient.
+extern "C" int nerfail_cnn_bwd_weights(const float* packed, int num_classes, const float* x, const float* workspace,
+                                       const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch,
+                                       float* d_params, float* d_x, void* stream) {
+    Dims d;
+    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
+    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
+    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
+    NF_REQUIRE(packed != nullptr && x != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr &&
+                   scratch != nullptr && d_params != nullptr,
+               "packed, x, workspace, masks, d_logits, scratch or d_params is NULL");
+    const PackLayout L = pack_layout(num_classes);
+    const GradLayout G = grad_layout(num_classes);
+    const DwScratch S = dw_scratch(d, B);
+    hipStream_t st = as_stream(stream);
+    const float* acts[kStages];
+    const unsigned char* mks[kStages];
+    const float* p = workspace;
+    const unsigned char* q = masks;
+    for (int s = 0; s < kStages; ++s) {
+        acts[s] = p;
+        mks[s] = q;
+        p += act_floats(d, s, B);
+        q += mask_bytes_of(d, s, B);
+    }
+    const float* hidden = p;
+    float* gpool[kStages];
+    for (int s = 0; s < kStages; ++s) gpool[s] = scratch + S.gpool[s];
+    float* dh = scratch + S.dh;
+    float* part = scratch + S.part;
+
+    // ---- backward data
+    fc_bwd_kernel<<<dim3(B), dim3(kFlat), 0, st>>>(d_logits, hidden, packed + L.fc1P, packed + L.w2, num_classes, B, gpool[6]);
+    NF_LAUNCHED("cnn_fc_bwd");
+    for (int s = kStages - 1; s >= 1; --s) {
+        ConvArgs a = {};
+        a.w = packed + L.bwd[s];
+        a.out = gpool[s - 1];
+        a.gp = gpool[s];
+        a.act = acts[s];
+        a.gmask = mks[s];
+        a.hin = d.hin[s];
+        a.win = d.win[s];
+        a.hp = d.hin[s + 1];
+        a.wp = d.win[s + 1];
+        a.B = B;
+        int rc = conv_bwd_stage(s, a, B, st);
+        if (rc) return rc;
+    }
+    if (d_x) {
+        const unsigned tiles = (unsigned)(((W + 15) / 16) * ((H + 15) / 16));
+        conv1_bwd_kernel<<<dim3(tiles, 1, B), dim3(256), 0, st>>>(packed + L.w1raw, gpool[0], acts[0], mks[0], d_x, H, W, d.hin[1],
+                                                                 d.win[1], B);
+        NF_LAUNCHED("cnn_conv1_bwd");
+    }
+
+    // ---- FC head
+    fc_dh_kernel<<<dim3(B), dim3(kHidden), 0, st>>>(d_logits, hidden, packed + L.w2, num_classes, dh);
+    NF_LAUNCHED("cnn_fc_dh");
+    const size_t nfc = (size_t)kHidden * kFlat + kHidden + (size_t)num_classes * kHidden + num_classes;
+    fc_dw_kernel<<<dim3((unsigned)((nfc + 255) / 256)), dim3(256), 0, st>>>(d_logits, hidden, dh, acts[6], B, num_classes,
+                                                                           d_params + G.w[7], d_params + G.b[7],
+                                                                           d_params + G.w[8], d_params + G.b[8]);
+    NF_LAUNCHED("cnn_fc_dw");
+
+    // ---- conv stages: partial slabs, then their fixed-order sum (the slab region is reused, stream order keeps it safe)
+    for (int s = 0; s < kStages; ++s) {
+        const DwPlan pl = dw_plan(d, s, B);
+        DwArgs a = {};
+        a.in = s == 0 ? x : acts[s - 1];
+        a.gp = gpool[s];
+        a.act = acts[s];
+        a.gmask = mks[s];
+        a.part = part;
+        a.hin = d.hin[s];
+        a.win = d.win[s];
+        a.hp = d.hin[s + 1];
+        a.wp = d.win[s + 1];
+        a.ntx = pl.ntx;
+        a.nty = pl.nty;
+        a.ntiles = pl.ntiles;
+        a.tps = pl.tps;
+        int rc = conv_dw_stage(s, a, pl, st);
+        if (rc) return rc;
+        rc = reduce_slabs(part, pl.slabs, pl.out, stage_cin(s), s == 0 ? 2 : 1, d_params + G.w[s], st);
+        if (rc) return rc;
+        rc = db_stage(s, gpool[s], acts[s], part, (size_t)B * a.hp * a.wp, pl, st);
+        if (rc) return rc;
+        rc = reduce_slabs(part, pl.db_slabs, stage_cout(s), 0, 0, d_params + G.b[s], st);
+        if (rc) return rc;
+    }
+    return 0;
 }

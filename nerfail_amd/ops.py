@@ -436,4 +436,86 @@ def cnn_fwd_saved(logits):
         return None
     return packed, ws, masks, node.hw
 
-CNN_OPS = ('cnn_fwd', 'cnn_bwd_data', 'cnn_bwd_data_multi')
+
+def cnn_grad_layout(num_classes):
+    """[(offset, shape)] of the 18 parameter gradients in the flat d_params buffer of nerfail_cnn_bwd_weights: nn.Module
+    layout in state-dict order, every region starting on a multiple of 4 floats (include/nerfail_hip.h, ABI 11)."""
+    chans = (3, 32, 64, 128, 256, 256, 128, 64)
+    shapes = []
+    for i in range(7):
+        shapes += [(chans[i + 1], chans[i], 3, 3), (chans[i + 1],)]
+    shapes += [(512, 1024), (512,), (num_classes, 512), (num_classes,)]
+    out, o = [], 0
+    for sh in shapes:
+        n = 1
+        for d in sh:
+            n *= d
+        out.append((o, sh))
+        o += (n + 3) // 4 * 4
+    return out, o
+
+
+@custom_op(NS + '::cnn_bwd_weights', mutates_args=(), device_types='cuda')
+def cnn_bwd_weights(packed: Tensor, x: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, need_dx: bool) -> tuple[Tensor, Tensor]:
+    """(d_params, d_x) of cnn_fwd from d loss / d logits [B,num_classes], the forward's input, workspace and masks: d_params
+    is the flat gradient of all 18 parameters (cnn_grad_layout), d_x [B,3,H,W] is bitwise cnn_bwd_data's (empty unless
+    need_dx). No float atomics: two calls give the same bits."""
+    lib = _lib.load()
+    if d_logits.dtype != torch.float32 or x.dtype != torch.float32:
+        raise TypeError('cnn_bwd_weights: x and d_logits must be float32 (got %s, %s)' % (x.dtype, d_logits.dtype))
+    if d_logits.dim() != 2 or x.dim() != 4 or x.shape[0] != d_logits.shape[0] or x.shape[1] != 3:
+        raise ValueError('cnn_bwd_weights: x must be [B,3,H,W] and d_logits [B,num_classes] (got %s, %s)'
+                         % (tuple(x.shape), tuple(d_logits.shape)))
+    B, C = d_logits.shape
+    H, W = x.shape[2], x.shape[3]
+    if masks.numel() == 0:
+        raise RuntimeError('cnn_bwd_weights: the forward kept no masks (cnn_fwd with keep_masks=False)')
+    nb = lib.nerfail_cnn_bwd_weights_scratch_bytes(B, H, W, C)
+    if nb == 0 or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C) or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W):
+        raise ValueError('cnn_bwd_weights: unsupported d_logits %s for a forward of x %s (needs the workspace and masks of a '
+                         'forward of these B images)' % (tuple(d_logits.shape), tuple(x.shape)))
+    dev = d_logits.device
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=dev)
+    d_params = torch.zeros((lib.nerfail_cnn_grad_floats(C),), dtype=torch.float32, device=dev)   # zeros: the alignment padding
+    dx = torch.empty((B, 3, H, W) if need_dx else (0,), dtype=torch.float32, device=dev)
+    _chk(lib.nerfail_cnn_bwd_weights(_lib.dev(packed), C, _lib.dev(x, 'x'), _lib.dev(workspace), _lib.dev(masks),
+                                     _lib.dev(d_logits, 'd_logits'), B, H, W, _lib.dev(scratch), _lib.dev(d_params),
+                                     _lib.dev(dx) if need_dx else None, _s()))
+    return d_params, dx
+
+
+@cnn_bwd_weights.register_fake
+def _(packed, x, workspace, masks, d_logits, need_dx):
+    _, total = cnn_grad_layout(d_logits.shape[1])
+    return d_logits.new_empty((total,)), d_logits.new_empty(tuple(x.shape) if need_dx else (0,))
+
+
+class CnnTrainFn(torch.autograd.Function):
+    """logits = MyCNN(x) with gradients for the parameters: cnn_fwd keeping its masks, cnn_bwd_weights backwards. `module`
+    supplies the weight image; the parameters are passed so that autograd routes their gradients."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        packed = module.packed()
+        logits, ws, masks = cnn_fwd(packed, x, module.num_classes, True)
+        ctx.save_for_backward(packed, x, ws, masks)
+        ctx.num_classes = module.num_classes
+        ctx.mark_non_differentiable()
+        return logits
+
+    @staticmethod
+    def backward(ctx, g_logits):
+        packed, x, ws, masks = ctx.saved_tensors
+        need_dx = ctx.needs_input_grad[1]
+        d_params, dx = cnn_bwd_weights(packed, x, ws, masks, g_logits.contiguous().float(), need_dx)
+        layout, _ = cnn_grad_layout(ctx.num_classes)
+        grads = []
+        for i, (o, sh) in enumerate(layout):
+            n = 1
+            for d in sh:
+                n *= d
+            grads.append(d_params[o:o + n].view(sh) if ctx.needs_input_grad[2 + i] else None)
+        return (None, dx if need_dx else None) + tuple(grads)
+
+
+CNN_OPS = ('cnn_fwd', 'cnn_bwd_data', 'cnn_bwd_data_multi', 'cnn_bwd_weights')

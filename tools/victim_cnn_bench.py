@@ -6,7 +6,11 @@ each victim (the legs of bench_sections.attack_bench). Prints one JSON object. U
 alternated inside each round: the native backward of 8 one-hot rows of one 800x800 forward as eight cnn_bwd_data calls and as
 one cnn_bwd_data_multi call, the single backward at B = 8 beside them (the same MFMA work), and the DeepFool inner loop with
 the MIOpen victim, the native victim forced to one backward per class (batched_classifier_backward = False) and the native
-victim on the automatic setting."""
+victim on the automatic setting.
+
+--train: one model_train.py-shaped step (forward, cross-entropy, backward, torch.optim.SGD(lr=1e-3, momentum=0.9) step) at
+B = 16 and B = 8, 800x800: MyCNN(8, trainable=True) (nerfail_cnn_bwd_weights) against the stock module on MIOpen, arms
+alternated, three rounds. The number that matters is the ratio to the stock module in the same session."""
 import json
 import os
 import sys
@@ -157,13 +161,43 @@ def multi_legs(dev, victims, rounds=3):
     return out
 
 
+def train_legs(dev, stock, rounds=3):
+    from nerfail_amd.MyModel import MyCNN
+    import torch.nn.functional as F
+    native = MyCNN(8, trainable=True)
+    native.load_state_dict(dict(zip(native.state_dict(), stock.state_dict().values())), strict=True)
+    arms = {'miopen': stock.requires_grad_(True).train(), 'native': native.to(dev).train()}
+    opts = {k: torch.optim.SGD(v.parameters(), lr=1e-3, momentum=0.9) for k, v in arms.items()}
+    out = {}
+    for B in (16, 8):
+        x = torch.rand((B, 3, BS.H, BS.W), device=dev) * 255
+        y = torch.randint(0, 8, (B,), device=dev)
+
+        def step(k):
+            opts[k].zero_grad()
+            F.cross_entropy(arms[k](x), y).backward()
+            opts[k].step()
+        for k in arms:
+            out['train_step_b%d_%s_ms' % (B, k)] = []
+        for _ in range(rounds):
+            for k in arms:
+                out['train_step_b%d_%s_ms' % (B, k)].append(timed(lambda: step(k), reps=3, blocks=3) * 1e3)
+        a, b = out['train_step_b%d_native_ms' % B], out['train_step_b%d_miopen_ms' % B]
+        out['train_step_b%d_native_over_miopen' % B] = float(np.median(a) / np.median(b))
+    out['note'] = 'per arm: one value per round, arms alternated inside a round; each value the median of 3 blocks of 3 steps'
+    return out
+
+
 def main():
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     stock = BS.victim_cnn(8).to(dev).requires_grad_(False).eval()
     victims = {'miopen': stock, 'native': native_victim(stock)}
     res = {'device': torch.cuda.get_device_name(0), 'batch': 8, 'size': [BS.H, BS.W]}
-    if '--multi' in sys.argv:
+    if '--train' in sys.argv:
+        res['batch'] = [16, 8]
+        res.update(train_legs(dev, stock))
+    elif '--multi' in sys.argv:
         res.update(multi_legs(dev, victims))
     else:
         res.update(classifier_legs(dev, victims))
