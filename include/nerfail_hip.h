@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 11
+#define NERFAIL_ABI_VERSION 12
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -152,6 +152,27 @@ int nerfail_mlp_fwd_embedded_x3(const float* packed, const void* x3, int D, int 
                                 float* raw, void* stream);
 int nerfail_mlp_fwd_rays_x3(const float* packed, const void* x3, int D, int W, int skip, const float* rays,
                             const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream);
+
+/* ABI 12. The same kernel without feature_linear: no activation lies between feature_linear and views_linears[0], so
+ * Wc = Wv[:, :W] Wf and bc = Wv[:, :W] bf + bv are composed ONCE per weight set (nerfail_mlp_pack_x3f, on the device, from
+ * the f32 image: each sum over m = 0..W-1 in this order in double, bv added last, rounded once to f32, then Wc split
+ * into bf16 planes like every weight) and the 256 -> 256 layer, 11 % of the kernel's MFMAs, leaves the hot path. The folded
+ * image `x3f` is separate from `x3`: the stream of layers 0..D-1 as there, ONE views layer (Wc, then the direction columns),
+ * the constant area of the f32 image with bias piece D = bc (zero behind it), and last the composed f32 block of
+ * nerfail_mlp_x3f_composed_floats() floats - Wc [W/2][W] row-major, then bc [W/2] zero-padded to 256 floats. A caller
+ * checks that block for inf / NaN (weights so large that the product leaves f32) and, if it finds any, keeps using the
+ * unfolded entry points above. Same shapes, same selection rules and same fall-backs as the x3 entry points (forced reg /
+ * lds: the exact kernels; shapes not covered: nerfail_mlp_packed_x3f_bytes returns 0 and the f32 path runs); f32-accurate,
+ * not bitwise the unfolded kernel's results. */
+size_t nerfail_mlp_packed_x3f_bytes(int D, int W, int skip);
+size_t nerfail_mlp_x3f_composed_floats(int D, int W, int skip);
+int nerfail_mlp_pack_x3f(const float* packed, int D, int W, int skip, void* x3f, void* stream);
+int nerfail_mlp_fwd_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* pts, const float* viewdirs,
+                        int64_t M, int samples_per_ray, float* raw, void* stream);
+int nerfail_mlp_fwd_embedded_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* x, int64_t M,
+                                 float* raw, void* stream);
+int nerfail_mlp_fwd_rays_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
+                             const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream);
 
 /* ---- split-precision ("f16x3") forward: same contract as nerfail_mlp_fwd, fp32-equivalent results --------
  * Every product a*w is evaluated as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on the fp16 matrix cores with fp32

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must be imported first: libnerfail_hip.so binds to 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFAIL_HIP_LIB') or os.path.join(_HERE, 'lib', 'libnerfail_hip.so')   # override: A/B builds (tools/ablate.py)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_DEPTH = 16
 DW_BF16X3, DW_ACCUMULATE = 1, 2          # flags of nerfail_mlp_bwd_weights
 RAY_FLOATS = 11
@@ -59,6 +59,12 @@ SIGNATURES = {
     'nerfail_mlp_fwd_x3': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
     'nerfail_mlp_fwd_embedded_x3': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p]),
     'nerfail_mlp_fwd_rays_x3': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p, c_p]),
+    'nerfail_mlp_packed_x3f_bytes': (ctypes.c_size_t, [c_i, c_i, c_i]),
+    'nerfail_mlp_x3f_composed_floats': (ctypes.c_size_t, [c_i, c_i, c_i]),
+    'nerfail_mlp_pack_x3f': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
+    'nerfail_mlp_fwd_x3f': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
+    'nerfail_mlp_fwd_embedded_x3f': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p]),
+    'nerfail_mlp_fwd_rays_x3f': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p, c_p]),
     'nerfail_mlp_f16_image_bytes': (ctypes.c_size_t, [c_i, c_i, c_i]),
     'nerfail_mlp_pack_f16': (c_i, [ctypes.POINTER(MlpParams), c_p, c_p]),
     'nerfail_mlp_fwd_f16': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),

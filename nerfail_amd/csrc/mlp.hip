@@ -30,7 +30,10 @@ namespace nerfail {
 bool mlp_x3_covers(const MlpLayout& L, int W);                                      // mlp_x3.hip
 size_t mlp_x3_bytes(const MlpLayout& L, int W);
 int pack_mlp_x3(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s);
-int launch_mlp_x3(const MlpArgs& a, const void* img, int W, hipStream_t s);
+int launch_mlp_x3(const MlpArgs& a, const void* img, int W, bool fold, hipStream_t s);
+size_t mlp_x3f_bytes(const MlpLayout& L, int W);                                    // the folded image (no feature layer)
+size_t mlp_x3f_composed_floats(const MlpLayout& L, int W);
+int pack_mlp_x3f(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s);
 
 // ------------------------------------------------------------------------------------- device side
 template <int NT, bool TRAIN>
@@ -186,12 +189,13 @@ static int launch_mlp(const MlpArgs& a, int W, hipStream_t s) {
 }
 
 // x3 entry points: the bf16x3 kernel for inference when the selection allows it and it covers the shape, else exactly
-// launch_mlp. Forced ('x') on a shape it does not cover, or without an image, is an error.
-static int launch_mlp_x3_or(const MlpArgs& a, const void* img, int W, hipStream_t s) {
+// launch_mlp. Forced ('x') on a shape it does not cover, or without an image, is an error. fold: the x3f entry points - `img`
+// is the folded image and the folded kernel runs; every rule is the same.
+static int launch_mlp_x3_or(const char* fn, const MlpArgs& a, const void* img, int W, bool fold, hipStream_t s) {
     if (a.acts == nullptr && (g_fwd_select == 0 || g_fwd_select == 3)) {
         if (g_fwd_select == 3 || (img != nullptr && mlp_x3_covers(a.lay, W))) {
-            if (img == nullptr) { set_error("nerfail_mlp_fwd_x3: NERFAIL_FWD_KERNEL=x without a bf16x3 image"); return NERFAIL_EINVAL; }
-            return launch_mlp_x3(a, img, W, s);
+            if (img == nullptr) { set_error("%s: NERFAIL_FWD_KERNEL=x without a bf16x3 image", fn); return NERFAIL_EINVAL; }
+            return launch_mlp_x3(a, img, W, fold, s);
         }
     }
     return launch_mlp(a, W, s);
@@ -210,10 +214,11 @@ extern "C" int nerfail_mlp_fwd_select(int which) {
 // The forward entry points differ in the form of their input only: sample points + one view direction per ray (pts), an
 // already embedded batch (xemb), or packed rays + depths (rays: the points are formed inside the kernel, pts = o + d * z,
 // RN:381 / :399, instead of being read from a [M,3] tensor that the sampling kernels wrote). `in0` / `in1` are the two input
-// pointers of that form (xemb has one), `acts` asks for the training forward, `use_x3` for the bf16x3 selection with image `x3`.
+// pointers of that form (xemb has one), `acts` asks for the training forward, `sel` for the bf16x3 selection with image `x3` (kX3Fold: the folded image).
 enum MlpInput { kInPts, kInEmbedded, kInRays };
+enum MlpSel { kF32, kX3, kX3Fold };
 #define MLP_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return NERFAIL_EINVAL; } } while (0)
-static int mlp_fwd_entry(const char* fn, MlpInput form, const float* packed, bool use_x3, const void* x3, int D, int W, int skip,
+static int mlp_fwd_entry(const char* fn, MlpInput form, const float* packed, MlpSel sel, const void* x3, int D, int W, int skip,
                          const float* in0, const float* in1, int64_t M, int spr, float* raw, float* acts, bool need_acts, void* stream) {
     MLP_REQUIRE(M >= 0, form == kInRays ? "n_rays is negative" : "M is negative");
     MLP_REQUIRE(form == kInEmbedded || spr >= 1, "samples_per_ray must be positive");
@@ -227,18 +232,18 @@ static int mlp_fwd_entry(const char* fn, MlpInput form, const float* packed, boo
     a.pts = form == kInPts ? in0 : nullptr; a.viewdirs = form == kInPts ? in1 : nullptr;
     a.xemb = form == kInEmbedded ? in0 : nullptr;
     a.rays = form == kInRays ? in0 : nullptr; a.z = form == kInRays ? in1 : nullptr;
-    return use_x3 ? launch_mlp_x3_or(a, x3, W, as_stream(stream)) : launch_mlp(a, W, as_stream(stream));
+    return sel != kF32 ? launch_mlp_x3_or(fn, a, x3, W, sel == kX3Fold, as_stream(stream)) : launch_mlp(a, W, as_stream(stream));
 }
 #undef MLP_REQUIRE
 
 extern "C" int nerfail_mlp_fwd(const float* packed, int D, int W, int skip, const float* pts, const float* viewdirs,
                                int64_t M, int samples_per_ray, float* raw, void* stream) {
-    return mlp_fwd_entry(__func__, kInPts, packed, false, nullptr, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
+    return mlp_fwd_entry(__func__, kInPts, packed, kF32, nullptr, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_embedded(const float* packed, int D, int W, int skip, const float* x, int64_t M, float* raw,
                                         void* stream) {
-    return mlp_fwd_entry(__func__, kInEmbedded, packed, false, nullptr, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
+    return mlp_fwd_entry(__func__, kInEmbedded, packed, kF32, nullptr, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
 }
 
 extern "C" size_t nerfail_mlp_train_acts_floats(int D, int W, int64_t M) {
@@ -249,12 +254,12 @@ extern "C" size_t nerfail_mlp_train_acts_floats(int D, int W, int64_t M) {
 
 extern "C" int nerfail_mlp_fwd_train(const float* packed, int D, int W, int skip, const float* pts, const float* viewdirs,
                                      int64_t M, int samples_per_ray, float* raw, float* acts, void* stream) {
-    return mlp_fwd_entry(__func__, kInPts, packed, false, nullptr, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, acts, true, stream);
+    return mlp_fwd_entry(__func__, kInPts, packed, kF32, nullptr, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, acts, true, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_rays(const float* packed, int D, int W, int skip, const float* rays, const float* z_vals,
                                     int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
-    return mlp_fwd_entry(__func__, kInRays, packed, false, nullptr, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
+    return mlp_fwd_entry(__func__, kInRays, packed, kF32, nullptr, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
 }
 
 // ---- bf16x3 inference (mlp_x3.hip): the weight stream split once into three bf16 planes; each entry point takes both images
@@ -272,15 +277,48 @@ extern "C" int nerfail_mlp_pack_x3(const float* packed, int D, int W, int skip, 
 
 extern "C" int nerfail_mlp_fwd_x3(const float* packed, const void* x3, int D, int W, int skip, const float* pts,
                                   const float* viewdirs, int64_t M, int samples_per_ray, float* raw, void* stream) {
-    return mlp_fwd_entry(__func__, kInPts, packed, true, x3, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
+    return mlp_fwd_entry(__func__, kInPts, packed, kX3, x3, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_embedded_x3(const float* packed, const void* x3, int D, int W, int skip, const float* x, int64_t M,
                                            float* raw, void* stream) {
-    return mlp_fwd_entry(__func__, kInEmbedded, packed, true, x3, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
+    return mlp_fwd_entry(__func__, kInEmbedded, packed, kX3, x3, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
 }
 
 extern "C" int nerfail_mlp_fwd_rays_x3(const float* packed, const void* x3, int D, int W, int skip, const float* rays,
                                        const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
-    return mlp_fwd_entry(__func__, kInRays, packed, true, x3, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
+    return mlp_fwd_entry(__func__, kInRays, packed, kX3, x3, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
+}
+
+// ---- bf16x3 inference without feature_linear: its weights composed into the views layer at pack time (mlp_x3.hip)
+extern "C" size_t nerfail_mlp_packed_x3f_bytes(int D, int W, int skip) {
+    MlpLayout L;
+    return make_layout(D, W, skip, L) ? mlp_x3f_bytes(L, W) : 0;
+}
+
+extern "C" size_t nerfail_mlp_x3f_composed_floats(int D, int W, int skip) {
+    MlpLayout L;
+    return make_layout(D, W, skip, L) ? mlp_x3f_composed_floats(L, W) : 0;
+}
+
+extern "C" int nerfail_mlp_pack_x3f(const float* packed, int D, int W, int skip, void* out, void* stream) {
+    MlpLayout L;
+    NF_REQUIRE(make_layout(D, W, skip, L), "unsupported (D, W)");
+    NF_REQUIRE(packed != nullptr && out != nullptr, "NULL pointer");
+    return pack_mlp_x3f(packed, L, W, out, as_stream(stream));
+}
+
+extern "C" int nerfail_mlp_fwd_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* pts,
+                                   const float* viewdirs, int64_t M, int samples_per_ray, float* raw, void* stream) {
+    return mlp_fwd_entry(__func__, kInPts, packed, kX3Fold, x3f, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream);
+}
+
+extern "C" int nerfail_mlp_fwd_embedded_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* x, int64_t M,
+                                            float* raw, void* stream) {
+    return mlp_fwd_entry(__func__, kInEmbedded, packed, kX3Fold, x3f, D, W, skip, x, nullptr, M, 1, raw, nullptr, false, stream);
+}
+
+extern "C" int nerfail_mlp_fwd_rays_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
+                                        const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
+    return mlp_fwd_entry(__func__, kInRays, packed, kX3Fold, x3f, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
 }

@@ -20,11 +20,23 @@ __host__ __device__ inline int enc_channel(int s, int h, int bands) {
     return -1;
 }
 // Channel of a 32-channel accumulator tile held in register r of lane half h (32x32 C/D layout).
-__host__ __device__ inline int acc_channel(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+__host__ __device__ constexpr int acc_channel(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // Output channel of k-step s of a hidden part in lane half h: the accumulator tiles of the producing layer, 16 steps per
 // tile. The k map of the TRANSPOSED weight images (W^T: k = out channel) and the hidden part of the forward map below.
-__host__ __device__ inline int hidden_channel(int s, int h) { return 32 * (s / 16) + acc_channel(s % 16, h); }
+__host__ __device__ constexpr int hidden_channel(int s, int h) { return 32 * (s / 16) + acc_channel(s % 16, h); }
+// Its inverse: hidden column c is k-step hidden_step(c) of lane half hidden_half(c). A bias piece ([OT][2][16], load_bias)
+// holds channel c at bias_index(c).
+__host__ __device__ constexpr int hidden_half(int c) { return (c >> 2) & 1; }
+__host__ __device__ constexpr int hidden_step(int c) { return 16 * (c >> 5) + (c & 3) + 4 * ((c & 31) >> 3); }
+__host__ __device__ constexpr int bias_index(int c) { return 32 * (c >> 5) + 16 * hidden_half(c) + (hidden_step(c) & 15); }
+constexpr bool hidden_inverse_holds() {
+    for (int c = 0; c < 256; ++c)
+        if (hidden_channel(hidden_step(c), hidden_half(c)) != c || hidden_step(c) >= 128 || bias_index(c) >= 256 ||
+            32 * (bias_index(c) >> 5) + acc_channel(bias_index(c) & 15, (bias_index(c) >> 4) & 1) != c) return false;
+    return true;
+}
+static_assert(hidden_inverse_holds(), "hidden_step / hidden_half / bias_index invert hidden_channel / the bias order");
 // THE forward column map, the contract between every weight packer and every MLP kernel: the nn.Linear column that k-step s
 // of a layer multiplies in lane half h, -1 = zero padding. A layer's k-steps are its encoding part (32 steps, present when
 // emb0 >= 0), its hidden part (16*NT steps, h0 >= 0) and its view-direction part (16 steps, dir0 >= 0), in this order;

@@ -76,6 +76,19 @@ static inline bool make_x3_layout(const MlpLayout& L, int W, X3Layout& X) {
     X.pieces = off;
     return off % X3Cfg::GP == 0;
 }
+// The folded image (nerfail_mlp_pack_x3f): feature_linear and the hidden part of views_linears[0] composed into ONE 256 -> 128
+// part (no activation lies between them), so layer D has no stream of its own: off[D] == off[D + 1], one 128-tile-step layer
+// (16 ring groups) shorter. Behind the stream: the constant area as the f32 image has it (bias piece D, feature_linear's there
+// and unused here, = the composed bias bc: the hooks of layer D - 1 hand piece D to the views layer's output tiles), then the composed f32 block - Wc [W/2][W] row-major, bc [W/2] zero-padded to a piece.
+static inline bool make_x3f_layout(const MlpLayout& L, int W, X3Layout& X) {
+    if (!make_x3_layout(L, W, X)) return false;
+    const unsigned feature = X.off[L.D + 1] - X.off[L.D];
+    X.off[L.D + 1] = X.off[L.D];
+    X.pieces -= feature;
+    return X.pieces % X3Cfg::GP == 0;
+}
+__host__ __device__ inline unsigned x3f_const_floats(const MlpLayout& L) { return L.total - L.b_off[0]; }
+static inline unsigned x3f_composed_floats(const MlpLayout& L) { return (unsigned)(L.NT / 2 * 32) * (L.NT * 32) + kPiece; }
 
 // x = hi + mid + lo (+ |r| <= 2^-27 |x|) by round-to-nearest, two elements at a time (element 0 in the low half).
 __device__ __forceinline__ unsigned cvt_bf2(float x0, float x1) {
@@ -95,7 +108,9 @@ struct X3PackArgs {
     MlpLayout L;
     X3Layout X;
 };
-__global__ void pack_x3_kernel(const float* __restrict__ packed, X3PackArgs p, u32x4* __restrict__ img) {
+// FOLD: the hidden part of the views layer is split from the composed Wc (compose_x3f_kernel) instead of the f32 image
+template <bool FOLD>
+__global__ void pack_x3_kernel(const float* __restrict__ packed, X3PackArgs p, u32x4* __restrict__ img, const float* __restrict__ wc) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long ts = g >> 6;                                        // tile-step in the stream
     const int lane = (int)(g & 63);
@@ -111,6 +126,10 @@ __global__ void pack_x3_kernel(const float* __restrict__ packed, X3PackArgs p, u
     const f32x4 q0 = *reinterpret_cast<const f32x4*>(w + (q * OT32) * kPiece);
     const f32x4 q1 = *reinterpret_cast<const f32x4*>(w + ((q + 2) * OT32) * kPiece);
     float x[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
+    if (FOLD && l == p.L.D + 1 && u < p.L.NT) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = wc[row * (32 * p.L.NT) + 32 * u + 4 * lg + (j & 3) + 16 * (j >> 2)];
+    }
     u32x4 hi, mid, lo;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -125,6 +144,48 @@ __global__ void pack_x3_kernel(const float* __restrict__ packed, X3PackArgs p, u
     o[0] = hi;
     o[64] = mid;
     o[128] = lo;
+}
+
+// ---- the composed views layer of the folded image. h2 = relu(Wv[:, :W] (Wf h + bf) + Wv[:, W:] dirs + bv) has no activation
+// between feature_linear and views_linears[0]: Wc = Wv[:, :W] Wf and bc = Wv[:, :W] bf + bv, by a FIXED rule - the sum over
+// m = 0, 1, ..., W-1 in this order, in double from 0 (a product of two f32 values is exact in double: fused or not, the order
+// alone fixes the bits), bv added last, rounded once to f32. Everything is read from the f32 image through the forward column
+// map and its inverse (mlp_layout.h): column c of a hidden part is k-step hidden_step(c) of lane half hidden_half(c), and a
+// bias piece holds channel c at bias_index(c).
+// weight (row i, hidden column c) of layer l (OT32 32-row out tiles) in the f32 image
+__device__ __forceinline__ float x3f_weight(const float* __restrict__ packed, const MlpLayout& L, int l, int OT32, int i, int c) {
+    const int s = hidden_step(c), h = hidden_half(c);
+    return packed[L.w_off[l] + ((s >> 2) * OT32 + (i >> 5)) * kPiece + ((i & 31) + 32 * h) * 4 + (s & 3)];
+}
+// threads [0, W/2 * W): Wc; then one per float of the constant area (bias piece D receives bc, zero behind it); then the bc piece
+__global__ void compose_x3f_kernel(const float* __restrict__ packed, MlpLayout L, float* __restrict__ cst, float* __restrict__ comp) {
+    const int W = 32 * L.NT, WV = W / 2, D = L.D;
+    const int nconst = (int)x3f_const_floats(L);
+    int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t < WV * W) {
+        const int i = t / W, j = t % W;
+        double acc = 0.;
+        for (int m = 0; m < W; ++m)
+            acc += (double)x3f_weight(packed, L, D + 1, L.NT / 2, i, m) * (double)x3f_weight(packed, L, D, L.NT, m, j);
+        comp[t] = (float)acc;
+        return;
+    }
+    t -= WV * W;
+    if (t >= nconst + kPiece) return;
+    const int pos = t < nconst ? t % kPiece : t - nconst;              // position in a bias piece / index in the bc piece
+    const bool in_bias = t < nconst && t / kPiece == D;
+    if (t < nconst && !in_bias) { cst[t] = packed[L.b_off[0] + t]; return; }
+    // bias order -> channel: the inverse of bias_index
+    const int ch = in_bias ? 32 * (pos >> 5) + acc_channel(pos & 15, (pos >> 4) & 1) : pos;
+    float v = 0.f;
+    if (ch < WV && pos < (in_bias ? W : WV)) {
+        double acc = 0.;
+        for (int m = 0; m < W; ++m)
+            acc += (double)x3f_weight(packed, L, D + 1, L.NT / 2, ch, m) * (double)packed[L.b_off[D] + bias_index(m)];
+        acc += (double)packed[L.b_off[D + 1] + bias_index(ch)];
+        v = (float)acc;
+    }
+    (t < nconst ? cst[t] : comp[WV * W + pos]) = v;
 }
 
 // ---- the weight ring of one workgroup (the x3 counterpart of WRing in mlp_lds.hip; every member but f1 / f2 is
@@ -346,7 +407,9 @@ __device__ __forceinline__ void x3_part(X3Ring& st, f32x4 (&out)[X3Cfg::OT][2], 
     }
 }
 
-template <int NT, int SKIP>
+// FOLD: `img` is the folded image (make_x3f_layout) - no feature layer; the views layer reads relu(h) directly, and the
+// constant area comes from behind the image's stream instead of the f32 image.
+template <int NT, int SKIP, bool FOLD>
 __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, const void* img, int img_pieces) {
     static_assert(NT == X3Cfg::NT, "W = 256 only");
     using C = X3Cfg;
@@ -366,7 +429,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
     const float* const park_rd = park_w + (c + 32 * (g & 1)) * 4 + (g >> 1) * 256;
     {   // constant area: biases (one piece per layer), alpha head, rgb head - from the f32 image
         const int n = (int)(L.total - L.b_off[0]);
-        const float* __restrict__ gm = a.packed + L.b_off[0];
+        const float* __restrict__ gm = FOLD ? static_cast<const float*>(img) + (long)img_pieces * kPiece : a.packed + L.b_off[0];
         for (int i = tid * 4; i < n; i += 1024) *reinterpret_cast<f32x4*>(cst + i) = *reinterpret_cast<const f32x4*>(gm + i);
     }
     __syncthreads();
@@ -413,7 +476,13 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
             float emb[4 * kEmbQuads], demb[4 * kDirQuads];
             int hh = h;
             asm volatile("" : "+v"(hh));
-            encode_sample(a, s, hh, emb, demb);
+            if constexpr (FOLD) {       // spr opaque per round: its reciprocal (s / spr) is then formed here, not kept live (a spill)
+                MlpArgs ar = a;
+                asm volatile("" : "+s"(ar.spr));
+                encode_sample(ar, s, hh, emb, demb);
+            } else {
+                encode_sample(a, s, hh, emb, demb);
+            }
 #pragma unroll
             for (int k = 0; k < kEmbQuads; ++k)
                 *reinterpret_cast<f32x4*>(park + k * 256) = (f32x4){emb[4 * k], emb[4 * k + 1], emb[4 * k + 2], emb[4 * k + 3]};
@@ -441,23 +510,42 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
 
         float alpha[2] = {0.f, 0.f};
         auto layer = [&](f32x4 (&in)[OT][2], f32x4 (&out)[OT][2], int l, bool may_skip, bool may_be_last) __attribute__((always_inline)) {
-            if (may_be_last && l == L.D) {                                  // alpha_linear on relu(h)
+            if (!FOLD && may_be_last && l == L.D) {                                  // alpha_linear on relu(h)
                 x3_head<OT>(in, c_alpha + lane_off, alpha);
                 alpha[0] += c_alpha[NT * 32];
                 alpha[1] += c_alpha[NT * 32];
             }
             if (may_skip && l == L.skip + 1) x3_part<OT, kEmbQuads / 4, false>(st, out, b_park(0), no_hook);   // cat([input_pts, h])
             // input tiles 2u, 2u+1 are last read by the split of step u (during step u-1): dead from step u on
+            int lb = l + 1;                                                 // the bias piece handed to the dying input tiles
+            if constexpr (FOLD) asm volatile("" : "+s"(lb));                // kept scalar: as a VGPR induction address it spills
             x3_part<OT, NT, true>(st, out, b_acc(in), [&](int u, int t, int k) {
-                if (u > 0) { bias_tile(in, l + 1, 2 * u - 2, 8, t, k); bias_tile(in, l + 1, 2 * u - 1, 9, t, k); }
-                if (u == NT - 1) { bias_tile(in, l + 1, 2 * u, 10, t, k); bias_tile(in, l + 1, 2 * u + 1, 11, t, k); }
+                if (u > 0) { bias_tile(in, lb, 2 * u - 2, 8, t, k); bias_tile(in, lb, 2 * u - 1, 9, t, k); }
+                if (u == NT - 1) { bias_tile(in, lb, 2 * u, 10, t, k); bias_tile(in, lb, 2 * u + 1, 11, t, k); }
             });
+            if (FOLD && may_be_last && l == L.D - 1) {                      // folded: `out` is the last pts activation
+                x3_head<OT>(out, c_alpha + lane_off, alpha);
+                alpha[0] += c_alpha[NT * 32];
+                alpha[1] += c_alpha[NT * 32];
+            }
         };
 #pragma unroll 1
         for (int l = 1; l < L.D; l += 2) {                                  // D is even (host check): whole pairs
-            layer(P, Q, l, SKIP == 1, false);
-            layer(Q, P, l + 1, SKIP == 2, true);
+            layer(P, Q, l, SKIP == 1, FOLD);
+            if (!FOLD || l + 1 < L.D) layer(Q, P, l + 1, SKIP == 2, !FOLD);     // FOLD: no layer D (wave-uniform)
         }
+        float rgb[2][3];                                                    // rgb_linear: W/2 -> 3
+        if constexpr (FOLD) {
+            // h = relu(Q) is the last pts activation (one 256-wide layer fewer: the arrays have swapped roles). The composed
+            // views layer goes into P's first tiles, which hold its bias bc (piece D, written by layer D - 1 as they died);
+            // P's other tiles, dead, receive their half of the NEXT tile's layer 0 bias, the first half follows the head.
+            // (alpha_linear ran on relu(Q) behind layer D - 1, inside the loop: behind the loop the kernel spills VGPRs)
+            x3_part<OTV, NT, true>(st, P, b_acc(Q), [&](int u, int t, int k) { bias_tile(P, 0, OTV + u, 2, t, k); });
+            x3_part<OTV, kDirQuads / 4, false>(st, P, b_park(kEmbQuads), no_hook);
+            x3_head3<OTV>(P, c_rgb + lane_off, OTV * 16, rgb);
+#pragma unroll
+            for (int t = 0; t < OTV; ++t) { bias_tile(P, 0, t, 0, 0, 10); bias_tile(P, 0, t, 0, 1, 11); }
+        } else {
         // views_linears[0]: cat([feature, embedded dirs]) -> W/2 into Q's first tiles (no activation on the feature);
         // P receives the bias of the NEXT tile's layer 0 as its tiles die
         x3_part<OTV, NT, false>(st, Q, b_acc(P), [&](int u, int t, int k) {
@@ -465,8 +553,8 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
             if (u == NT - 1) { bias_tile(P, 0, 2 * u, 4, t, k); bias_tile(P, 0, 2 * u + 1, 5, t, k); }
         });
         x3_part<OTV, kDirQuads / 4, false>(st, Q, b_park(kEmbQuads), no_hook);
-        float rgb[2][3];                                                    // rgb_linear: W/2 -> 3
         x3_head3<OTV>(Q, c_rgb + lane_off, OTV * 16, rgb);
+        }
         // lane group n < 2 stores sample half n
         const int n = g & 1;
         int je = 16 * n + c;
@@ -491,25 +579,55 @@ size_t mlp_x3_bytes(const MlpLayout& L, int W) {
     return mlp_x3_covers(L, W) && make_x3_layout(L, W, X) ? (size_t)X.pieces * kPiece * 4 : 0;
 }
 
+size_t mlp_x3f_composed_floats(const MlpLayout& L, int W) { return mlp_x3_covers(L, W) ? x3f_composed_floats(L) : 0; }
+
+size_t mlp_x3f_bytes(const MlpLayout& L, int W) {
+    X3Layout X;
+    if (!mlp_x3_covers(L, W) || !make_x3f_layout(L, W, X)) return 0;
+    return ((size_t)X.pieces * kPiece + x3f_const_floats(L) + x3f_composed_floats(L)) * 4;
+}
+
 int pack_mlp_x3(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s) {
     X3PackArgs p;
     p.L = L;
     if (!mlp_x3_covers(L, W) || !make_x3_layout(L, W, p.X)) { set_error("nerfail_mlp_pack_x3: shape not covered (W = 256, even D <= 8)"); return NERFAIL_EINVAL; }
     const long threads = (long)p.X.pieces / 3 * 64;
-    pack_x3_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(packed, p, reinterpret_cast<u32x4*>(out));
+    pack_x3_kernel<false><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(packed, p, reinterpret_cast<u32x4*>(out), nullptr);
     NF_LAUNCHED("pack_x3_kernel");
     return NERFAIL_OK;
 }
 
-int launch_mlp_x3(const MlpArgs& a, const void* img, int W, hipStream_t s) {
-    X3Layout X;
-    if (!mlp_x3_covers(a.lay, W) || !make_x3_layout(a.lay, W, X)) { set_error("nerf_mlp_fwd_x3_kernel: shape not covered (W = 256, even D <= 8)"); return NERFAIL_EINVAL; }
-    if (a.M >= (1L << 36)) { set_error("nerfail_mlp_fwd: M must be below 2^36 samples per call"); return NERFAIL_EINVAL; }
+int pack_mlp_x3f(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s) {
+    X3PackArgs p;
+    p.L = L;
+    if (!mlp_x3_covers(L, W) || !make_x3f_layout(L, W, p.X)) { set_error("nerfail_mlp_pack_x3f: shape not covered (W = 256, even D <= 8)"); return NERFAIL_EINVAL; }
+    float* const cst = static_cast<float*>(out) + (size_t)p.X.pieces * kPiece;
+    float* const comp = cst + x3f_const_floats(L);
+    const long cthreads = (long)(W / 2) * W + x3f_const_floats(L) + kPiece;
+    compose_x3f_kernel<<<dim3((unsigned)((cthreads + 255) / 256)), dim3(256), 0, s>>>(packed, L, cst, comp);
+    NF_LAUNCHED("compose_x3f_kernel");
+    const long threads = (long)p.X.pieces / 3 * 64;
+    pack_x3_kernel<true><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(packed, p, reinterpret_cast<u32x4*>(out), comp);
+    NF_LAUNCHED("pack_x3_kernel");
+    return NERFAIL_OK;
+}
+
+template <bool FOLD>
+static void launch_x3(const MlpArgs& a, const void* img, int pieces, hipStream_t s) {
     const dim3 grid(mlp_grid_blocks((a.M + 31) / 32)), block(256);      // persistent: one 4-wave workgroup per CU
     const int skip_layer = a.lay.skip >= 0 ? a.lay.skip + 1 : -1;
-    if (skip_layer < 0) nerf_mlp_fwd_x3_kernel<8, 0><<<grid, block, 0, s>>>(a, img, (int)X.pieces);
-    else if (skip_layer & 1) nerf_mlp_fwd_x3_kernel<8, 1><<<grid, block, 0, s>>>(a, img, (int)X.pieces);
-    else nerf_mlp_fwd_x3_kernel<8, 2><<<grid, block, 0, s>>>(a, img, (int)X.pieces);
+    if (skip_layer < 0) nerf_mlp_fwd_x3_kernel<8, 0, FOLD><<<grid, block, 0, s>>>(a, img, pieces);
+    else if (skip_layer & 1) nerf_mlp_fwd_x3_kernel<8, 1, FOLD><<<grid, block, 0, s>>>(a, img, pieces);
+    else nerf_mlp_fwd_x3_kernel<8, 2, FOLD><<<grid, block, 0, s>>>(a, img, pieces);
+}
+
+// fold: `img` is the folded image of nerfail_mlp_pack_x3f
+int launch_mlp_x3(const MlpArgs& a, const void* img, int W, bool fold, hipStream_t s) {
+    X3Layout X;
+    if (!mlp_x3_covers(a.lay, W) || !(fold ? make_x3f_layout(a.lay, W, X) : make_x3_layout(a.lay, W, X))) { set_error("nerf_mlp_fwd_x3_kernel: shape not covered (W = 256, even D <= 8)"); return NERFAIL_EINVAL; }
+    if (a.M >= (1L << 36)) { set_error("nerfail_mlp_fwd: M must be below 2^36 samples per call"); return NERFAIL_EINVAL; }
+    if (fold) launch_x3<true>(a, img, (int)X.pieces, s);
+    else launch_x3<false>(a, img, (int)X.pieces, s);
     NF_LAUNCHED("nerf_mlp_fwd_x3_kernel");
     return NERFAIL_OK;
 }

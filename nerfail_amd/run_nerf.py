@@ -47,9 +47,11 @@ def _mlp_points(fn, pts, viewdirs):
                                                    _lib.dev(pts, 'pts'), _lib.dev(viewdirs, 'viewdirs'), R * N, N,
                                                    _lib.dev(raw), _lib.stream()))
         return raw
-    _lib.check(_lib.load().nerfail_mlp_fwd_x3(_lib.dev(fn.packed()), _lib.dev(fn.packed_x3()), fn.D, fn.W, fn._skip(),
-                                              _lib.dev(pts, 'pts'), _lib.dev(viewdirs, 'viewdirs'), R * N, N, _lib.dev(raw),
-                                              _lib.stream()))
+    lib = _lib.load()
+    fold, img = fn.x3_image()                            # feature_linear folded into the views layer where that is possible
+    fwd = lib.nerfail_mlp_fwd_x3f if fold else lib.nerfail_mlp_fwd_x3
+    _lib.check(fwd(_lib.dev(fn.packed()), _lib.dev(img), fn.D, fn.W, fn._skip(), _lib.dev(pts, 'pts'),
+                   _lib.dev(viewdirs, 'viewdirs'), R * N, N, _lib.dev(raw), _lib.stream()))
     return raw
 
 
@@ -58,10 +60,11 @@ def _mlp_rays(fn, rays, z_vals, acts=None):
     points o + d z are formed inside the kernel and never touch HBM). acts: the training forward's activation buffer."""
     R, N = z_vals.shape
     raw = torch.empty((R, N, 4), dtype=torch.float32, device=z_vals.device)
-    x3 = fn.packed_x3() if acts is None else None        # inference: the bf16x3 kernel where it covers the shape
-    _lib.check(_lib.load().nerfail_mlp_fwd_rays_x3(_lib.dev(fn.packed()), _lib.dev(x3), fn.D, fn.W, fn._skip(),
-                                                   _lib.dev(rays, 'rays'), _lib.dev(z_vals, 'z_vals'), R, N, _lib.dev(raw),
-                                                   _lib.dev(acts), _lib.stream()))
+    lib = _lib.load()
+    fold, img = fn.x3_image() if acts is None else (False, None)   # inference: the bf16x3 kernel where it covers the shape
+    fwd = lib.nerfail_mlp_fwd_rays_x3f if fold else lib.nerfail_mlp_fwd_rays_x3
+    _lib.check(fwd(_lib.dev(fn.packed()), _lib.dev(img), fn.D, fn.W, fn._skip(), _lib.dev(rays, 'rays'),
+                   _lib.dev(z_vals, 'z_vals'), R, N, _lib.dev(raw), _lib.dev(acts), _lib.stream()))
     return raw
 
 

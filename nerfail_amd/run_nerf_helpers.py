@@ -111,6 +111,8 @@ class NeRF(nn.Module):
         self._packed16_key = None
         self._packed_x3 = None
         self._packed_x3_key = None
+        self._packed_x3f = None
+        self._packed_x3f_key = None
         # 'f32' : exact-f32 MFMA kernel (default).  'f16x3': split-precision fp16 MFMA kernel, fp32-equivalent
         # results (each product as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi with fp32 accumulation), inference only.
         self.precision = 'f32'
@@ -158,6 +160,33 @@ class NeRF(nn.Module):
             _lib.check(lib.nerfail_mlp_pack_x3(_lib.dev(f32), self.D, self.W, self._skip(), _lib.dev(buf), _lib.stream()))
         self._packed_x3, self._packed_x3_key = buf, key
         return buf
+
+    def packed_x3f(self):
+        """Folded bf16x3 image (nerfail_mlp_pack_x3f): feature_linear composed into views_linears[0] on the device, once per
+        weight version - cached and invalidated like packed_x3(). None for shapes the kernel does not cover, and when the
+        composed block Wc / bc is not finite (weights so large that the product leaves f32): inference then takes the
+        unfolded image of packed_x3()."""
+        f32 = self.packed()
+        params = list(self.parameters())
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        if self._packed_x3f_key == key:
+            return self._packed_x3f
+        lib = _lib.load()
+        n = lib.nerfail_mlp_packed_x3f_bytes(self.D, self.W, self._skip())
+        buf = None
+        if n:
+            buf = torch.empty((n,), dtype=torch.uint8, device=f32.device)
+            _lib.check(lib.nerfail_mlp_pack_x3f(_lib.dev(f32), self.D, self.W, self._skip(), _lib.dev(buf), _lib.stream()))
+            composed = buf[n - 4 * lib.nerfail_mlp_x3f_composed_floats(self.D, self.W, self._skip()):].view(torch.float32)
+            if not bool(torch.isfinite(composed).all()):
+                buf = None
+        self._packed_x3f, self._packed_x3f_key = buf, key
+        return buf
+
+    def x3_image(self):
+        """(folded, image) of the bf16x3 inference kernel: the folded image where it exists, else the unfolded one (or None)."""
+        img = self.packed_x3f()
+        return (True, img) if img is not None else (False, self.packed_x3())
 
     def _mlp_params(self, keep):
         mp = _lib.MlpParams()
@@ -246,9 +275,11 @@ class NeRF(nn.Module):
         assert x.shape[-1] == self.input_ch + self.input_ch_views
         flat = x.reshape(-1, x.shape[-1])
         out = torch.empty((flat.shape[0], 4), dtype=torch.float32, device=flat.device)
-        _lib.check(_lib.load().nerfail_mlp_fwd_embedded_x3(_lib.dev(self.packed()), _lib.dev(self.packed_x3()), self.D, self.W,
-                                                           self._skip(), _lib.dev(flat, 'x'), flat.shape[0], _lib.dev(out),
-                                                           _lib.stream()))
+        lib = _lib.load()
+        fold, img = self.x3_image()
+        fwd = lib.nerfail_mlp_fwd_embedded_x3f if fold else lib.nerfail_mlp_fwd_embedded_x3
+        _lib.check(fwd(_lib.dev(self.packed()), _lib.dev(img), self.D, self.W, self._skip(), _lib.dev(flat, 'x'), flat.shape[0],
+                       _lib.dev(out), _lib.stream()))
         return out.reshape(x.shape[:-1] + (4,))
 
 
