@@ -188,26 +188,37 @@ __global__ void compose_x3f_kernel(const float* __restrict__ packed, MlpLayout L
     (t < nconst ? cst[t] : comp[WV * W + pos]) = v;
 }
 
-// ---- the weight ring of one workgroup (the x3 counterpart of WRing in mlp_lds.hip; every member but f1 / f2 is
-// wave-uniform). Refill interval: the SPG tile-steps from one boundary tile-step (inclusive) to the next; DMA P of the
-// interval is issued behind the first MFMA of its P-th tile-step (P < GPW), the boundary's own right after the barrier.
+// ---- the weight ring of one workgroup (the x3 counterpart of WRing in mlp_lds.hip; every member but f1 / f2 / voff / rl / rdp
+// is wave-uniform). Refill interval: the SPG tile-steps from one boundary tile-step (inclusive) to the next; DMA P of the
+// interval is issued behind the first MFMA of its P-th tile-step (P < GPW), the boundary's own behind its MFMA 4.
 // Boundary i + 1 needs group i + 1 landed; its DMAs are older than the two younger groups' 2 * GPW -> vmcnt(2 * GPW).
+// Bookkeeping in BYTES, by increments (no multiply or shift per DMA): `fill` and `srcb` carry the per-wave part
+// wave * GPW pieces from the start; a DMA takes both as they are, pieces 0..3 and 4..5 of a wave through the 12-bit
+// immediate (srcb steps over the first four pieces once, between DMA 3 and DMA 4; the LDS side is one add into m0). The
+// slot being filled is always the group read before the current one: fill = ring + rd (old) + wave part, so the ring
+// needs ONE wrap-around (rd's). Every update is one or two scalar instructions pinned (opaque copy) into an MFMA gap that
+// has room for them (x3_step).
+typedef __attribute__((address_space(3))) char lds_char_t;
+typedef __attribute__((address_space(3))) const char lds_cchar_t;
 struct X3Ring {
     using C = X3Cfg;
+    static constexpr int kPB = kPiece * 4;                           // bytes of a piece
+    static constexpr int kGB = C::GP * kPB;                          // bytes of a ring group
     __amdgpu_buffer_rsrc_t rsrc;     // the x3 image as a raw buffer (reads past its end return 0, never fault)
     int voff;                        // lane * 16
-    float* ring;                     // LDS ring base
-    const float* rl;                 // ring + lane * 4
-    int total;                       // stream length in pieces (multiple of GP)
-    int src, slot, rd, wave;         // next group's first source piece, its ring group, first ring piece of the group read next
+    lds_char_t* ring;                // LDS ring base
+    lds_cchar_t* rl;                 // ring + lane * 16
+    lds_cchar_t* rdp;                // rl + rd: the fragment reads' address (one per group, constant offsets)
+    lds_char_t* fill;                // this wave's first piece of the ring group being filled
+    int woff;                        // wave * GPW pieces
+    int src_end;                     // stream length + woff
+    int srcb;                        // source offset of this wave's next DMA block (pieces 0..3, then 4..)
+    int rd;                          // offset in the ring of the group read next
     u32x4 f1[3], f2[3];              // fragments of the next two tile-steps
 
     template <int I>
     __device__ __forceinline__ void dma_at() const {
-        constexpr int B4 = I / 4;                                  // one base per block of 4 pieces (12-bit immediate)
-        const int first = wave * C::GPW + 4 * B4;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(ring + (slot * C::GP + first) * kPiece), 16, voff,
-                                                 (src + first) * (kPiece * 4), (I % 4) * kPiece * 4, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(fill + (I / 4) * 4 * kPB), 16, voff, srcb, (I % 4) * kPB, 0);
     }
     __device__ __forceinline__ void dma(int i) const {             // i is a constant after unrolling
         switch (i) {
@@ -216,32 +227,61 @@ struct X3Ring {
             default: break;
         }
     }
-    __device__ __forceinline__ void group_issued() {
-        src += C::GP;
-        if (src >= total) src = 0;
-        slot = (slot + 1 == C::S) ? 0 : slot + 1;
+    // srcb: + 4 pieces between DMA 3 and DMA 4, the rest of a group behind the last DMA, then the wrap to the stream's start
+    __device__ __forceinline__ void src_mid() { srcb += 4 * kPB; asm volatile("" : "+s"(srcb)); }
+    __device__ __forceinline__ void src_step() { srcb += kGB - 4 * kPB; asm volatile("" : "+s"(srcb)); }
+    __device__ __forceinline__ void src_wrap() { srcb = srcb == src_end ? woff : srcb; asm volatile("" : "+s"(srcb)); }
+    // behind the last fragment read of a group: its slot is the next to be filled, the group after it the next to be read
+    __device__ __forceinline__ void rd_step() {
+        fill = ring + rd + woff;
+        rd += kGB;
+        asm volatile("" : "+s"(fill), "+s"(rd));
     }
+    __device__ __forceinline__ void rd_wrap() { rd = rd == C::RP * kPB ? 0 : rd; asm volatile("" : "+s"(rd)); }
+    __device__ __forceinline__ void rd_apply() { rdp = rl + rd; asm volatile("" : "+v"(rdp)); }
     __device__ __forceinline__ void boundary() const {
         lds_wait_vmcnt<(C::S - 2) * C::GPW>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
-    // plane p of the tile-step at position POS (mod SPG) of the group read next: a constant offset from one address per group
-    __device__ __forceinline__ u32x4 frag(int POS, int p) const { return *(lds_cu4*)(rl + (rd + 3 * POS + p) * kPiece); }
-    __device__ __forceinline__ void next_group() {
-        rd += C::GP;
-        if (rd >= C::RP) rd = 0;
+    // The ring's share of the gap behind MFMA k of the tile-step at position P of the refill interval. Gaps 4, 7 and 9 carry
+    // one instruction of the operand split at most (x3_part), gap 0 one load.
+    __device__ __forceinline__ void side(int P, int k) {
+        if (P == 0 ? k == 4 : (P < C::GPW && k == 0)) dma(P);      // the boundary's gap 0 holds the wait and the barrier
+        if (P == 3 && k == 4) src_mid();
+        if (P == C::GPW && k == 4) src_step();
+        if (P == C::GPW && k == 7) src_wrap();
+        if (P == C::SPG - 1 && k == 4) rd_step();                  // the last fragment read of the group was behind MFMA 3
+        if (P == C::SPG - 1 && k == 7) rd_wrap();
+        if (P == C::SPG - 1 && k == 9) rd_apply();
     }
+    // plane p of the tile-step at position POS (mod SPG) of the group read next: a constant offset from one address per group
+    __device__ __forceinline__ u32x4 frag(int POS, int p) const { return *(lds_cu4*)(rdp + (3 * POS + p) * kPB); }
     // S-1 groups issued, group 0 readable; then the state right behind a boundary tile-step that sat two tile-steps before
     // the stream's first: DMAs 0 and 1 of group S-1 issued, the fragments of tile-steps 0 and 1 read
-    __device__ __forceinline__ void start() {
+    __device__ __forceinline__ void start(float* ring0, int lane, int wave, int total) {
+        static_assert(C::GPW > 4 && C::GPW <= 8 && C::GPW < C::SPG - 1, "side(): two DMA blocks per wave, bookkeeping behind the last DMA");
+        voff = lane * 16;
+        ring = (lds_char_t*)ring0;
+        rl = ring + lane * 16;
+        woff = wave * C::GPW * kPB;
+        src_end = total * kPB + woff;
+        srcb = woff;
+        fill = ring + woff;
 #pragma unroll
         for (int g = 0; g < C::S - 1; ++g) {
 #pragma unroll
-            for (int i = 0; i < C::GPW; ++i) dma(i);
-            group_issued();
+            for (int i = 0; i < C::GPW; ++i) {
+                if (i == 4) src_mid();
+                dma(i);
+            }
+            src_step();
+            src_wrap();
+            fill += kGB;
         }
+        rd = 0;
+        rdp = rl;
         boundary();
         dma(0);
         dma(1);
@@ -317,18 +357,21 @@ __device__ __forceinline__ void x3_head3(const f32x4 (&x)[NIN][2], const float* 
 
 // One tile-step at stream position POS (mod SPG, a constant after unrolling): the twelve MFMAs of out tile `acc`, product
 // by product smallest first, each for both sample halves (MFMA k = product k / 2, half k % 2). A 16x16x32 MFMA leaves 8 of
-// its 16 cycles for vector issue: about two instructions of any kind per gap. Behind MFMA k: side(k) (operand
-// preparation, bias tiles), then behind MFMA 0 the refill DMA and behind MFMAs 1..3 a fragment read of the tile-step two
-// ahead (an LDS load issued by side(0) or side(1) is older than those reads: waiting for it does not wait for them).
+// its 16 cycles for vector issue: the budget of a gap is three instructions of any kind (tools/mfma_gaps.py). Behind MFMA
+// k: in the boundary tile-step's gap 0 the wait and the barrier (the refill DMA and the fragment reads behind them are the
+// first to touch the new group and the released slot; MFMA 0 itself runs on fragments read two tile-steps before), then
+// side(k) (operand preparation, bias tiles), the ring's bookkeeping (X3Ring::side), and behind MFMAs 1..3 a fragment read of
+// the tile-step two ahead (an LDS load issued by side(0) or side(1) is older than those reads: waiting for it does not
+// wait for them).
 template <class Side>
 __device__ __forceinline__ void x3_step(X3Ring& st, const int POS, f32x4 (&acc)[2], const u32x4 (&b)[2][3], Side side) {
     using C = X3Cfg;
     const int P = (POS - C::kSync + C::SPG) % C::SPG;              // position in the refill interval
     const int AHEAD = (POS + 2) % C::SPG;
+    static_assert((C::SPG - 1 + C::kSync + 2) % C::SPG == C::SPG - 1, "the group's last fragments are read at P = SPG - 1");
     u32x4 a[3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) { a[p] = st.f1[p]; st.f1[p] = st.f2[p]; }
-    if (P == 0) st.boundary();
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
         const int pr = k >> 1, n = k & 1;                          // a1b1, a0b2, a2b0, a0b1, a1b0, a0b0
@@ -337,16 +380,13 @@ __device__ __forceinline__ void x3_step(X3Ring& st, const int POS, f32x4 (&acc)[
         __builtin_amdgcn_sched_barrier(0);
         mfma_x3(acc[n], a[pa], b[n][pb]);
         __builtin_amdgcn_sched_barrier(0);
+        if (P == 0 && k == 0) st.boundary();
         side(k);
-        if (k == 0 && P < C::GPW) st.dma(P);
+        st.side(P, k);
         if (k == 1) st.f2[1] = st.frag(AHEAD, 1);
         if (k == 2) st.f2[0] = st.frag(AHEAD, 0);
-        if (k == 3) {
-            st.f2[2] = st.frag(AHEAD, 2);
-            if (AHEAD == C::SPG - 1) st.next_group();
-        }
+        if (k == 3) st.f2[2] = st.frag(AHEAD, 2);
     }
-    if (P == C::SPG - 1) st.group_issued();
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -355,7 +395,7 @@ __device__ __forceinline__ void x3_step(X3Ring& st, const int POS, f32x4 (&acc)[
 // accumulator register, relu'd here when RELU, or a parked encoding value). Step s+1's operand is split during step s:
 // pair (n, p) = (t / 4, t % 4) in tile-step t < 8, at most two instructions per gap - load 0, load 1 behind MFMAs 0, 1;
 // ReLU behind 2, 3; then hi; extract hi; subtract; mid; extract mid; subtract; lo behind 4..10. Step 0's cannot be early
-// (its source is the layer before). hook(s, t, k): behind MFMAs k = 10, 11 of tile-step t of step s.
+// (its source is the layer before). hook(s, t, k): behind MFMA k of tile-step t of step s (bias tiles: gaps the split leaves room in).
 template <int OT, int NS, bool RELU, class Ld, class Hook>
 __device__ __forceinline__ void x3_part(X3Ring& st, f32x4 (&out)[X3Cfg::OT][2], Ld ld, Hook hook) {
     static_assert((NS * OT) % X3Cfg::SPG == 0 && OT >= 8, "a part is a whole number of ring groups; 8 pairs per step");
@@ -394,7 +434,7 @@ __device__ __forceinline__ void x3_part(X3Ring& st, f32x4 (&out)[X3Cfg::OT][2], 
                     if (k == 9) xs[t] -= es[t];
                     if (k == 10) bn[n][2][p] = cvt_bf2(xs[t][0], xs[t][1]);
                 }
-                if (k >= 10) hook(s, t, k);
+                hook(s, t, k);
             };
             x3_step(st, (s * OT + t) % X3Cfg::SPG, out[t], b, side);
         }
@@ -441,26 +481,31 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
 
     X3Ring st;
     st.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(img), 0, img_pieces * (kPiece * 4), 0x00020000);
-    st.voff = lane * 16; st.ring = ring0; st.rl = ring0 + lane * 4;
-    st.total = img_pieces; st.src = 0; st.slot = 0; st.rd = 0; st.wave = wave;
-    st.start();
+    st.start(ring0, lane, wave, img_pieces);
 
     f32x4 P[OT][2], Q[OT][2];
     // dst[i] = bias of layer l, tile i (f32, in AGPRs), as side work of two tile-steps: the LDS read into the first sample
-    // half behind MFMA 10 of tile-step t0, the register copy into the second behind MFMA 11 of tile-step t0 + 1 (when the
-    // read has landed: a copy right behind it would wait for it)
+    // half behind MFMA 10 of tile-step t0, the four register copies into the second behind MFMAs 5, 6, 8, 9 of tile-step
+    // t0 + 1 (when the read has landed: a copy right behind it would wait for it). Those gaps are empty in tile-steps 8..15
+    // of a step, where the layers' bias tiles sit, and hold two split instructions at most below (the views layer's);
+    // X3Ring::side uses gaps 0, 4, 7, 9 and shares gap 9 only in the interval's last tile-step (t = 5 mod 8: no bias copy).
     auto bias_tile = [&](f32x4 (&dst)[OT][2], int l, int i, int t0, int t, int k) {
         if (t == t0 && k == 10) {
             dst[i][0] = lds_read4(cst_g + l * kPiece + x3_tile_off(i));
-            asm volatile("" : "+a"(dst[i][0]));
         }
         if (t == t0 + 1 && k == 11) {
             dst[i][1] = dst[i][0];
             asm volatile("" : "+a"(dst[i][1]));
         }
     };
+    // (outside the stream: a whole tile at once)
+    auto bias_tile_now = [&](f32x4 (&dst)[OT][2], int l, int i) {
+        dst[i][0] = lds_read4(cst_g + l * kPiece + x3_tile_off(i));
+        dst[i][1] = dst[i][0];
+        asm volatile("" : "+a"(dst[i][0]), "+a"(dst[i][1]));
+    };
 #pragma unroll
-    for (int t = 0; t < OT; ++t) { bias_tile(P, 0, t, 0, 0, 10); bias_tile(P, 0, t, 0, 1, 11); }                    // later rounds: written during the views layer
+    for (int t = 0; t < OT; ++t) bias_tile_now(P, 0, t);                    // later rounds: written during the views layer
 
     const int ntiles = (int)((a.M + 31) / 32);
     const int nrounds = (int)((ntiles + (long)gridDim.x * 4 - 1) / ((long)gridDim.x * 4));
@@ -544,7 +589,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
             x3_part<OTV, kDirQuads / 4, false>(st, P, b_park(kEmbQuads), no_hook);
             x3_head3<OTV>(P, c_rgb + lane_off, OTV * 16, rgb);
 #pragma unroll
-            for (int t = 0; t < OTV; ++t) { bias_tile(P, 0, t, 0, 0, 10); bias_tile(P, 0, t, 0, 1, 11); }
+            for (int t = 0; t < OTV; ++t) bias_tile_now(P, 0, t);
         } else {
         // views_linears[0]: cat([feature, embedded dirs]) -> W/2 into Q's first tiles (no activation on the feature);
         // P receives the bias of the NEXT tile's layer 0 as its tiles die
