@@ -25,6 +25,7 @@ from torch import nn
 
 from . import _lib
 from . import ops
+from ._images import ImageCache
 
 
 class MyCNN(nn.Module):
@@ -38,8 +39,7 @@ class MyCNN(nn.Module):
         self.fc1 = nn.Linear(1024, 512)
         self.fc2 = nn.Linear(512, num_classes)
         self.num_classes = num_classes
-        self._packed = None
-        self._packed_key = None
+        self._images = ImageCache(self._params, {'packed': (self._pack, None)})
 
     def _params(self):
         ps = []
@@ -48,24 +48,20 @@ class MyCNN(nn.Module):
             ps += [c.weight, c.bias]
         return ps + [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
 
-    def _key(self, ps):
-        return tuple((p.data_ptr(), p._version) for p in ps)
+    def _pack(self):
+        lib = _lib.load()
+        src = [_lib.f32c(p) for p in self._params()]
+        for p in src:
+            _lib.dev(p, 'MyCNN parameter')
+        packed = torch.empty((lib.nerfail_cnn_packed_floats(self.num_classes),), dtype=torch.float32, device=src[0].device)
+        ptrs = (ctypes.c_void_p * len(src))(*[p.data_ptr() for p in src])
+        _lib.check(lib.nerfail_cnn_pack(ptrs, self.num_classes, _lib.dev(packed), _lib.stream()))
+        return packed
 
     def packed(self):
-        """The MFMA weight image (nerfail_cnn_pack), rebuilt when any parameter moves or is written in place."""
-        ps = self._params()
-        key = self._key(ps)
-        if self._packed is None or key != self._packed_key:
-            dev = ps[0].device
-            lib = _lib.load()
-            src = [_lib.f32c(p) for p in ps]
-            for p in src:
-                _lib.dev(p, 'MyCNN parameter')
-            packed = torch.empty((lib.nerfail_cnn_packed_floats(self.num_classes),), dtype=torch.float32, device=dev)
-            ptrs = (ctypes.c_void_p * len(src))(*[p.data_ptr() for p in src])
-            _lib.check(lib.nerfail_cnn_pack(ptrs, self.num_classes, _lib.dev(packed), _lib.stream()))
-            self._packed, self._packed_key = packed, key
-        return self._packed
+        """The MFMA weight image (nerfail_cnn_pack), cached like NeRF's (_images.ImageCache): rebuilt when any parameter
+        moves or is written in place."""
+        return self._images.get('packed')
 
     def forward(self, x):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -98,10 +94,10 @@ class MyCNN(nn.Module):
             raise RuntimeError('MyCNN.input_gradients: `logits` is not the output of a mask-keeping forward of a MyCNN (a '
                                'grad-enabled forward of an input that requires grad, its graph not yet freed)')
         packed, ws, masks, (H, W) = saved
-        if self._packed is None or packed.data_ptr() != self._packed.data_ptr():
+        if not self._images.holds('packed', packed):
             raise RuntimeError('MyCNN.input_gradients: `logits` did not come from the last weight image of this module '
                                '(another module\'s forward, or the parameters were written and repacked since)')
-        if self._key(self._params()) != self._packed_key:
+        if not self._images.is_current('packed', packed):
             raise RuntimeError('MyCNN.input_gradients: a parameter was written or moved since the forward that returned '
                                '`logits`; run the forward again')
         if not isinstance(d_logits, torch.Tensor) or d_logits.dim() != 3 or tuple(d_logits.shape[1:]) != tuple(logits.shape):

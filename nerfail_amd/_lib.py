@@ -35,6 +35,26 @@ class MlpParams(ctypes.Structure):
                 ('alpha_w', c_p), ('alpha_b', c_p), ('rgb_w', c_p), ('rgb_b', c_p)]
 
 
+def mlp_params(D, W, input_ch, input_ch_views, skip, tensors, keep):
+    """struct nerfail_mlp_params over `tensors`: 2 D + 8 of them in _train.ordered_params order - the parameters of a network,
+    or the buffers that receive their gradients. With a list `keep`, every tensor that is not contiguous float32 is copied and
+    all of them are appended to `keep`: the caller holds that list until the launch reading the struct has been enqueued,
+    or the copies are freed under it. keep=None takes the pointers of the tensors as they are (outputs, where a copy would
+    swallow the result: the caller passes contiguous float32 and keeps them alive itself)."""
+    if keep is not None:
+        tensors = [f32c(t) for t in tensors]
+        keep += tensors
+    ptrs = [t.data_ptr() for t in tensors]
+    if len(ptrs) != 2 * D + 8:
+        raise ValueError('nerfail_mlp_params: D = %d takes %d tensors (got %d)' % (D, 2 * D + 8, len(ptrs)))
+    mp = MlpParams()
+    mp.D, mp.W, mp.input_ch, mp.input_ch_views, mp.skip = D, W, input_ch, input_ch_views, skip
+    for i in range(D):
+        mp.pts_w[i], mp.pts_b[i] = ptrs[2 * i], ptrs[2 * i + 1]
+    (mp.views_w, mp.views_b, mp.feature_w, mp.feature_b, mp.alpha_w, mp.alpha_b, mp.rgb_w, mp.rgb_b) = ptrs[2 * D:]
+    return mp
+
+
 # name -> (restype, argtypes); every symbol include/nerfail_hip.h declares
 SIGNATURES = {
     'nerfail_abi_version': (c_i, []),

@@ -7,88 +7,34 @@ Gradients flow to the parameters of network_fn / network_fine only: rays are dat
 import torch
 
 from . import _lib
+from .run_nerf_helpers import mlp_forward
 
-PARAM_ORDER = None
 
-
+# The weight images live in the network's one cache (NeRF._images, rules in _images.py); these are its training-side names.
 def ordered_params(net):
     """Parameters in the fixed order used for Function.apply / grads: pts_linears (w, b)*D, views, feature, alpha, rgb."""
-    ps = []
-    for l in net.pts_linears:
-        ps += [l.weight, l.bias]
-    ps += [net.views_linears[0].weight, net.views_linears[0].bias, net.feature_linear.weight, net.feature_linear.bias,
-           net.alpha_linear.weight, net.alpha_linear.bias, net.rgb_linear.weight, net.rgb_linear.bias]
-    return ps
+    return net.ordered_params()
 
 
 def _grads_struct(net, tensors):
-    """nerfail_mlp_params filled with the data pointers of `tensors` (same order as ordered_params)."""
-    mp = _lib.MlpParams()
-    mp.D, mp.W, mp.input_ch, mp.input_ch_views, mp.skip = net.D, net.W, net.input_ch, net.input_ch_views, net._skip()
-    it = iter(tensors)
-    for i in range(net.D):
-        mp.pts_w[i] = next(it).data_ptr()
-        mp.pts_b[i] = next(it).data_ptr()
-    mp.views_w, mp.views_b = next(it).data_ptr(), next(it).data_ptr()
-    mp.feature_w, mp.feature_b = next(it).data_ptr(), next(it).data_ptr()
-    mp.alpha_w, mp.alpha_b = next(it).data_ptr(), next(it).data_ptr()
-    mp.rgb_w, mp.rgb_b = next(it).data_ptr(), next(it).data_ptr()
-    return mp
+    """nerfail_mlp_params over `tensors` (ordered_params order), used as they are: the buffers the gradients are written to."""
+    return _lib.mlp_params(net.D, net.W, net.input_ch, net.input_ch_views, net._skip(), tensors, None)
 
 
 def packed_T(net):
-    """Transposed weight image for the backward-data pass, cached like NeRF.packed()."""
-    params = ordered_params(net)
-    key = tuple((p.data_ptr(), p._version) for p in params)
-    if getattr(net, '_packedT', None) is not None and net._packedT_key == key:
-        return net._packedT
-    lib = _lib.load()
-    n = lib.nerfail_mlp_packed_T_floats(net.D, net.W, net._skip())
-    keep = [_lib.f32c(p) for p in params]
-    mp = _grads_struct(net, keep)
-    buf = torch.empty((n,), dtype=torch.float32, device=params[0].device)
-    _lib.check(lib.nerfail_mlp_pack_T(mp, _lib.dev(buf), _lib.stream()))
-    net._packedT, net._packedT_key = buf, key
-    return buf
+    """Transposed weight image for the backward-data pass (nerfail_mlp_pack_T)."""
+    return net._images.get('f32_T')
 
 
 def packed_both(net):
-    """Forward and transposed weight images of `net` from ONE launch (nerfail_mlp_pack_train), filling the caches of
-    NeRF.packed() and packed_T(): the training loop re-packs both after every optimizer step."""
-    params = list(net.parameters())
-    key = tuple((p.data_ptr(), p._version) for p in params)
-    keyT = tuple((p.data_ptr(), p._version) for p in ordered_params(net))
-    if net._packed is not None and net._packed_key == key and getattr(net, '_packedT', None) is not None and net._packedT_key == keyT:
-        return net._packed, net._packedT
-    lib = _lib.load()
-    n, nT = lib.nerfail_mlp_packed_floats(net.D, net.W, net._skip()), lib.nerfail_mlp_packed_T_floats(net.D, net.W, net._skip())
-    if n == 0:
-        raise NotImplementedError('unsupported NeRF shape D=%d W=%d (W in {64,128,256})' % (net.D, net.W))
-    keep = []
-    mp = net._mlp_params(keep)
-    buf = torch.empty((n,), dtype=torch.float32, device=params[0].device)
-    bufT = torch.empty((nT,), dtype=torch.float32, device=params[0].device)
-    _lib.check(lib.nerfail_mlp_pack_train(mp, _lib.dev(buf), _lib.dev(bufT), _lib.stream()))
-    net._packed, net._packed_key = buf, key
-    net._packedT, net._packedT_key = bufT, keyT
-    return buf, bufT
+    """Forward and transposed weight images of `net` from ONE launch (nerfail_mlp_pack_train); afterwards NeRF.packed() and
+    packed_T() are hits: the training loop re-packs both after every optimizer step."""
+    return net.packed_both()
 
 
 def packed_f16_T(net):
-    """fp16 hi/lo image of the transposed weights (split-precision backward-data), cached on parameter versions."""
-    params = ordered_params(net)
-    key = tuple((p.data_ptr(), p._version) for p in params)
-    if getattr(net, '_packed16T', None) is not None and net._packed16T_key == key:
-        return net._packed16T
-    lib = _lib.load()
-    n = lib.nerfail_mlp_f16_image_T_bytes(net.D, net.W, net._skip())
-    net.check_f16x3_range()
-    keep = [_lib.f32c(p) for p in params]
-    mp = _grads_struct(net, keep)
-    buf = torch.empty((n,), dtype=torch.uint8, device=params[0].device)
-    _lib.check(lib.nerfail_mlp_pack_f16_T(mp, _lib.dev(buf), _lib.stream()))
-    net._packed16T, net._packed16T_key = buf, key
-    return buf
+    """fp16 hi/lo image of the transposed weights (split-precision backward-data, nerfail_mlp_pack_f16_T)."""
+    return net._images.get('f16_T')
 
 
 def acts_floats(net, M):
@@ -99,40 +45,27 @@ def dz_floats(net, M):
     return _lib.load().nerfail_mlp_train_dz_floats(net.D, net.W, M)
 
 
-def mlp_fwd_train(net, pts, viewdirs, acts=None):
-    """Forward that saves the activations; `acts`: where (a slice of a buffer shared by the coarse and the fine pass, so
-    that ONE backward launch can walk both), else a fresh buffer."""
-    lib = _lib.load()
-    R, N = pts.shape[0], pts.shape[1]
-    raw = torch.empty((R, N, 4), dtype=torch.float32, device=pts.device)
+def _train_buffers(net, R, N, acts, device):
+    """(raw, acts) of a training forward of R * N samples; `acts` given: checked, else a fresh buffer."""
     if acts is None:
-        acts = torch.empty((acts_floats(net, R * N),), dtype=torch.float32, device=pts.device)
+        acts = torch.empty((acts_floats(net, R * N),), dtype=torch.float32, device=device)
     elif acts.numel() != acts_floats(net, R * N):
         raise ValueError('acts buffer has %d floats, the pass needs %d' % (acts.numel(), acts_floats(net, R * N)))
-    if getattr(net, 'precision', 'f32') != 'f16x3':
-        packed_both(net)                                     # one launch for both images (the backward needs the second)
-    if getattr(net, 'precision', 'f32') == 'f16x3':        # split-precision forward, same saved activations
-        _lib.check(lib.nerfail_mlp_fwd_f16_train(_lib.dev(net.packed()), _lib.dev(net.packed_f16()), net.D, net.W, net._skip(),
-                                                 _lib.dev(pts), _lib.dev(viewdirs), R * N, N, _lib.dev(raw), _lib.dev(acts),
-                                                 _lib.stream()))
-        return raw, acts
-    _lib.check(lib.nerfail_mlp_fwd_train(_lib.dev(net.packed()), net.D, net.W, net._skip(), _lib.dev(pts), _lib.dev(viewdirs),
-                                         R * N, N, _lib.dev(raw), _lib.dev(acts), _lib.stream()))
-    return raw, acts
+    return torch.empty((R, N, 4), dtype=torch.float32, device=device), acts
+
+
+def mlp_fwd_train(net, pts, viewdirs, acts=None):
+    """Forward that saves the activations; `acts`: where (a slice of a buffer shared by the coarse and the fine pass, so
+    that ONE backward launch can walk both), else a fresh buffer. precision 'f16x3': the split-precision forward, same
+    saved activations, and no joint f32 pack (its backward-data pass reads the fp16 transposed image)."""
+    raw, acts = _train_buffers(net, pts.shape[0], pts.shape[1], acts, pts.device)
+    return mlp_forward(net, raw, pts=pts, viewdirs=viewdirs, acts=acts), acts
 
 
 def mlp_fwd_train_rays(net, rays, z_vals, acts=None):
     """mlp_fwd_train with the sample points formed inside the kernel (nerfail_mlp_fwd_rays): rays [R,11], z_vals [R,N]."""
-    R, N = z_vals.shape
-    if acts is None:
-        acts = torch.empty((acts_floats(net, R * N),), dtype=torch.float32, device=z_vals.device)
-    elif acts.numel() != acts_floats(net, R * N):
-        raise ValueError('acts buffer has %d floats, the pass needs %d' % (acts.numel(), acts_floats(net, R * N)))
-    packed_both(net)
-    raw = torch.empty((R, N, 4), dtype=torch.float32, device=z_vals.device)
-    _lib.check(_lib.load().nerfail_mlp_fwd_rays(_lib.dev(net.packed()), net.D, net.W, net._skip(), _lib.dev(rays), _lib.dev(z_vals), R, N,
-                                                _lib.dev(raw), _lib.dev(acts), _lib.stream()))
-    return raw, acts
+    raw, acts = _train_buffers(net, z_vals.shape[0], z_vals.shape[1], acts, z_vals.device)
+    return mlp_forward(net, raw, rays=rays, z_vals=z_vals, acts=acts), acts
 
 
 def _same_arch(a, b):

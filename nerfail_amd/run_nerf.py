@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from .optim import Adam, decayed_lrate  # noqa: F401
 from .run_nerf_helpers import (NeRF, Embedder, get_embedder, get_rays, get_rays_np, img2mse, mse2psnr, to8b,  # noqa: F401
-                               sample_pdf, linspace01, _cuda, _k4, _c2w12)
+                               sample_pdf, linspace01, mlp_forward, _cuda, _k4, _c2w12)
 
 np.random.seed(0)      # RN:23
 DEBUG = False
@@ -39,33 +39,17 @@ def _is_fused(embed_fn, embeddirs_fn, fn):
 
 
 def _mlp_points(fn, pts, viewdirs):
-    """Fused encode + MLP on raw points: pts [R,N,3], viewdirs [R,3] -> raw [R,N,4] (nerfail_mlp_fwd)."""
-    R, N = pts.shape[0], pts.shape[1]
-    raw = torch.empty((R, N, 4), dtype=torch.float32, device=pts.device)
-    if getattr(fn, 'precision', 'f32') == 'f16x3':       # opt-in split-precision kernel (fp32-equivalent results)
-        _lib.check(_lib.load().nerfail_mlp_fwd_f16(_lib.dev(fn.packed()), _lib.dev(fn.packed_f16()), fn.D, fn.W, fn._skip(),
-                                                   _lib.dev(pts, 'pts'), _lib.dev(viewdirs, 'viewdirs'), R * N, N,
-                                                   _lib.dev(raw), _lib.stream()))
-        return raw
-    lib = _lib.load()
-    fold, img = fn.x3_image()                            # feature_linear folded into the views layer where that is possible
-    fwd = lib.nerfail_mlp_fwd_x3f if fold else lib.nerfail_mlp_fwd_x3
-    _lib.check(fwd(_lib.dev(fn.packed()), _lib.dev(img), fn.D, fn.W, fn._skip(), _lib.dev(pts, 'pts'),
-                   _lib.dev(viewdirs, 'viewdirs'), R * N, N, _lib.dev(raw), _lib.stream()))
-    return raw
+    """Fused encode + MLP on raw points: pts [R,N,3], viewdirs [R,3] -> raw [R,N,4] (mlp_forward: the bf16x3 kernel with
+    feature_linear folded into the views layer where that is possible, the opt-in split-precision kernel for 'f16x3')."""
+    raw = torch.empty((pts.shape[0], pts.shape[1], 4), dtype=torch.float32, device=pts.device)
+    return mlp_forward(fn, raw, pts=pts, viewdirs=viewdirs)
 
 
 def _mlp_rays(fn, rays, z_vals, acts=None):
-    """Fused sample-point formation + encode + MLP: packed rays [R,11], z_vals [R,N] -> raw [R,N,4] (nerfail_mlp_fwd_rays: the
-    points o + d z are formed inside the kernel and never touch HBM). acts: the training forward's activation buffer."""
-    R, N = z_vals.shape
-    raw = torch.empty((R, N, 4), dtype=torch.float32, device=z_vals.device)
-    lib = _lib.load()
-    fold, img = fn.x3_image() if acts is None else (False, None)   # inference: the bf16x3 kernel where it covers the shape
-    fwd = lib.nerfail_mlp_fwd_rays_x3f if fold else lib.nerfail_mlp_fwd_rays_x3
-    _lib.check(fwd(_lib.dev(fn.packed()), _lib.dev(img), fn.D, fn.W, fn._skip(), _lib.dev(rays, 'rays'),
-                   _lib.dev(z_vals, 'z_vals'), R, N, _lib.dev(raw), _lib.dev(acts), _lib.stream()))
-    return raw
+    """Fused sample-point formation + encode + MLP: packed rays [R,11], z_vals [R,N] -> raw [R,N,4] (the points o + d z are
+    formed inside the kernel and never touch HBM). acts: the training forward's activation buffer."""
+    raw = torch.empty(tuple(z_vals.shape) + (4,), dtype=torch.float32, device=z_vals.device)
+    return mlp_forward(fn, raw, rays=rays, z_vals=z_vals, acts=acts)
 
 
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64):

@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._images import ImageCache
 
 # Misc (RH:9-11) - host-side one-liners, kept for drop-in completeness
 class _Img2Mse(torch.autograd.Function):
@@ -85,7 +86,12 @@ class NeRF(nn.Module):
 
     forward(x) takes the embedded batch [M, input_ch + input_ch_views] like the reference and runs the
     whole MLP in one HIP kernel. The render path does not go through forward(): run_network() hands
-    raw points to the fused encode+MLP kernel (nerfail_mlp_fwd) using packed()."""
+    raw points to the fused encode+MLP kernel. Every path goes through mlp_forward() below.
+
+    The kernels read device weight images, not the parameters: f32 (packed()), its bf16x3 splits x3 and x3f (packed_x3(),
+    packed_x3f()), the fp16 hi/lo image f16 (packed_f16()) and, for the backward-data pass, the transposed f32_T and f16_T
+    (_train.packed_T(), packed_f16_T()). All six live in ONE cache (_images.ImageCache, whose docstring has the rules): packed
+    when first asked for, dropped together when any parameter is written in place or moved."""
 
     def __init__(self, D=8, W=256, input_ch=3, input_ch_views=3, output_ch=4, skips=[4], use_viewdirs=False):
         super(NeRF, self).__init__()
@@ -105,124 +111,114 @@ class NeRF(nn.Module):
             self.rgb_linear = nn.Linear(W // 2, 3)
         else:
             self.output_linear = nn.Linear(W, output_ch)
-        self._packed = None
-        self._packed_key = None
-        self._packed16 = None
-        self._packed16_key = None
-        self._packed_x3 = None
-        self._packed_x3_key = None
-        self._packed_x3f = None
-        self._packed_x3f_key = None
+        self._images = ImageCache(self.ordered_params, {          # name: (packer, the image it is made from)
+            'f32': (self._pack_f32, None), 'f32_T': (self._pack_f32_T, None), 'x3': (self._pack_x3, 'f32'),
+            'x3f': (self._pack_x3f, 'f32'), 'f16': (self._pack_f16, None), 'f16_T': (self._pack_f16_T, None)})
+        self._f16_checked_once = False                            # state of check_f16x3_range: the first pack waits,
+        self._f16_pending = self._f16_host = None                 # later ones leave an event and a pinned float to look at
         # 'f32' : exact-f32 MFMA kernel (default).  'f16x3': split-precision fp16 MFMA kernel, fp32-equivalent
         # results (each product as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi with fp32 accumulation), inference only.
         self.precision = 'f32'
 
-    # -- MFMA-fragment-ordered weight image, rebuilt when any parameter changes (data_ptr, _version)
     def _skip(self):
         s = [i for i in self.skips if i < self.D - 1]
         if len(s) > 1:
             raise NotImplementedError('one skip connection supported (the reference always uses skips=[4])')
         return s[0] if s else -1
 
-    def packed(self):
+    def ordered_params(self):
+        """The parameters in the one order of the image key, nerfail_mlp_params and the gradients of the training step:
+        pts_linears (w, b) * D, views, feature, alpha, rgb."""
         if not self.use_viewdirs:
             raise NotImplementedError('HIP path implements use_viewdirs=True (all NeRFail configs, configs/*.txt)')
-        params = list(self.parameters())
-        if not params[0].is_cuda:
-            raise RuntimeError('NeRF parameters are on %s: call .cuda() - there is no CPU path' % params[0].device)
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        lib = _lib.load()
-        n = lib.nerfail_mlp_packed_floats(self.D, self.W, self._skip())
-        if n == 0:
-            raise NotImplementedError('unsupported NeRF shape D=%d W=%d (W in {64,128,256})' % (self.D, self.W))
+        ps = []
+        for l in list(self.pts_linears) + [self.views_linears[0], self.feature_linear, self.alpha_linear, self.rgb_linear]:
+            ps += [l.weight, l.bias]
+        return ps
+
+    def _mlp_params(self, keep):
+        return _lib.mlp_params(self.D, self.W, self.input_ch, self.input_ch_views, self._skip(), self.ordered_params(), keep)
+
+    # -- the packers of the image table: each allocates and fills, the cache decides when
+    def _pack(self, pack, *sizes):
+        """Fresh buffers of the sizes the named queries give, filled from the parameters by ONE launch of the named packer."""
+        lib, dev, shape = _lib.load(), self.pts_linears[0].weight.device, (self.D, self.W, self._skip())
+        if dev.type != 'cuda':
+            raise RuntimeError('NeRF parameters are on %s: call .cuda() - there is no CPU path' % dev)
+        bufs = []
+        for query in sizes:
+            n = getattr(lib, query)(*shape)
+            if n == 0:
+                raise NotImplementedError('unsupported NeRF shape D=%d W=%d (W in {64,128,256})' % (self.D, self.W))
+            bufs.append(torch.empty((n,), dtype=torch.float32 if query.endswith('_floats') else torch.uint8, device=dev))
         keep = []
         mp = self._mlp_params(keep)
-        buf = torch.empty((n,), dtype=torch.float32, device=params[0].device)
-        _lib.check(lib.nerfail_mlp_pack(mp, _lib.dev(buf), _lib.stream()))
-        self._packed, self._packed_key = buf, key
+        _lib.check(getattr(lib, pack)(mp, *[_lib.dev(b) for b in bufs], _lib.stream()))
+        return bufs
+
+    def _pack_f32(self):
+        return self._pack('nerfail_mlp_pack', 'nerfail_mlp_packed_floats')[0]
+
+    def _pack_f32_T(self):
+        return self._pack('nerfail_mlp_pack_T', 'nerfail_mlp_packed_T_floats')[0]
+
+    def _pack_both(self):
+        return self._pack('nerfail_mlp_pack_train', 'nerfail_mlp_packed_floats', 'nerfail_mlp_packed_T_floats')
+
+    def _pack_f16(self):
+        self.check_f16x3_range()
+        return self._pack('nerfail_mlp_pack_f16', 'nerfail_mlp_f16_image_bytes')[0]
+
+    def _pack_f16_T(self):
+        self.check_f16x3_range()
+        return self._pack('nerfail_mlp_pack_f16_T', 'nerfail_mlp_f16_image_T_bytes')[0]
+
+    def _pack_x3(self, f32, pack='nerfail_mlp_pack_x3', size='nerfail_mlp_packed_x3_bytes'):
+        lib, shape = _lib.load(), (self.D, self.W, self._skip())
+        n = getattr(lib, size)(*shape)
+        if n == 0:
+            return None                                           # a shape the bf16x3 kernel does not cover
+        buf = torch.empty((n,), dtype=torch.uint8, device=f32.device)
+        _lib.check(getattr(lib, pack)(_lib.dev(f32), *shape, _lib.dev(buf), _lib.stream()))
         return buf
+
+    def _pack_x3f(self, f32):
+        buf = self._pack_x3(f32, 'nerfail_mlp_pack_x3f', 'nerfail_mlp_packed_x3f_bytes')
+        if buf is not None:                                       # ONE host synchronisation per weight version
+            n = _lib.load().nerfail_mlp_x3f_composed_floats(self.D, self.W, self._skip())
+            if not bool(torch.isfinite(buf[buf.numel() - 4 * n:].view(torch.float32)).all()):
+                return None
+        return buf
+
+    # -- the images by name
+    def packed(self):
+        """f32 image in MFMA fragment order (nerfail_mlp_pack): what every kernel takes first."""
+        return self._images.get('f32')
+
+    def packed_both(self):
+        """(f32, f32_T) from ONE launch (nerfail_mlp_pack_train): the training step re-packs both after every optimizer step."""
+        return self._images.get_joint(('f32', 'f32_T'), self._pack_both)
 
     def packed_x3(self):
-        """bf16x3 weight image of the inference kernel (nerfail_mlp_pack_x3, split on the device from packed()), cached and
-        invalidated like packed(). None for shapes the bf16x3 kernel does not cover: the x3 entry points then run the f32 path."""
-        f32 = self.packed()
-        params = list(self.parameters())
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed_x3_key == key:
-            return self._packed_x3
-        lib = _lib.load()
-        n = lib.nerfail_mlp_packed_x3_bytes(self.D, self.W, self._skip())
-        buf = None
-        if n:
-            buf = torch.empty((n,), dtype=torch.uint8, device=f32.device)
-            _lib.check(lib.nerfail_mlp_pack_x3(_lib.dev(f32), self.D, self.W, self._skip(), _lib.dev(buf), _lib.stream()))
-        self._packed_x3, self._packed_x3_key = buf, key
-        return buf
+        """bf16x3 weight image of the inference kernel (nerfail_mlp_pack_x3, split on the device from packed()). None for
+        shapes the bf16x3 kernel does not cover: the x3 entry points then run the f32 path."""
+        return self._images.get('x3')
 
     def packed_x3f(self):
-        """Folded bf16x3 image (nerfail_mlp_pack_x3f): feature_linear composed into views_linears[0] on the device, once per
-        weight version - cached and invalidated like packed_x3(). None for shapes the kernel does not cover, and when the
-        composed block Wc / bc is not finite (weights so large that the product leaves f32): inference then takes the
-        unfolded image of packed_x3()."""
-        f32 = self.packed()
-        params = list(self.parameters())
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed_x3f_key == key:
-            return self._packed_x3f
-        lib = _lib.load()
-        n = lib.nerfail_mlp_packed_x3f_bytes(self.D, self.W, self._skip())
-        buf = None
-        if n:
-            buf = torch.empty((n,), dtype=torch.uint8, device=f32.device)
-            _lib.check(lib.nerfail_mlp_pack_x3f(_lib.dev(f32), self.D, self.W, self._skip(), _lib.dev(buf), _lib.stream()))
-            composed = buf[n - 4 * lib.nerfail_mlp_x3f_composed_floats(self.D, self.W, self._skip()):].view(torch.float32)
-            if not bool(torch.isfinite(composed).all()):
-                buf = None
-        self._packed_x3f, self._packed_x3f_key = buf, key
-        return buf
+        """Folded bf16x3 image (nerfail_mlp_pack_x3f): feature_linear composed into views_linears[0] on the device. None for
+        shapes the kernel does not cover, and when the composed block Wc / bc is not finite (weights so large that the
+        product leaves f32): inference then takes the unfolded image of packed_x3()."""
+        return self._images.get('x3f')
 
     def x3_image(self):
         """(folded, image) of the bf16x3 inference kernel: the folded image where it exists, else the unfolded one (or None)."""
         img = self.packed_x3f()
         return (True, img) if img is not None else (False, self.packed_x3())
 
-    def _mlp_params(self, keep):
-        mp = _lib.MlpParams()
-        mp.D, mp.W, mp.input_ch, mp.input_ch_views, mp.skip = self.D, self.W, self.input_ch, self.input_ch_views, self._skip()
-
-        def ptr(t):
-            t = _lib.f32c(t)
-            keep.append(t)
-            return t.data_ptr()
-        for i, l in enumerate(self.pts_linears):
-            mp.pts_w[i] = ptr(l.weight)
-            mp.pts_b[i] = ptr(l.bias)
-        mp.views_w, mp.views_b = ptr(self.views_linears[0].weight), ptr(self.views_linears[0].bias)
-        mp.feature_w, mp.feature_b = ptr(self.feature_linear.weight), ptr(self.feature_linear.bias)
-        mp.alpha_w, mp.alpha_b = ptr(self.alpha_linear.weight), ptr(self.alpha_linear.bias)
-        mp.rgb_w, mp.rgb_b = ptr(self.rgb_linear.weight), ptr(self.rgb_linear.bias)
-        return mp
-
     def packed_f16(self):
-        """fp16 hi/lo weight image of the split-precision kernel (nerfail_mlp_pack_f16), cached like packed()."""
-        params = list(self.parameters())
-        key = tuple((p.data_ptr(), p._version) for p in params)
+        """fp16 hi/lo weight image of the split-precision kernel (nerfail_mlp_pack_f16)."""
         self._f16_poll()                                  # an earlier pack's range check, if its value has arrived
-        if self._packed16 is not None and key == self._packed16_key:
-            return self._packed16
-        lib = _lib.load()
-        n = lib.nerfail_mlp_f16_image_bytes(self.D, self.W, self._skip())
-        if n == 0:
-            raise NotImplementedError('unsupported NeRF shape D=%d W=%d' % (self.D, self.W))
-        self.check_f16x3_range()
-        keep = []
-        mp = self._mlp_params(keep)
-        buf = torch.empty((n,), dtype=torch.uint8, device=params[0].device)
-        _lib.check(lib.nerfail_mlp_pack_f16(mp, _lib.dev(buf), _lib.stream()))
-        self._packed16, self._packed16_key = buf, key
-        return buf
+        return self._images.get('f16')
 
     F16X3_MAX_WEIGHT = 60.0       # the split-precision image holds fp16(w * 2^10): |w| * 1024 must stay below 65504
 
@@ -231,32 +227,30 @@ class NeRF(nn.Module):
         become inf (and its lo part NaN) - silently wrong results in a mode advertised as fp32-equivalent. EVERY pack
         measures max |weight| on the device (three small kernels). The first pack of a model waits for the value; later ones
         (training re-packs after every optimizer step) copy it to pinned host memory without stalling the stream and the
-        NEXT call that touches the split-precision image (`packed_f16`, the transposed image, this method) looks at it: a
-        weight that leaves the range is reported one forward later at the latest, whatever changed it (optimizer step,
-        load_state_dict, a manual edit). sync=True waits for the value of this call. Activations are bounded by the same
+        NEXT call that touches the split-precision image (`packed_f16`, a pack of the transposed image, this method) looks
+        at it: a weight that leaves the range is reported one forward later at the latest, whatever changed it (optimizer
+        step, load_state_dict, a manual edit). sync=True waits for the value of this call. Activations are bounded by the same
         mechanism only through the weights: NeRF activations are O(1..100), fp16 range is 65504."""
         self._f16_poll()
         ws = [p.detach() for n_, p in self.named_parameters() if n_.endswith('weight')]
         with torch.no_grad():
             m = torch.stack(torch._foreach_norm(ws, float('inf'))).max()
-        if sync or not m.is_cuda or not getattr(self, '_f16_checked_once', False):
+        if sync or not m.is_cuda or not self._f16_checked_once:
             self._f16_checked_once = True
             self._f16_verdict(float(m))
             return
         # a measurement still on its way is WAITED for before its slot is reused: no verdict is ever overwritten unread
         # (ADVICE r3: every pack is checked, one forward later at the latest - the training loop packs once per step)
         self._f16_poll(wait=True)
-        host = getattr(self, '_f16_host', None)
-        if host is None:
-            host = self._f16_host = torch.empty((1,), dtype=torch.float32).pin_memory()
-        host.copy_(m.reshape(1), non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._f16_pending = ev
+        if self._f16_host is None:
+            self._f16_host = torch.empty((1,), dtype=torch.float32).pin_memory()
+        self._f16_host.copy_(m.reshape(1), non_blocking=True)
+        self._f16_pending = torch.cuda.Event()
+        self._f16_pending.record()
 
     def _f16_poll(self, wait=False):
         """Looks at the max |weight| an earlier pack measured, if it has arrived (or waits for it)."""
-        ev = getattr(self, '_f16_pending', None)
+        ev = self._f16_pending
         if ev is None:
             return
         if wait:
@@ -274,13 +268,40 @@ class NeRF(nn.Module):
         x = _lib.f32c(x, _cuda())
         assert x.shape[-1] == self.input_ch + self.input_ch_views
         flat = x.reshape(-1, x.shape[-1])
-        out = torch.empty((flat.shape[0], 4), dtype=torch.float32, device=flat.device)
-        lib = _lib.load()
-        fold, img = self.x3_image()
-        fwd = lib.nerfail_mlp_fwd_embedded_x3f if fold else lib.nerfail_mlp_fwd_embedded_x3
-        _lib.check(fwd(_lib.dev(self.packed()), _lib.dev(img), self.D, self.W, self._skip(), _lib.dev(flat, 'x'), flat.shape[0],
-                       _lib.dev(out), _lib.stream()))
-        return out.reshape(x.shape[:-1] + (4,))
+        raw = torch.empty((flat.shape[0], 4), dtype=torch.float32, device=flat.device)
+        return mlp_forward(self, raw, embedded=flat).reshape(x.shape[:-1] + (4,))
+
+
+def mlp_forward(net, raw, pts=None, viewdirs=None, embedded=None, rays=None, z_vals=None, acts=None):
+    """The ONE choice of forward entry point. Input, one of: pts [R,N,3] + viewdirs [R,3] | embedded [M,90] | packed rays
+    [R,11] + z_vals [R,N] (the points o + d z are formed inside the kernel). Fills and returns `raw`. With `acts` (the
+    activation buffer of a training forward) the pass saves what the backward needs.
+
+      net.precision == 'f16x3', points only  nerfail_mlp_fwd_f16 / nerfail_mlp_fwd_f16_train on the f32 and the f16 image
+      inference                              nerfail_mlp_fwd[_embedded|_rays]_x3f on the folded bf16x3 image if there is one,
+                                             else ..._x3 on the unfolded one, which runs exact f32 when that is None too
+      training (points, rays)                nerfail_mlp_fwd_train / nerfail_mlp_fwd_rays on the f32 image, after the joint
+                                             pack: the backward needs the transposed image of the same weights"""
+    lib, train = _lib.load(), acts is not None
+    if embedded is not None:
+        form, inputs = '_embedded', [_lib.dev(embedded, 'x'), embedded.shape[0]]
+    elif rays is not None:
+        form, inputs = '_rays', [_lib.dev(rays, 'rays'), _lib.dev(z_vals, 'z_vals'), z_vals.shape[0], z_vals.shape[1]]
+    else:
+        form, inputs = '', [_lib.dev(pts, 'pts'), _lib.dev(viewdirs, 'viewdirs'), pts.shape[0] * pts.shape[1], pts.shape[1]]
+    if net.precision == 'f16x3' and form == '':
+        name, images = 'nerfail_mlp_fwd_f16' + ('_train' if train else ''), [net.packed(), net.packed_f16()]
+    elif train:
+        if form == '_embedded':
+            raise NotImplementedError('no training forward on an embedded batch')
+        name, images = 'nerfail_mlp_fwd' + (form or '_train'), [net.packed_both()[0]]
+    else:
+        fold, img = net.x3_image()
+        name, images = 'nerfail_mlp_fwd%s_x3%s' % (form, 'f' if fold else ''), [net.packed(), img]
+    tail = [_lib.dev(acts)] if train or form == '_rays' else []       # the rays entry points take acts (or NULL) always
+    _lib.check(getattr(lib, name)(*[_lib.dev(i) for i in images], net.D, net.W, net._skip(), *inputs, _lib.dev(raw), *tail,
+                                  _lib.stream()))
+    return raw
 
 
 # ----------------------------------------------------------------------------- rays

@@ -117,7 +117,8 @@ def test_python_api_images(shape, packed):
     """net.packed() & co. allocate their own (uninitialised) buffers: equal to the pinned images on every written byte."""
     from nerfail_amd import _train
     ref = packed[shape_id(shape)]
-    written = ref['f32'] == images(shape, fill=FILL ^ 0xFF)['f32']      # unwritten bytes keep the two patterns
+    other = images(shape, fill=FILL ^ 0xFF)['f32']
+    written = ref['f32'] == other                                       # unwritten bytes keep the two patterns
     assert 0 < int((~written).sum()) < written.numel() // 2
     net = make_net(shape)
     f32 = net.packed().view(torch.uint8)
@@ -129,6 +130,23 @@ def test_python_api_images(shape, packed):
     assert (x3 is None) == ('x3' not in ref)
     if x3 is not None:
         assert torch.equal(x3, ref['x3'])
+    # the folded image against nerfail_mlp_pack_x3f called directly. The packer writes every byte, but it copies the bias
+    # pieces and heads of the f32 image with their unwritten bytes: two direct packs, each from an f32 image and into a
+    # buffer of one pattern, tell which bytes the weights decide - all but some of that copied block
+    x3f = net.packed_x3f()
+    assert (x3f is None) == (shape != (8, 256, 4))
+    if x3f is not None:
+        from nerfail_amd import _lib
+        lib, a = _lib.load(), (net.D, net.W, net._skip())
+        n, composed = lib.nerfail_mlp_packed_x3f_bytes(*a), 4 * lib.nerfail_mlp_x3f_composed_floats(*a)
+        consts = 4 * ((net.D + 2) * net.W + 512 + 512)                  # bias pieces, alpha head, rgb head (mlp_layout.h)
+        direct = []
+        for fill, src in ((FILL, ref['f32']), (FILL ^ 0xFF, other)):
+            direct.append(torch.full((n,), fill, dtype=torch.uint8, device='cuda:0'))
+            _lib.check(lib.nerfail_mlp_pack_x3f(_lib.dev(src), *a, _lib.dev(direct[-1]), _lib.stream()))
+        decided = direct[0] == direct[1]
+        assert bool(decided[:n - composed - consts].all()) and bool(decided[n - composed:].all())
+        assert x3f.dtype == torch.uint8 and x3f.numel() == n and torch.equal(x3f[decided], direct[0][decided])
     # the one training launch on a fresh, identically initialised net: the same pair
     both, bothT = _train.packed_both(make_net(shape))
     assert torch.equal(both.view(torch.uint8)[written], f32[written])

@@ -109,10 +109,17 @@ def test_uncovered_shapes_are_refused(D, W, skip):
 
 
 @pytest.mark.parametrize('D,W,skips', [(8, 128, [4]), (4, 64, [2]), (5, 256, [2])])
-def test_no_image_for_uncovered_shapes_without_a_device(D, W, skips, monkeypatch):
-    """packed_x3f() of a shape without an image is None; the f32 image it starts from is stubbed, there is no GPU here."""
+def test_no_image_for_uncovered_shapes_without_a_device(D, W, skips):
+    """packed_x3f() of a shape without an image is None, asked for once; the f32 image it starts from is stubbed, there is
+    no GPU here."""
+    from nerfail_amd._images import ImageCache
     from nerfail_amd.run_nerf_helpers import NeRF
     net = NeRF(D=D, W=W, input_ch=63, input_ch_views=27, output_ch=5, skips=list(skips), use_viewdirs=True)
-    monkeypatch.setattr(net, 'packed', lambda: torch.zeros(1))
+    asked = []
+
+    def pack_x3f(f32):
+        asked.append(f32)
+        return net._pack_x3f(f32)
+    net._images = ImageCache(net.ordered_params, {'f32': (lambda: torch.zeros(1), None), 'x3f': (pack_x3f, 'f32')})
     assert net.packed_x3f() is None
-    assert net._packed_x3f_key is not None and net.packed_x3f() is None      # cached
+    assert net.packed_x3f() is None and len(asked) == 1                      # cached
