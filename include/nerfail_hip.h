@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 12
+#define NERFAIL_ABI_VERSION 13
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -64,6 +64,34 @@ int nerfail_pack_rays(const float* rays_o, const float* rays_d, int64_t n, float
  * (row-major pixel index = row*W + col): the per-rank unit when a view is sharded. */
 int nerfail_ray_gen(int H, int W, const float* K4_host, const float* c2w_host, float near_, float far_,
                     int64_t pix_begin, int64_t pix_count, float* rays, void* stream);
+
+/* ABI 13. The training batch (K1b): which rays a step trains on, and those rays, from resident data.
+ *
+ * nerfail_index_shuffle: out[j] = P(key, m)(first + j), j < n, where P(key, m) is a bijection of [0, m) evaluated per
+ * element - no memory, no sort: a balanced Feistel network (6 rounds, murmur3's 32-bit finaliser as round function) over
+ * the smallest even bit width covering m - 1, cycle-walked back into [0, m). The definition is the __host__ __device__
+ * function index_shuffle() of csrc/index_shuffle.h; tests/batch_ref.py restates it. Requires 1 <= m <= 2^31, first >= 0,
+ * n >= 0, first + n <= m. The first n values of a permutation are n distinct indices - what RN:768
+ * (np.random.choice(H*W, N_rand, replace=False)) draws; successive ranges of one permutation are the batches of an epoch -
+ * what RN:704 / RN:733-742 take from a shuffled copy of every training ray. Same distribution as the reference's draws,
+ * not the same bits. */
+int nerfail_index_shuffle(uint64_t key, int64_t m, int64_t first, int64_t n, int64_t* out, void* stream);
+
+/* Packed rays and target colours of one training batch, RN:733-735 (use_batching) and RN:746-773 (one image, optional
+ * precrop window RN:754-761), from resident data: poses[n_img,12] (row-major [3,4] c2w per image), images[n_img,H,W,3]
+ * (NULL: no targets are written). The population is n_views view slots times the window (row0, col0, wh, ww) of the image:
+ * index q in [0, m), m = n_views*wh*ww, is slot q / (wh*ww), row row0 + (q % (wh*ww)) / ww, column col0 + q % ww.
+ * Slot s shows image view_ids[s] (int32 [n_views]), or view0 + s when view_ids is NULL.
+ * The batch is sel[n] (int64 population indices), or, when sel is NULL, q_j = P(key, m)(first + j) computed in the kernel.
+ * Writes rays[n,11] - row j bit for bit the row nerfail_ray_gen writes for that pixel and pose -, target[n,3] (copies of the
+ * pixels; untouched when images is NULL) and, unless NULL, sel_out[n] = q_j.
+ * Validated: the window lies inside the image, 1 <= m <= 2^31, 0 <= first, n <= m - first (both modes), view0 .. view0 +
+ * n_views inside [0, n_img) when view_ids is NULL, NULL pointers. The VALUES of view_ids (< n_img) and sel (< m) are the
+ * caller's contract, as index maps are elsewhere in this ABI. */
+int nerfail_train_batch(int H, int W, const float* K4_host, float near_, float far_, const float* poses, int n_img,
+                        const float* images, int row0, int col0, int wh, int ww, const int32_t* view_ids, int view0,
+                        int n_views, const int64_t* sel, uint64_t key, int64_t first, int64_t n, float* rays,
+                        float* target, int64_t* sel_out, void* stream);
 
 /* ------------------------------------------------------------------ sampling (K2, K6) ----- */
 

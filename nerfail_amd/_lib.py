@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must be imported first: libnerfail_hip.so binds to 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFAIL_HIP_LIB') or os.path.join(_HERE, 'lib', 'libnerfail_hip.so')   # override: A/B builds (tools/ablate.py)
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_DEPTH = 16
 DW_BF16X3, DW_ACCUMULATE = 1, 2          # flags of nerfail_mlp_bwd_weights
 RAY_FLOATS = 11
@@ -19,6 +19,7 @@ RAY_FLOATS = 11
 c_f = ctypes.c_float
 c_i = ctypes.c_int
 c_i64 = ctypes.c_int64
+c_u64 = ctypes.c_uint64
 c_p = ctypes.c_void_p
 
 
@@ -63,6 +64,9 @@ SIGNATURES = {
     'nerfail_get_rays': (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     'nerfail_pack_rays': (c_i, [c_p, c_p, c_i64, c_f, c_f, c_p, c_p]),
     'nerfail_ray_gen': (c_i, [c_i, c_i, c_p, c_p, c_f, c_f, c_i64, c_i64, c_p, c_p]),
+    'nerfail_index_shuffle': (c_i, [c_u64, c_i64, c_i64, c_i64, c_p, c_p]),
+    'nerfail_train_batch': (c_i, [c_i, c_i, c_p, c_f, c_f, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_u64, c_i64, c_i64,
+                                  c_p, c_p, c_p, c_p]),
     'nerfail_sample_coarse': (c_i, [c_p, c_i64, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     'nerfail_sample_pdf': (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i, c_i, c_p, c_p]),
     'nerfail_sample_fine': (c_i, [c_p, c_i64, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),

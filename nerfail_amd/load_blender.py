@@ -108,7 +108,8 @@ def train_step(images, poses, i_train, hwf, K, render_kwargs_train, optimizer, g
                lrate_decay=250, chunk=1024 * 32, precrop_iters=0, precrop_frac=.5, near=2., far=6., rng=np.random):
     """One iteration of the no_batching loop RN:746-801: random train image, get_rays on the full image (RN:752), N_rand
     random pixels (RN:768), render with gradients, loss = mse(rgb) + mse(rgb0), backward, Adam step, lr decay.
-    Returns (loss, psnr, new_lrate)."""
+    Returns (loss, psnr, new_lrate). The literal step, host draws and a host wait included; the loop to train with is
+    nerfail_amd.train.train (device-side batches, no wait between log points)."""
     from . import run_nerf as RN
     from .run_nerf_helpers import get_rays, img2mse, mse2psnr
     H, W, focal = hwf

@@ -11,6 +11,8 @@ Each op is a `torch.library.custom_op` over ONE entry point of libnerfail_hip.so
 create_gauss_w, igsm_step, knn8, get_rays ...) call these ops. SURVEY's `render_rays_fused_fwd/bwd` is their composition:
 `_train.RenderRaysTrain` (a torch.autograd.Function over ray sampling, mlp_fwd_train, composite, sample_fine and, backwards,
 composite_bwd and mlp_bwd), selected by render_rays whenever a NeRF parameter requires grad."""
+from typing import Optional, Sequence
+
 import torch
 from torch import Tensor
 from torch.library import custom_op
@@ -44,6 +46,72 @@ def ray_gen(K: Tensor, c2w: Tensor, anchor: Tensor, H: int, W: int, near: float,
 @ray_gen.register_fake
 def _(K, c2w, anchor, H, W, near, far, pix_begin, pix_count):
     return anchor.new_empty((pix_count, _lib.RAY_FLOATS), dtype=torch.float32)
+
+
+# ----------------------------------------------------------------------------------------------- K1b training batch (RN:690-773)
+def _u64(key):
+    """The dispatcher's int is a signed 64-bit value: keys are taken modulo 2^64 (pass the two's complement of one >= 2^63)."""
+    return int(key) & 0xFFFFFFFFFFFFFFFF
+
+
+def as_op_key(key):
+    """A 64-bit key as the signed int the ops accept."""
+    key = _u64(key)
+    return key - (1 << 64) if key >= (1 << 63) else key
+
+
+@custom_op(NS + '::index_shuffle', mutates_args=(), device_types='cuda')
+def index_shuffle(anchor: Tensor, key: int, m: int, first: int, n: int) -> Tensor:
+    """int64 [n]: P(key, m)(first + j), the range [first, first + n) of the keyed permutation of [0, m) (nerfail_index_shuffle).
+    `anchor` is any tensor on the target device. Not differentiable: indices are data."""
+    out = torch.empty((n,), dtype=torch.int64, device=anchor.device)
+    _chk(_lib.load().nerfail_index_shuffle(_u64(key), m, first, n, _lib.dev(out), _s()))
+    return out
+
+
+@index_shuffle.register_fake
+def _(anchor, key, m, first, n):
+    return anchor.new_empty((n,), dtype=torch.int64)
+
+
+@custom_op(NS + '::train_batch', mutates_args=(), device_types='cuda')
+def train_batch(poses: Tensor, images: Optional[Tensor], view_ids: Optional[Tensor], sel: Optional[Tensor], H: int, W: int,
+                K4: Sequence[float], near: float, far: float, window: Sequence[int], view0: int, n_views: int, key: int, first: int,
+                n: int, want_sel: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """(rays [n,11], target [n,3], sel_out [n] int64) of one training batch from resident poses [n_img,12] and images
+    [n_img,H,W,3] (nerfail_train_batch). K4 = (fx, fy, cx, cy), window = (row0, col0, wh, ww). The batch is `sel` (int64
+    population indices) or, with sel None, positions [first, first + n) of the permutation `key` of the population
+    n_views * wh * ww. images None: target is empty; want_sel False: sel_out is empty. Not differentiable: rays and targets
+    are data."""
+    dev = poses.device
+    if poses.dtype != torch.float32 or poses.dim() != 2 or poses.shape[1] != 12:
+        raise ValueError('train_batch: poses must be float32 [n_img, 12] (got %s %s)' % (poses.dtype, tuple(poses.shape)))
+    n_img = poses.shape[0]
+    if images is not None and (images.dtype != torch.float32 or tuple(images.shape) != (n_img, H, W, 3)):
+        raise ValueError('train_batch: images must be float32 [%d, %d, %d, 3] (got %s %s)' % (n_img, H, W, images.dtype, tuple(images.shape)))
+    if view_ids is not None and (view_ids.dtype != torch.int32 or tuple(view_ids.shape) != (n_views,)):
+        raise ValueError('train_batch: view_ids must be int32 [n_views]')
+    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (n,)):
+        raise ValueError('train_batch: sel must be int64 [n]')
+    if len(K4) != 4 or len(window) != 4:
+        raise ValueError('train_batch: K4 = (fx, fy, cx, cy) and window = (row0, col0, wh, ww)')
+    rays = torch.empty((n, _lib.RAY_FLOATS), dtype=torch.float32, device=dev)
+    target = torch.empty((n if images is not None else 0, 3), dtype=torch.float32, device=dev)
+    sel_out = torch.empty((n if want_sel else 0,), dtype=torch.int64, device=dev)
+    _chk(_lib.load().nerfail_train_batch(H, W, _lib.host_floats(K4), near, far, _lib.dev(poses, 'poses'), n_img, _lib.dev(images, 'images'),
+                                         window[0], window[1], window[2], window[3], _lib.dev(view_ids, 'view_ids'), view0, n_views,
+                                         _lib.dev(sel, 'sel'), _u64(key), first, n, _lib.dev(rays),
+                                         _lib.dev(target) if images is not None else None, _lib.dev(sel_out) if want_sel else None, _s()))
+    return rays, target, sel_out
+
+
+@train_batch.register_fake
+def _(poses, images, view_ids, sel, H, W, K4, near, far, window, view0, n_views, key, first, n, want_sel):
+    return (poses.new_empty((n, _lib.RAY_FLOATS)), poses.new_empty((n if images is not None else 0, 3)),
+            poses.new_empty((n if want_sel else 0,), dtype=torch.int64))
+
+
+BATCH_OPS = ('index_shuffle', 'train_batch')
 
 
 # ----------------------------------------------------------------------------------------------- K5 + K7 composite (RN:262-305)
