@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NERFAIL_ABI_VERSION 13
+#define NERFAIL_ABI_VERSION 14
 
 #define NERFAIL_OK 0
 #define NERFAIL_EINVAL 1   /* bad argument (null pointer, size, unsupported shape) */
@@ -503,6 +503,12 @@ int nerfail_adam_step(const nerfail_adam_tensor* tensors, int n_tensors, double 
 /* img2mse of the training loss (RH:9, RN:781-789): loss[0] = mean((x - y)^2) over n values by a fixed-order tree, and - when
  * dx is not NULL - dx[i] = 2 (x[i] - y[i]) / n, the gradient of that mean (one launch instead of ~9 torch kernels). */
 int nerfail_mse(const float* x, const float* y, int64_t n, float* loss, float* dx, void* stream);
+
+/* One rank's share of that loss in a data-parallel step (ABI 14): x and y hold n of the n_total >= n values of the global
+ * batch; loss[0] = sum((x - y)^2) * (1 / n_total) and dx[i] = 2 (x[i] - y[i]) * (1 / n_total). The shares of all ranks add up
+ * to the global mean, the parameter gradients they drive to its gradient. nerfail_mse is the n_total = n case of the same
+ * kernel (same fixed-order tree: bit for bit the ABI 13 result). */
+int nerfail_mse_part(const float* x, const float* y, int64_t n, int64_t n_total, float* loss, float* dx, void* stream);
 
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 

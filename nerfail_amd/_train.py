@@ -140,6 +140,109 @@ def _zero_grads(net):
     return _new_grads(net, True)
 
 
+def arena_layout(shapes_per_net):
+    """Layout of the gradient arena from parameter shapes alone: ([[offset of every parameter] per network], P). The
+    parameters of the networks follow each other in ordered_params order, densely; P = their total numel is the index of
+    the two tail floats (loss, mse)."""
+    offsets, off = [], 0
+    for shapes in shapes_per_net:
+        offs = []
+        for shape in shapes:
+            n = 1
+            for d in shape:
+                n *= int(d)
+            offs.append(off)
+            off += n
+        offsets.append(offs)
+    return offsets, off
+
+
+class GradArena:
+    """The one gradient buffer of a data-parallel training run: float32 [coarse params | fine params | loss, mse].
+    RenderRaysTrain.backward writes the parameter gradients straight into it (through fresh per-parameter views, which
+    autograd adopts as p.grad), the step's loss and fine image loss go into the tail, ONE all-reduce sums all of it over the
+    ranks, and optimizer.step() reads the p.grad that still alias it: no gather before the collective, no scatter after."""
+
+    def __init__(self, nets, device=None):
+        self.nets = [n for n in nets if n is not None]
+        self.shapes = [[tuple(p.shape) for p in ordered_params(n)] for n in self.nets]
+        self.offsets, self.P = arena_layout(self.shapes)
+        if device is None:
+            device = ordered_params(self.nets[0])[0].device
+        self.buf = torch.zeros((self.P + 2,), dtype=torch.float32, device=device)
+        self.ends = [offs[0] for offs in self.offsets[1:]] + [self.P]
+
+    @property
+    def nbytes(self):
+        return self.buf.numel() * self.buf.element_size()
+
+    def _index(self, net):
+        for k, n in enumerate(self.nets):
+            if n is net:
+                return k
+        raise ValueError('GradArena: the network is not one of the arena\'s')
+
+    def views(self, net, zero=False):
+        """Fresh views of `net`'s range, one per parameter in ordered_params order (`zero`: one memset of the range first)."""
+        k = self._index(net)
+        if zero:
+            self.buf[self.offsets[k][0]:self.ends[k]].zero_()
+        out = []
+        for off, shape in zip(self.offsets[k], self.shapes[k]):
+            n = 1
+            for d in shape:
+                n *= d
+            out.append(self.buf[off:off + n].view(shape))
+        return out
+
+    def zero_(self):
+        self.buf.zero_()
+
+    def holds(self, t):
+        """Does tensor `t` lie inside the arena's memory?"""
+        lo = self.buf.data_ptr()
+        return t is not None and lo <= t.data_ptr() and t.data_ptr() + t.numel() * t.element_size() <= lo + 4 * self.P
+
+    def adopt(self):
+        """Make every p.grad alias the arena: gradients autograd placed elsewhere (a step of several render chunks, whose
+        backward passes it accumulates out of place) are copied in; a parameter without a gradient (an idle rank, which ran
+        no backward) gets the view as it is. After a single-chunk backward this finds nothing to do."""
+        with torch.no_grad():
+            for net in self.nets:
+                views = None
+                for i, p in enumerate(ordered_params(net)):
+                    if self.holds(p.grad):
+                        continue
+                    views = self.views(net) if views is None else views
+                    if p.grad is not None:
+                        views[i].copy_(p.grad)
+                    p.grad = views[i]
+
+    def put_tail(self, loss, mse):
+        torch.stack((loss.detach(), mse.detach()), out=self.buf[self.P:])
+
+    @property
+    def loss(self):
+        return self.buf[self.P]
+
+    @property
+    def mse(self):
+        return self.buf[self.P + 1]
+
+    def reduce_(self, group=None, timing=None):
+        """THE collective of a step: one all-reduce (sum) of the whole arena, P + 2 floats. `timing`: a dict that gets HIP
+        events around it ('allreduce_events': (start, end, bytes)), as attack.sharded_perturbation_grad_rgb records them."""
+        from . import sharding
+        if timing is not None and self.buf.is_cuda:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        sharding.all_reduce_sum_(self.buf, group)
+        if timing is not None and self.buf.is_cuda:
+            e1.record()
+            timing.setdefault('allreduce_events', []).append((e0, e1, self.nbytes))
+        return self.buf
+
+
 class RenderRaysTrain(torch.autograd.Function):
     """forward(rays, cfg, *params) -> (rgb_map, disp_map, acc_map, rgb0, disp0, acc0, z_std, pts_max, raw)."""
 
@@ -157,6 +260,10 @@ class RenderRaysTrain(torch.autograd.Function):
     def backward(ctx, g_rgb, g_disp, g_acc, g_rgb0, g_disp0, g_acc0, g_zstd, g_ptsmax, g_raw):
         cfg, sv = ctx.cfg, ctx.saved
         coarse, fine = cfg['network_fn'], cfg['network_fine']
+        arena = cfg.get('grad_arena')
+
+        def _grads(net, zero):                     # where this pass writes d loss / d params of `net`
+            return _new_grads(net, zero) if arena is None else arena.views(net, zero)
         nets = [coarse] + ([fine] if fine is not None else [])
         wb = cfg['white_bkgd']
         c, f = sv['coarse'], sv['fine']
@@ -165,7 +272,7 @@ class RenderRaysTrain(torch.autograd.Function):
             d_raw = composite_backward(c['raw'], c['z'], sv['rays'], c['noise'], wb, g_rgb, g_disp, g_acc)
             if g_raw is not None and cfg['retraw']:
                 d_raw = d_raw + g_raw
-            grads = {id(coarse): _new_grads(coarse, False)}
+            grads = {id(coarse): _grads(coarse, False)}
             mlp_backward2(coarse, d_raw.reshape(-1, 4), c['acts'], grads[id(coarse)], Mc, None, None, 0)
         else:
             run = fine if fine is not None else coarse
@@ -176,7 +283,7 @@ class RenderRaysTrain(torch.autograd.Function):
             composite_backward(f['raw'], f['z'], sv['rays'], f['noise'], wb, g_rgb, g_disp, g_acc, out=d_all[Mc:])
             if g_raw is not None and cfg['retraw']:
                 d_all[Mc:] += g_raw.reshape(-1, 4)
-            grads = {id(n): _new_grads(n, not joint) for n in nets}
+            grads = {id(n): _grads(n, not joint) for n in nets}
             if joint and run is coarse:            # one network evaluated twice (network_fine=None): one run of Mc + Mf samples
                 mlp_backward2(coarse, d_all, sv['acts_all'], grads[id(coarse)], Mc + Mf, None, None, 0)
             elif joint:                            # coarse + fine in ONE launch each (independent: RN:394 detaches z_samples)

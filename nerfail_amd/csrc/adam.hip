@@ -64,11 +64,14 @@ extern "C" int nerfail_adam_step(const nerfail_adam_tensor* tensors, int n_tenso
 // boundary on a 1024-ray batch: two calls per training step were 1 % of the step. One launch: the mean by a fixed-order
 // tree (one workgroup: the batch is 3072 values; bitwise reproducible), and d mean / d x = 2 (x - y) / n written alongside
 // so that the backward is a single multiply by the upstream scalar.
+// The denominator is n_total, not n (ABI 14): a rank that holds n of the n_total values of a data-parallel batch gets its
+// SHARE of the global mean and of its gradient, so that the sum over ranks of the losses is the mean and the sum of the
+// parameter gradients its gradient. n_total = n is the one-rank loss, by this same kernel: same tree, same bits.
 namespace nerfail {
-__global__ __launch_bounds__(1024) void mse_kernel(const float* __restrict__ x, const float* __restrict__ y, long n,
+__global__ __launch_bounds__(1024) void mse_kernel(const float* __restrict__ x, const float* __restrict__ y, long n, long n_total,
                                                    float* __restrict__ loss, float* __restrict__ dx) {
     __shared__ float part[16];
-    const float inv_n = 1.0f / (float)n;
+    const float inv_n = 1.0f / (float)n_total;
     float s = 0.f;
     for (long i = threadIdx.x; i < n; i += 1024) {
         const float d = x[i] - y[i];
@@ -86,10 +89,15 @@ __global__ __launch_bounds__(1024) void mse_kernel(const float* __restrict__ x, 
 }
 }  // namespace nerfail
 
-extern "C" int nerfail_mse(const float* x, const float* y, int64_t n, float* loss, float* dx, void* stream) {
+extern "C" int nerfail_mse_part(const float* x, const float* y, int64_t n, int64_t n_total, float* loss, float* dx, void* stream) {
     NF_REQUIRE(n > 0, "n must be positive");
+    NF_REQUIRE(n_total >= n, "n_total must be at least n");
     NF_REQUIRE(x && y && loss, "NULL pointer");
-    nerfail::mse_kernel<<<dim3(1), dim3(1024), 0, as_stream(stream)>>>(x, y, (long)n, loss, dx);
+    nerfail::mse_kernel<<<dim3(1), dim3(1024), 0, as_stream(stream)>>>(x, y, (long)n, (long)n_total, loss, dx);
     NF_LAUNCHED("mse_kernel");
     return NERFAIL_OK;
+}
+
+extern "C" int nerfail_mse(const float* x, const float* y, int64_t n, float* loss, float* dx, void* stream) {
+    return nerfail_mse_part(x, y, n, n, loss, dx, stream);
 }

@@ -260,12 +260,14 @@ def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=F
 # ----------------------------------------------------------------------------- the per-chunk pipeline
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                want_pts_max=False, t_rand=None, u=None, noise=None, noise_fine=None):
+                want_pts_max=False, t_rand=None, u=None, noise=None, noise_fine=None, grad_arena=None):
     """RN:308-418 (and NC:320-436 when want_pts_max): coarse samples -> MLP -> composite ->
     importance samples (sorted merge) -> fine MLP -> composite (+ argmax-weight point).
 
     Extra keyword-only inputs beyond the reference: t_rand [R,N_samples], u [R,N_importance],
-    noise / noise_fine [R,N] (already scaled) supply the random draws explicitly.
+    noise / noise_fine [R,N] (already scaled) supply the random draws explicitly. grad_arena: a _train.GradArena over
+    (network_fn, network_fine) that receives the parameter gradients of this call's backward (ONE call per backward: a
+    second call's backward would overwrite the first's); None: fresh buffers.
     """
     dev = _cuda()
     rays = _lib.f32c(ray_batch, dev)
@@ -305,7 +307,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         nets = [network_fn] + ([network_fine] if network_fine is not None else [])
         params = [p for n in nets for p in _train.ordered_params(n)]
         cfg = dict(pipeline=pipeline, network_fn=network_fn, network_fine=network_fine, white_bkgd=white_bkgd,
-                   retraw=retraw)
+                   retraw=retraw, grad_arena=grad_arena)
         o = _train.RenderRaysTrain.apply(rays, cfg, *params)
         out = dict(zip(('rgb_map', 'disp_map', 'acc_map', 'rgb0', 'disp0', 'acc0', 'z_std', 'pts_max', 'raw'), o))
     else:

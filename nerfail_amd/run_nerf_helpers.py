@@ -12,20 +12,23 @@ from ._images import ImageCache
 
 # Misc (RH:9-11) - host-side one-liners, kept for drop-in completeness
 class _Img2Mse(torch.autograd.Function):
-    """mean((x - y)^2) and its gradient w.r.t. x from ONE launch (nerfail_mse); the backward is one multiply."""
+    """sum((x - y)^2) / n_total and its gradient w.r.t. x from ONE launch (nerfail_mse_part; n_total None = x.numel(): the
+    mean, nerfail_mse's bits); the backward is one multiply."""
 
     @staticmethod
-    def forward(ctx, x, y):
+    def forward(ctx, x, y, n_total=None):
         xc, yc = _lib.f32c(x), _lib.f32c(y)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(xc) if x.requires_grad else None
-        _lib.check(_lib.load().nerfail_mse(_lib.dev(xc), _lib.dev(yc), xc.numel(), _lib.dev(loss), _lib.dev(dx), _lib.stream()))
+        n = xc.numel()
+        _lib.check(_lib.load().nerfail_mse_part(_lib.dev(xc), _lib.dev(yc), n, n if n_total is None else int(n_total), _lib.dev(loss),
+                                                _lib.dev(dx), _lib.stream()))
         ctx.dx = dx
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return (None if ctx.dx is None else ctx.dx * g), None
+        return (None if ctx.dx is None else ctx.dx * g), None, None
 
 
 # the fused kernel is ONE workgroup (fixed-order tree, bitwise reproducible): right for a training batch (1024 rays x 3 = 3072
@@ -33,12 +36,18 @@ class _Img2Mse(torch.autograd.Function):
 MSE_FUSED_MAX = 1 << 16
 
 
-def img2mse(x, y):
+def img2mse(x, y, n_total=None):
     """RH:9. On the MI355X (float32 HIP tensors of equal shape, target without gradient) one fused kernel; any other
-    input takes the reference's expression."""
+    input takes the reference's expression.
+    n_total (data-parallel training): x and y are this rank's share of a batch of n_total >= x.numel() VALUES; the result is
+    sum((x - y)^2) / n_total, so that the ranks' losses add up to the global mean and their gradients to its gradient."""
+    if n_total is not None and int(n_total) < x.numel():
+        raise ValueError('img2mse: n_total = %d is smaller than the %d values given' % (int(n_total), x.numel()))
     if (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.is_cuda and y.is_cuda and x.dtype == torch.float32
             and y.dtype == torch.float32 and x.shape == y.shape and not y.requires_grad and 0 < x.numel() <= MSE_FUSED_MAX):
-        return _Img2Mse.apply(x, y)
+        return _Img2Mse.apply(x, y, n_total)
+    if n_total is not None:
+        return torch.sum((x - y) ** 2) / float(int(n_total))
     return torch.mean((x - y) ** 2)
 
 

@@ -2,7 +2,8 @@
 
 Rays are independent units: a view's pixel range is cut into contiguous per-rank ranges and rendered
 with NO data-path collective (each rank writes / keeps its own slice). The attack step has one real
-exchange: the sum of the per-shard perturbation gradients (attack.nerfail_s_step).
+exchange: the sum of the per-shard perturbation gradients (attack.nerfail_s_step). Training splits the rays of each
+step and sums one flat buffer of parameter gradients per step (train.train, _train.GradArena).
 The range arithmetic is pure host logic: importable and testable without a GPU.
 """
 import torch
@@ -39,29 +40,66 @@ def force_collectives():
     return os.environ.get('NERFAIL_FORCE_COLLECTIVE', '0') == '1'
 
 
-def all_reduce_sum_(t, group=None):
-    """In-place sum over ranks. RCCL all-reduce for HIP tensors whenever the group has a device-capable backend ('nccl', a
-    'cpu:gloo,cuda:nccl' pair, or the default-initialised group that maps to it): the GPU-box path, xGMI. Only under a pure
-    'gloo' group (the CPU tests and the one-GPU rehearsal, where RCCL refuses two ranks on one device) a HIP tensor is
+def _stage(t):
+    """The pinned host buffer of t's size and dtype (kept per size, least recently used size dropped)."""
+    key = (t.numel(), t.dtype)
+    h = _STAGE.pop(key, None)
+    if h is None:
+        h = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
+        while len(_STAGE) >= STAGE_SLOTS:                 # bounded: the least recently used size goes (ADVICE r3)
+            _STAGE.pop(next(iter(_STAGE)))
+    _STAGE[key] = h                                       # most recently used last
+    return h
+
+
+def _staged(t, group):
+    """A HIP tensor under a pure 'gloo' group: the collective runs on a pinned host copy."""
+    return t.is_cuda and str(dist.get_backend(group)) == 'gloo'
+
+
+def all_reduce_(t, op, group=None):
+    """In-place all-reduce with `op` over ranks. RCCL all-reduce for HIP tensors whenever the group has a device-capable backend
+    ('nccl', a 'cpu:gloo,cuda:nccl' pair, or the default-initialised group that maps to it): the GPU-box path, xGMI. Only under
+    a pure 'gloo' group (the CPU tests and the one-GPU rehearsal, where RCCL refuses two ranks on one device) a HIP tensor is
     staged through a pinned host buffer (kept per size), reduced there and copied back."""
     if not (dist.is_available() and dist.is_initialized()):
         return t
     world = dist.get_world_size(group)
     if world <= 1 and not force_collectives():
         return t
-    if t.is_cuda and str(dist.get_backend(group)) == 'gloo':
-        key = (t.numel(), t.dtype)
-        h = _STAGE.pop(key, None)
-        if h is None:
-            h = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
-            while len(_STAGE) >= STAGE_SLOTS:                 # bounded: the least recently used size goes (ADVICE r3)
-                _STAGE.pop(next(iter(_STAGE)))
-        _STAGE[key] = h                                       # most recently used last
+    if _staged(t, group):
+        h = _stage(t)
         h.copy_(t.reshape(-1), non_blocking=False)
-        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(h, op=op, group=group)
         t.copy_(h.reshape(t.shape))
         return t
-    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(t, op=op, group=group)
+    return t
+
+
+def all_reduce_sum_(t, group=None):
+    """In-place sum over ranks (all_reduce_ with SUM)."""
+    return all_reduce_(t, dist.ReduceOp.SUM, group) if dist.is_available() else t
+
+
+def broadcast_(t, src=0, group=None):
+    """In-place broadcast of group rank `src`'s tensor to every rank, on the same two paths as all_reduce_: RCCL on the
+    device, or - HIP tensor under pure gloo - through the pinned host buffer. `t` must be contiguous."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return t
+    world = dist.get_world_size(group)
+    if world <= 1 and not force_collectives():
+        return t
+    gsrc = dist.get_global_rank(group, src) if group is not None else src
+    if _staged(t, group):
+        h = _stage(t)
+        if dist.get_rank(group) == src:
+            h.copy_(t.reshape(-1), non_blocking=False)
+        dist.broadcast(h, src=gsrc, group=group)
+        if dist.get_rank(group) != src:
+            t.copy_(h.reshape(t.shape))
+        return t
+    dist.broadcast(t, src=gsrc, group=group)
     return t
 
 
