@@ -510,6 +510,65 @@ int nerfail_mse(const float* x, const float* y, int64_t n, float* loss, float* d
  * kernel (same fixed-order tree: bit for bit the ABI 13 result). */
 int nerfail_mse_part(const float* x, const float* y, int64_t n, int64_t n_total, float* loss, float* dx, void* stream);
 
+/* ------------------------------------------------------------------ NeRFail-S epoch statistics (ABI 15) -- */
+
+/* ABI 15 only ADDS the entry points of this section; no existing entry point, struct or default changes, so NERFAIL_ABI_VERSION
+ * (the compatibility word callers compare) stays 14 and the additions are announced by nerfail_abi_revision() = 15.
+ *
+ * The per-epoch bookkeeping of the NeRFail-S loop (AS:319-344, 405-431) on the device, so that the loop never waits for the
+ * GPU between epoch ends. Everything accumulates into one STATS ROW of NERFAIL_ATTACK_ROW_FLOATS float32 that the caller
+ * zeroes at the start of an epoch. Sums are kept as (hi, lo) float32 pairs whose exact sum is the double-precision running
+ * value (counts of views are plain float32, exact up to 2^24 views). A row can travel through a float32 all-reduce, which adds
+ * his and los separately: the sum over ranks is then good to one float32 rounding of the his (~6e-8 relative), no longer exact:
+ *   [0,1] sum of per-view CE(ori_cla)      [2,3] sum of per-view CE(cla)        [4] views with argmax(ori_cla) == label
+ *   [5] views with argmax(cla) == label    [6] views                            [7,8] sum (x_rgba - ori)^2
+ *   [9,10] number of elements in that sum  [11..15] unused, left alone
+ * One lane adds into the row per launch (plain loads and stores, no atomics): launches on one stream are ordered. */
+#define NERFAIL_ATTACK_ROW_FLOATS 16
+#define NERFAIL_ATTACK_MAX_CLASSES 32
+int nerfail_abi_revision(void);
+
+/* AS:319-330, 339, 344. cla, ori_cla: [B,C] logits, 1 <= C <= 32, 0 <= label < C. Per view: CE = log-sum-exp with the maximum
+ * subtracted, minus the label's logit (evaluated in double from the float32 logits); argmax = the FIRST maximum; a row that
+ * holds a NaN never counts as correct (its CE is NaN and makes the epoch's mean NaN, as in the reference). Adds, in this
+ * order: sum CE(ori_cla), sum CE(cla), correct(ori_cla), correct(cla), B. The views are summed in a fixed order. */
+int nerfail_attack_logit_stats(const float* cla, const float* ori_cla, int B, int C, int label, float* row, void* stream);
+
+/* AS:329, 341: sum over [n_views,P,4] of (x_rgba - ori)^2 into row[7,8], and the element count 4 P n_views into row[9,10].
+ * x_rgba is dense [n_views,P,4]; ori_views_host is a HOST array of n_views device pointers, each to one view's [P,4] image,
+ * float32 or (ori_is_u8) uint8 - resident views keep uint8. Differences and squares are formed in double; each lane sums
+ * its pixels (consecutive lanes take consecutive pixels), each workgroup its lanes, one workgroup the per-workgroup partials, all in a fixed order: no float atomics, the
+ * same bits on every run, and the same bits for a float32 and a uint8 image holding the same values. scratch:
+ * nerfail_img_sqerr_scratch_bytes() bytes (the partials), contents unspecified on return. */
+size_t nerfail_img_sqerr_scratch_bytes(void);
+int nerfail_img_sqerr(const float* x_rgba, const void* const* ori_views_host, int n_views, int64_t P, int ori_is_u8,
+                      void* scratch, float* row, void* stream);
+
+/* The beta term of AS:336 carried into d loss / d x_rgba: g[v,p,c] += scale * (x_rgba[v,p,c] - ori[v][p,c]) (float32: one
+ * subtraction, one product, one sum per element). For beta * mean((x_rgba - ori)^2) over a batch of B views the caller
+ * passes scale = 2 beta / (4 P B). g is dense [n_views,P,4] like x_rgba. */
+int nerfail_img_sqerr_grad_add(const float* x_rgba, const void* const* ori_views_host, int n_views, int64_t P, int ori_is_u8,
+                               float scale, float* g, void* stream);
+
+/* AS:405-431 on one workgroup. From the row: test loss = row[0,1] / views, attack loss = row[2,3] / views, the accuracies
+ * row[4] / views and row[5] / views, image loss = row[7,8] / row[9,10] (= AS:411's value: every view has the same 4 P
+ * elements). best: float32 [4] = {best attack accuracy, its attack loss, its epoch, unused}; the caller initialises it to
+ * {10000, 0, -1, 0} untargeted and {0, 0, -1, 0} targeted (AS:270-276). The epoch is taken when its attack accuracy is <= the
+ * best (untargeted) or >= the best (targeted) - a tie goes to the later epoch; then best is updated and *flag = 1, else
+ * *flag = 0. A NaN accuracy (an epoch without views) is never taken. record: float32 [NERFAIL_ATTACK_ROW_FLOATS] =
+ *   {test loss, test acc, attack loss, attack acc, image loss, views, taken, best epoch, best acc, best loss, epoch,
+ *    correct(ori_cla), correct(cla), 0, 0, 0}. The row is not written. */
+int nerfail_attack_epoch_close(const float* row, float* best, int epoch, int targeted, float* record, int32_t* flag,
+                               void* stream);
+
+/* dst[0..n) = src[0..n) if *flag != 0, else nothing is written (the best tensor of AS:426/431 without a host decision).
+ * Every workgroup reads the same flag word, written by an EARLIER launch on the stream. 128-bit copies when both pointers are
+ * 16-byte aligned. src and dst must not overlap. */
+int nerfail_copy_if(const int32_t* flag, const float* src, float* dst, int64_t n, void* stream);
+
+/* float32 -> uint8 as cv2.imwrite stores a float image (AS:401-402): clamp to [0, 255], round half to even; NaN -> 0. */
+int nerfail_export_u8(const float* src, int64_t n, unsigned char* dst, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

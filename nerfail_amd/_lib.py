@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NERFAIL_HIP_LIB') or os.path.join(_HERE, 'lib', 'libnerfail_hip.so')   # override: A/B builds (tools/ablate.py)
 
 ABI_VERSION = 14
+ABI_REVISION = 15                        # additions since ABI_VERSION (nerfail_abi_revision): the NeRFail-S epoch statistics
+ATTACK_ROW_FLOATS = 16                   # NERFAIL_ATTACK_ROW_FLOATS: the stats row and the epoch record of attack.nerfail_s
 MAX_DEPTH = 16
 DW_BF16X3, DW_ACCUMULATE = 1, 2          # flags of nerfail_mlp_bwd_weights
 RAY_FLOATS = 11
@@ -144,6 +146,14 @@ SIGNATURES = {
     'nerfail_adam_step': (c_i, [c_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_p]),
     'nerfail_mse': (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p]),
     'nerfail_mse_part': (c_i, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p]),
+    'nerfail_abi_revision': (c_i, []),
+    'nerfail_attack_logit_stats': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    'nerfail_img_sqerr_scratch_bytes': (ctypes.c_size_t, []),
+    'nerfail_img_sqerr': (c_i, [c_p, c_p, c_i, c_i64, c_i, c_p, c_p, c_p]),
+    'nerfail_img_sqerr_grad_add': (c_i, [c_p, c_p, c_i, c_i64, c_i, c_f, c_p, c_p]),
+    'nerfail_attack_epoch_close': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    'nerfail_copy_if': (c_i, [c_p, c_p, c_p, c_i64, c_p]),
+    'nerfail_export_u8': (c_i, [c_p, c_i64, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -193,8 +203,9 @@ def load():
         fn.restype = res
         fn.argtypes = args
     v = lib.nerfail_abi_version()
-    if v != ABI_VERSION:
-        raise RuntimeError('nerfail_amd: ABI version %d, expected %d - rebuild the library' % (v, ABI_VERSION))
+    if v != ABI_VERSION or lib.nerfail_abi_revision() != ABI_REVISION:
+        raise RuntimeError('nerfail_amd: ABI version %d revision %d, expected %d / %d - rebuild the library'
+                           % (v, lib.nerfail_abi_revision(), ABI_VERSION, ABI_REVISION))
     _lib = lib
     return lib
 

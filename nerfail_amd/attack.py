@@ -4,7 +4,9 @@
 (forward through gauss_net, CE loss, backward to the perturbation, sign step, epsilon clamp); with
 torch.distributed initialised it shards the batch's views over ranks and sums the perturbation gradient
 with ONE all-reduce (RCCL over xGMI on the GPU box, gloo in the CPU tests) before every rank applies the
-identical step - the only collective on the whole path.
+identical step - the only collective on the whole path. `nerfail_s` is the whole AS:278-442 loop as a
+product: epoch statistics, best tensor and export epoch, decided on the device (csrc/attack_stats.hip); under
+torch.distributed it adds one all-reduce of a 16-float statistics row per EPOCH.
 """
 import torch
 import torch.distributed as dist
@@ -175,3 +177,240 @@ def nerfail_s_loop(net, spatial, spatial_init, batches, label, iters, a=2.0, eps
             if on_iter is not None:
                 on_iter(it, b, s, loss)
     return s
+
+
+# ---------------------------------------------------------------------------------------------- the product loop (AS:278-442)
+STAT_FIELDS = ('test_loss', 'test_acc', 'attack_loss', 'attack_acc', 'img_loss', 'views', 'taken', 'best_epoch', 'best_acc',
+               'best_loss', 'epoch', 'test_correct', 'attack_correct')
+
+
+class AttackResult:
+    """What nerfail_s returns. `best`: the perturbation the rule of AS:422-431 kept (device tensor) - the attack's result, the
+    tensor the export epoch rendered; `last`: the last iterate; `stats`: one dict per epoch (STAT_FIELDS, plus epsilon_3d_min /
+    epsilon_3d_max; the last one is the export epoch's); `best_epoch` / `best_acc`: epoch and attack accuracy of `best`
+    (-1 / None when no attack epoch ran). The export epoch's record carries the rule of AS:422-431 applied once more, to the
+    export pass's accuracy, as the reference applies it after its last epoch: its `taken` / `best_epoch` / `best_acc` /
+    `best_loss` fields describe that comparison, not the kept tensor - `best_epoch` / `best_acc` of this object do (they
+    are the last ATTACK epoch's record)."""
+
+    def __init__(self, best, last, stats, best_epoch, best_acc):
+        self.best, self.last, self.stats, self.best_epoch, self.best_acc = best, last, stats, best_epoch, best_acc
+
+
+def _read_stats(record, minmax):
+    """THE host read of an epoch: its record and the running epsilon_3d [min, max], one device-to-host copy."""
+    v = torch.cat([record, minmax]).cpu().tolist()
+    d = dict(zip(STAT_FIELDS, v))
+    for k in ('views', 'taken', 'best_epoch', 'epoch', 'test_correct', 'attack_correct'):
+        d[k] = int(d[k])
+    d['epsilon_3d_min'], d['epsilon_3d_max'] = v[-2], v[-1]
+    return d
+
+
+def _ori_pointer_table(views):
+    return (_lib.c_p * views.B)(*[o.data_ptr() for o in views.ori])
+
+
+class _EpochStats:
+    """The device side of one run's bookkeeping: a stats row and a record per epoch, the best record, the flag word."""
+
+    def __init__(self, epochs, targeted, label, dev):
+        n = _lib.ATTACK_ROW_FLOATS
+        self.rows = torch.zeros((epochs, n), dtype=torch.float32, device=dev)
+        self.records = torch.zeros((epochs, n), dtype=torch.float32, device=dev)
+        self.best = torch.zeros((4,), dtype=torch.float32, device=dev)     # {acc, loss, epoch, -}; filled on the device: no host copy
+        self.best[0:1].fill_(0. if targeted else 10000.)                   # AS:270-276
+        self.best[2:3].fill_(-1.)
+        self.flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.lib = _lib.load()
+        self.scratch = torch.empty((self.lib.nerfail_img_sqerr_scratch_bytes() // 8,), dtype=torch.float64, device=dev)
+        self.targeted, self.label = int(bool(targeted)), int(label)
+
+    def batch(self, epoch, cla, ori_cla, x_rgba, views):
+        """AS:319-344 for one batch (this rank's views of it): five sums into the epoch's row, no host read."""
+        row = _lib.dev(self.rows[epoch])
+        c, oc = _lib.f32c(cla), _lib.f32c(ori_cla)
+        _lib.check(self.lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], self.label, row, _lib.stream()))
+        _lib.check(self.lib.nerfail_img_sqerr(_lib.dev(x_rgba.detach()), _ori_pointer_table(views), views.B, views.P, int(views.ori_u8),
+                                              _lib.c_p(self.scratch.data_ptr()), row, _lib.stream()))
+
+    def close(self, epoch, group, world):
+        if world > 1 or sharding.force_collectives():
+            sharding.all_reduce_sum_(self.rows[epoch], group)        # the ONE extra collective of an epoch: 16 floats
+        _lib.check(self.lib.nerfail_attack_epoch_close(_lib.dev(self.rows[epoch]), _lib.dev(self.best), epoch, self.targeted,
+                                                       _lib.dev(self.records[epoch]), _lib.dev(self.flag), _lib.stream()))
+
+    def keep_if_taken(self, s, best):
+        _lib.check(self.lib.nerfail_copy_if(_lib.dev(self.flag), _lib.dev(s), _lib.dev(best), s.numel(), _lib.stream()))
+
+
+def _batch_parts(batch, lo=None, hi=None):
+    wi, ori = batch[0], batch[1]
+    vids = batch[2] if len(batch) > 2 else getattr(wi, 'view_ids', None)
+    if lo is None:
+        return wi, ori, vids
+    return (None if wi is None else wi[lo:hi]), (None if ori is None else ori[lo:hi]), (None if vids is None else list(vids)[lo:hi])
+
+
+def _batch_size(batch):
+    wi, _, vids = _batch_parts(batch)
+    return len(vids) if vids is not None else (len(wi) if isinstance(wi, (list, tuple)) else wi.shape[0])
+
+
+def _attack_batch(net, s, s_init, batch, lab, a, epsilon, targeted, beta, stats, epoch, group, world, rank):
+    """One batch of an attack epoch: forward, the batch's statistics (on the perturbation BEFORE this batch's update, as the
+    reference takes them), the objective (1 - |beta|) CE + beta MSE of AS:332-336, backward, sign step. beta == 0 on one rank
+    is perturbation_step_rgb call for call (the fused gather backward + sign step); more than one rank shards the views as
+    sharded_perturbation_grad_rgb does and sums gradient + loss in its one all-reduce."""
+    from .GaussNet import hot_backward_rgb, hot_backward_rgb_step
+    B = _batch_size(batch)
+    sharded = world > 1 or sharding.force_collectives()
+    lo, hi = sharding.shard_range(B, rank, world) if sharded else (0, B)
+    Ns = s.numel() // 4
+    beta_1 = 1. - abs(beta)                                            # AS:332-334
+    if hi > lo:
+        wi, ori, vids = _batch_parts(batch, lo, hi) if sharded else _batch_parts(batch)
+        xr, cla, ori_cla, views, aux = net.attack_forward(s, wi, ori, vids)
+        stats.batch(epoch, cla.detach(), ori_cla.detach(), xr, views)
+        loss = torch.nn.functional.cross_entropy(cla, lab.broadcast_to([cla.shape[0]]), reduction='sum') / float(B)
+        if beta != 0.:
+            loss = beta_1 * loss
+        loss.backward()
+        if beta != 0.:                                                # d (beta mean((x_rgba - ori)^2)) / d x_rgba, mean over the WHOLE batch
+            _lib.check(stats.lib.nerfail_img_sqerr_grad_add(_lib.dev(xr.detach()), _ori_pointer_table(views), views.B, views.P, int(views.ori_u8),
+                                                            2. * float(beta) / (4. * views.P * B), _lib.dev(xr.grad), _lib.stream()))
+        if not sharded and getattr(net, 'fused_sign_step', True):
+            return hot_backward_rgb_step(aux, xr.grad, views, s, s_init, a, epsilon, targeted).view(s.shape)
+        buf = torch.empty((3 * Ns + 1,), dtype=torch.float32, device=xr.device)
+        hot_backward_rgb(aux, xr.grad, views, buf)
+        buf[3 * Ns] = loss.detach()
+    else:                                                             # more ranks than views: this rank only takes part in the sum
+        buf = torch.zeros((3 * Ns + 1,), dtype=torch.float32, device=_cuda())
+    if sharded:
+        sharding.all_reduce_sum_(buf, group)
+    return igsm_step_rgb(s, buf, s_init, a, epsilon, targeted).view(s.shape)
+
+
+class _ExportBuffers:
+    """Device uint8 [2,B,H,W,4] (adversarial image, mask image) and its pinned host twin, kept per batch shape."""
+
+    def __init__(self):
+        self.bufs = {}
+
+    def get(self, shape, dev):
+        if shape not in self.bufs:
+            self.bufs[shape] = (torch.empty((2,) + shape, dtype=torch.uint8, device=dev),
+                                torch.empty((2,) + shape, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
+        return self.bufs[shape]
+
+
+def _export_batch(net, best, batch, index, stats, epoch, world, rank, bufs, on_export):
+    """AS:310-317, 394-403 for one batch (this rank's views of it): the best tensor through the forward without gradient, the
+    same statistics, then x_rgba and the unclipped mask image x as uint8 to the host in ONE copy."""
+    from .GaussNet import hot_forward, resolve_views
+    B = _batch_size(batch)
+    sharded = world > 1 or sharding.force_collectives()                  # (as _attack_batch)
+    lo, hi = sharding.shard_range(B, rank, world) if sharded else (0, B)
+    if hi <= lo:
+        return
+    wi, ori, vids = _batch_parts(batch, lo, hi) if sharded else _batch_parts(batch)
+    lib = stats.lib
+    with torch.no_grad():
+        views = resolve_views(best, wi, ori, vids, net.keep_views_resident)
+        x, x_rgba, _ = hot_forward(best, views, net.epsilon, net._mm() if net.update_epsilon_3d else None, need_x=True)
+        net._ori_keep_src = getattr(views, '_ori_keep', None)
+        cla, ori_cla = net.cold_tail(x_rgba, views.ori_float, ori_key=net._ori_key(views))
+        net._ori_keep_src = None
+        stats.batch(epoch, cla, ori_cla, x_rgba, views)
+        if on_export is None:
+            return
+        d_u8, h_u8, ev = bufs.get(tuple(x_rgba.shape), x_rgba.device)     # (free again: every call waits for its own copy below)
+        n = x_rgba.numel()
+        _lib.check(lib.nerfail_export_u8(_lib.dev(x_rgba), n, _lib.dev(d_u8[0]), _lib.stream()))
+        _lib.check(lib.nerfail_export_u8(_lib.dev(x), n, _lib.dev(d_u8[1]), _lib.stream()))
+        h_u8.copy_(d_u8, non_blocking=True)
+        ev.record()
+        ev.synchronize()
+    arr = h_u8.numpy()
+    on_export(index, vids, arr[0].copy(), arr[1].copy())
+
+
+def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=False, beta=0., export_batches=None,
+              on_export=None, log=print, group=None):
+    """The NeRFail-S attack loop, AS:278-442, as one call: the counterpart of train.train().
+
+    `spatial`: the perturbation table [P,H,W,4] (BGRA rows; also the init the epsilon clamp is centred on, AS:265). `batches`:
+    the attack epochs' batch list - or a callable of the epoch that returns it (a reshuffling / subsampling loader, AS:230) -
+    each batch `(weight_and_index, ori_img[, view_ids])` as nerfail_s_loop takes them. `label`: the class index (int or a
+    tensor). Epochs 0 .. epochs-2 attack: per batch the forward, the batch's statistics (CE and accuracy of the clean and of
+    the attacked logits, the image loss MSE(x_rgba, ori_img), all of the perturbation BEFORE this batch's update, AS:319-344),
+    then the step - with beta == 0 today's fused path (bit for bit nerfail_s_loop), else the objective
+    (1 - |beta|) CE + beta MSE of AS:332-336. At the end of an epoch the sums become the epoch's means (AS:405-413), the
+    perturbation is kept as the best one when its attack accuracy is <= the best so far (>= when targeted; a tie goes to the
+    later epoch, AS:422-431) and net.epsilon_3d_zero() runs (AS:420). Epoch epochs-1 is the export epoch (AS:299-312,
+    394-403): the BEST tensor, no gradient, over `export_batches` (default: the attack batches), the same statistics, and
+    `on_export(batch_index, view_ids, adv_u8, mask_u8)` per batch with host uint8 arrays [B,H,W,4] of x_rgba and of the
+    unclipped mask image x, converted as cv2.imwrite converts a float image. With epochs == 1 there is no attack epoch and the
+    initial tensor is exported (AS:266 sets the best tensor to the init before the loop, so the reference's only epoch would
+    render the init as well; nothing of it is tested there).
+
+    Nothing between epoch ends waits for the GPU: the statistics accumulate in a device row, the rule is decided on the
+    device (nerfail_attack_epoch_close) and the best tensor kept by a conditional copy (nerfail_copy_if). One host read per
+    epoch (the epoch's record, for the four log lines of AS:415-418 and print_epsilon's two; log=None keeps the read and
+    drops the lines); the export epoch additionally waits once per batch for its images. Requires the deterministic
+    rgb-gradient step path (net.deterministic and net.rgb_grad_only, the defaults).
+
+    More than one rank (torch.distributed; `group`): every batch's views are sharded as nerfail_s_step shards them, each rank
+    accumulates the statistics of the views it owns, ONE extra all-reduce per epoch sums the stats row before the close, so
+    every rank takes the same decisions and ends with the same `best`. on_export is called on every rank for its own views.
+
+    Returns an AttackResult (best, last, stats, best_epoch, best_acc)."""
+    if not (getattr(net, 'deterministic', True) and getattr(net, 'rgb_grad_only', True)):
+        raise ValueError('nerfail_s runs the deterministic rgb-gradient step path (net.deterministic and net.rgb_grad_only)')
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    if not -1. <= float(beta) <= 1.:
+        raise ValueError('beta must be in [-1, 1] (AS:332-336)')
+    dev = _cuda()
+    beta = float(beta)
+    world, rank = sharding.world_and_rank(group)
+    label_i = int(label)                                              # (a device label is read once, before the first epoch)
+    lab = torch.full((), label_i, dtype=torch.int64, device=dev)
+    s_init = _lib.f32c(spatial, dev)
+    s = s_init
+    best = s_init.clone()
+    stats = _EpochStats(epochs, targeted, label_i, dev)
+    bufs = _ExportBuffers()
+    records = []
+
+    def finish(epoch):
+        d = _read_stats(stats.records[epoch], net._mm())
+        records.append(d)
+        if log is not None and rank == 0:
+            log('Attack ...... [%d/%d]' % (epoch, epochs))
+            log('{} Loss: {:.4f} Acc: {:.4f}'.format('test', d['test_loss'], d['test_acc']))                       # AS:415-418
+            log('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', d['attack_loss'], d['attack_acc']))
+            b1 = 1. - beta                                                                                        # (AS:340 has no abs)
+            log('{} Beta Loss: {:.4f} Beta Img Loss: {:.4f}'.format('attack', b1 * d['attack_loss'], beta * d['img_loss']))
+            log('{} Img Loss: {:.4f} Total Loss: {:.4f}'.format('attack', d['img_loss'],
+                                                                  (1. - abs(beta)) * d['attack_loss'] + beta * d['img_loss']))
+            log('epsilon_3d_min:  %s' % d['epsilon_3d_min'])
+            log('epsilon_3d_max:  %s' % d['epsilon_3d_max'])
+        net.epsilon_3d_zero()                                         # AS:420
+
+    for epoch in range(epochs - 1):
+        for batch in (batches(epoch) if callable(batches) else batches):
+            s = _attack_batch(net, s, s_init, batch, lab, float(a), float(epsilon), bool(targeted), beta, stats, epoch, group, world, rank)
+        stats.close(epoch, group, world)
+        stats.keep_if_taken(s, best)
+        finish(epoch)
+    epoch = epochs - 1
+    exp = export_batches if export_batches is not None else batches
+    for i, batch in enumerate(exp(epoch) if callable(exp) else exp):
+        _export_batch(net, best, batch, i, stats, epoch, world, rank, bufs, on_export)
+    stats.close(epoch, group, world)                                  # (its decision moves no tensor: the epoch ran on `best` itself)
+    finish(epoch)
+    last_attack = records[-2] if epochs > 1 else None
+    return AttackResult(best, s, records, last_attack['best_epoch'] if last_attack else -1,
+                        last_attack['best_acc'] if last_attack else None)

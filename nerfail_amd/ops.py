@@ -579,3 +579,82 @@ class CnnTrainFn(torch.autograd.Function):
 
 
 CNN_OPS = ('cnn_fwd', 'cnn_bwd_data', 'cnn_bwd_data_multi', 'cnn_bwd_weights')
+
+
+# ----------------------------------------------------------------------------------------------- NeRFail-S epoch statistics (AS:319-344, 405-431; ABI 15)
+def _ori_pointers(ori, n_views, P):
+    """Host array of the per-view image pointers of a dense [n_views, ..., 4] image tensor (float32 or uint8)."""
+    if ori.dtype not in (torch.float32, torch.uint8) or not ori.is_contiguous() or ori.numel() != n_views * P * 4:
+        raise ValueError('ori must be a contiguous float32 or uint8 tensor with the shape of x_rgba')
+    step = P * 4 * ori.element_size()
+    return (_lib.c_p * n_views)(*[ori.data_ptr() + b * step for b in range(n_views)])
+
+
+def _row_ok(row, name='row'):
+    if row.dtype != torch.float32 or row.numel() != _lib.ATTACK_ROW_FLOATS or not row.is_contiguous():
+        raise ValueError('%s must be %d contiguous float32' % (name, _lib.ATTACK_ROW_FLOATS))
+
+
+@custom_op(NS + '::attack_logit_stats', mutates_args=('row',), device_types='cuda')
+def attack_logit_stats(cla: Tensor, ori_cla: Tensor, label: int, row: Tensor) -> None:
+    """Adds sum CE(ori_cla), sum CE(cla), correct(ori_cla), correct(cla), B of one batch's [B,C] logits into the stats row."""
+    _row_ok(row)
+    if cla.dim() != 2 or cla.shape != ori_cla.shape:
+        raise ValueError('cla and ori_cla must both be [B,C]')
+    _chk(_lib.load().nerfail_attack_logit_stats(_lib.dev(_lib.f32c(cla)), _lib.dev(_lib.f32c(ori_cla)), cla.shape[0], cla.shape[1], label,
+                                                _lib.dev(row), _s()))
+
+
+@custom_op(NS + '::img_sqerr', mutates_args=('row',), device_types='cuda')
+def img_sqerr(x_rgba: Tensor, ori: Tensor, row: Tensor) -> None:
+    """Adds sum (x_rgba - ori)^2 over [B,...,4] and the element count into the stats row; ori float32 or uint8."""
+    _row_ok(row)
+    B, P = x_rgba.shape[0], x_rgba.numel() // (4 * max(x_rgba.shape[0], 1))
+    lib = _lib.load()
+    scratch = torch.empty((lib.nerfail_img_sqerr_scratch_bytes() // 8,), dtype=torch.float64, device=x_rgba.device)
+    _chk(lib.nerfail_img_sqerr(_lib.dev(x_rgba), _ori_pointers(ori, B, P), B, P, int(ori.dtype == torch.uint8), _lib.c_p(scratch.data_ptr()),
+                               _lib.dev(row), _s()))
+
+
+@custom_op(NS + '::img_sqerr_grad_add', mutates_args=('g',), device_types='cuda')
+def img_sqerr_grad_add(x_rgba: Tensor, ori: Tensor, scale: float, g: Tensor) -> None:
+    """g += scale (x_rgba - ori): the beta term of AS:336 in d loss / d x_rgba."""
+    B, P = x_rgba.shape[0], x_rgba.numel() // (4 * max(x_rgba.shape[0], 1))
+    if g.shape != x_rgba.shape:
+        raise ValueError('g must have the shape of x_rgba')
+    _chk(_lib.load().nerfail_img_sqerr_grad_add(_lib.dev(x_rgba), _ori_pointers(ori, B, P), B, P, int(ori.dtype == torch.uint8), scale,
+                                                _lib.dev(g), _s()))
+
+
+@custom_op(NS + '::attack_epoch_close', mutates_args=('best', 'record', 'flag'), device_types='cuda')
+def attack_epoch_close(row: Tensor, best: Tensor, epoch: int, targeted: bool, record: Tensor, flag: Tensor) -> None:
+    """AS:405-431: the row's sums -> the epoch record; the best-so-far rule against `best` (float32 [4]); flag (int32 [1])."""
+    _row_ok(row)
+    _row_ok(record, 'record')
+    if best.dtype != torch.float32 or best.numel() != 4 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError('best must be float32 [4] and flag int32 [1]')
+    _chk(_lib.load().nerfail_attack_epoch_close(_lib.dev(row), _lib.dev(best), epoch, int(targeted), _lib.dev(record), _lib.dev(flag), _s()))
+
+
+@custom_op(NS + '::copy_if', mutates_args=('dst',), device_types='cuda')
+def copy_if(flag: Tensor, src: Tensor, dst: Tensor) -> None:
+    """dst <- src when the int32 flag word on the device is set."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float32 or src.numel() != dst.numel() or flag.dtype != torch.int32:
+        raise ValueError('src and dst must be float32 of one size, flag int32')
+    _chk(_lib.load().nerfail_copy_if(_lib.dev(flag), _lib.dev(src), _lib.dev(dst), src.numel(), _s()))
+
+
+@custom_op(NS + '::export_u8', mutates_args=(), device_types='cuda')
+def export_u8(src: Tensor) -> Tensor:
+    """uint8 of a float image as cv2.imwrite stores it: clamp to [0, 255], round half to even, NaN -> 0."""
+    out = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+    _chk(_lib.load().nerfail_export_u8(_lib.dev(src), src.numel(), _lib.dev(out), _s()))
+    return out
+
+
+@export_u8.register_fake
+def _(src):
+    return src.new_empty(src.shape, dtype=torch.uint8)
+
+
+ATTACK_STATS_OPS = ('attack_logit_stats', 'img_sqerr', 'img_sqerr_grad_add', 'attack_epoch_close', 'copy_if', 'export_u8')
