@@ -261,7 +261,9 @@ int nerfail_mlp_bwd_data2(const float* packed0, const float* packedT0, int64_t M
  *        (fp32 accumulation, fp32 exponent range, ~1.5e-5 relative per product: a gradient-grade opt-in mode).
  * W = 256: LDS-staged kernel, NO float atomics - every workgroup writes its partial block to `scratch`
  * (nerfail_mlp_bwd_weights_scratch_bytes) and a second kernel adds the partials in workgroup order, so the result is
- * bitwise reproducible. Other widths (and NERFAIL_DW_KERNEL=reg): register-fed kernel with float atomics, no scratch. */
+ * bitwise reproducible. Other widths (and NERFAIL_DW_KERNEL=reg): register-fed kernel with float atomics, no scratch.
+ * D <= 10 (the descriptor table of both kernels): a deeper network is refused with NERFAIL_EINVAL before anything is launched,
+ * the gradient tensors keep what they held. */
 #define NERFAIL_DW_BF16X3 1
 #define NERFAIL_DW_ACCUMULATE 2
 size_t nerfail_mlp_bwd_weights_scratch_bytes(int D, int W, int skip, int64_t M0, int64_t M1, int flags);

@@ -880,6 +880,8 @@ extern "C" int nerfail_mlp_bwd_weights(int D, int W, int skip, const float* acts
     if (!use_lds_dw(W)) {
         MlpLayout L;
         NF_REQUIRE(make_layout(D, W, skip, L), "unsupported (D, W)");
+        // (before zero_grads: a refused call leaves the gradient buffers as they were)
+        NF_REQUIRE(D + 4 <= kMaxDesc, "network too deep for the weight-gradient descriptor table");
         const TrainLayout TL = make_train_layout(D, W);
         const long tiles0 = (M0 + 31) / 32;
         for (int net = 0; net < 2; ++net) {

@@ -303,24 +303,31 @@ def raw2outputs_backward(raw, z_vals, rays_d, d_rgb_map, white_bkgd=True):
 
 
 def train_step_grads(ray_batch, sd_coarse, sd_fine, target, N_samples=64, N_importance=128, t_rand=None, u=None,
-                     D=8, W=256, white_bkgd=True):
-    """One training step's loss and parameter gradients (RN:776-791): loss = mse(rgb, t) + mse(rgb0, t)."""
+                     D=8, W=256, white_bkgd=True, arch_coarse=None, arch_fine=None):
+    """One training step's loss and parameter gradients (RN:776-791): loss = mse(rgb, t) + mse(rgb0, t).
+    arch_coarse / arch_fine = (D, W, skips) of each network (default: (D, W, (4,)) for both). sd_fine=None: the coarse network
+    is evaluated for both passes (RN:399); grads_coarse is then the sum of both passes and grads_fine is None."""
+    Dc, Wc, skc = arch_coarse if arch_coarse is not None else (D, W, (4,))
+    Df, Wf, skf = arch_fine if arch_fine is not None else ((Dc, Wc, skc) if sd_fine is None else (D, W, (4,)))
     ray_batch = np.asarray(ray_batch, F32)
     rays_o, rays_d, viewdirs = ray_batch[:, 0:3], ray_batch[:, 3:6], ray_batch[:, -3:]
     z0 = coarse_z_vals(ray_batch[:, 6:7], ray_batch[:, 7:8], N_samples, t_rand)
     pts0 = (rays_o[:, None, :] + rays_d[:, None, :] * z0[:, :, None]).astype(F32)
-    raw0, cache0 = _mlp_forward_cached(sd_coarse, pts0, viewdirs, D, W)
+    raw0, cache0 = _mlp_forward_cached(sd_coarse, pts0, viewdirs, Dc, Wc, skc)
     rgb0, _, _, w0, _ = raw2outputs(raw0, z0, rays_d, None, white_bkgd)
     z_mid = F32(.5) * (z0[..., 1:] + z0[..., :-1])
     z_s = sample_pdf(z_mid, w0[..., 1:-1], N_importance, u=u)
     z1 = np.sort(np.concatenate([z0, z_s], -1), -1)
     pts1 = (rays_o[:, None, :] + rays_d[:, None, :] * z1[:, :, None]).astype(F32)
-    raw1, cache1 = _mlp_forward_cached(sd_fine, pts1, viewdirs, D, W)
+    sd_run = sd_fine if sd_fine is not None else sd_coarse
+    raw1, cache1 = _mlp_forward_cached(sd_run, pts1, viewdirs, Df, Wf, skf)
     rgb1, _, _, _, _ = raw2outputs(raw1, z1, rays_d, None, white_bkgd)
     target = np.asarray(target, F32)
     loss = float(np.mean((rgb1 - target) ** 2, dtype=np.float64) + np.mean((rgb0 - target) ** 2, dtype=np.float64))
     n = rgb1.size
     d1 = raw2outputs_backward(raw1, z1, rays_d, 2.0 * (rgb1 - target) / n, white_bkgd)
     d0 = raw2outputs_backward(raw0, z0, rays_d, 2.0 * (rgb0 - target) / n, white_bkgd)
-    return dict(loss=loss, rgb_map=rgb1, rgb0=rgb0, d_raw_fine=d1, d_raw_coarse=d0,
-                grads_fine=mlp_backward(sd_fine, cache1, d1, D, W), grads_coarse=mlp_backward(sd_coarse, cache0, d0, D, W))
+    g1, g0 = mlp_backward(sd_run, cache1, d1, Df, Wf, skf), mlp_backward(sd_coarse, cache0, d0, Dc, Wc, skc)
+    if sd_fine is None:
+        g0, g1 = {k: (g0[k].astype(np.float64) + g1[k]).astype(F32) for k in g0}, None
+    return dict(loss=loss, rgb_map=rgb1, rgb0=rgb0, d_raw_fine=d1, d_raw_coarse=d0, grads_fine=g1, grads_coarse=g0)

@@ -437,8 +437,13 @@ def test_lds_training_forward_saves_the_same_bits_as_the_register_kernel():
     lib = _lib.load()
     rs = np.random.RandomState(4)
     try:
-        for (D, W, seed, R, Ns) in ((8, 256, 12, 1500, 64), (8, 256, 13, 37, 5), (4, 64, 14, 301, 192)):
-            _, net = hip_nerf(D, W, seed, requires_grad=True)
+        cases = [(8, 256, 12, 1500, 64, (4,)), (8, 256, 13, 37, 5, (4,)), (4, 64, 14, 301, 192, (4,))]
+        # every other even-depth instantiation <NT, SKIP, true> the training forward can reach (SKIP: 0 no skip, 1 / 2 the skip
+        # layer is the first / second of a pair), on 37 x 31 samples: 35 full tiles + a ragged one
+        cases += [(D, W, 20 + i, 37, 31, (sk,) if sk >= 0 else ()) for i, (D, W, sk) in enumerate(
+            ((4, 64, 1), (4, 64, 2), (2, 128, -1), (4, 128, 1), (6, 128, 4), (2, 256, -1), (4, 256, 0), (6, 256, 3)))]
+        for (D, W, seed, R, Ns, skips) in cases:
+            _, net = hip_nerf(D, W, seed, requires_grad=True, skips=skips)
             pts = T(rs.uniform(-3, 3, size=(R, Ns, 3)).astype(np.float32))
             vd = rs.normal(size=(R, 3)).astype(np.float32)
             vd = T(vd / np.linalg.norm(vd, axis=1, keepdims=True))
@@ -449,14 +454,15 @@ def test_lds_training_forward_saves_the_same_bits_as_the_register_kernel():
                 acts = torch.full((n,), float('nan'), device=dev())
                 raw, acts = _train.mlp_fwd_train(net, pts, vd, acts=acts)
                 out[which] = (raw.clone(), acts.clone())
-            assert torch.equal(out[1][0].view(torch.int32), out[2][0].view(torch.int32)), (D, W, 'raw')
+            assert torch.equal(out[1][0].view(torch.int32), out[2][0].view(torch.int32)), (D, W, skips, 'raw')
+            assert float(out[1][0].abs().max()) > 0
             a1, a2 = out[1][1].view(torch.int32), out[2][1].view(torch.int32)
             if (R * Ns) % 32 == 0:
-                assert torch.equal(a1, a2), (D, W, 'acts', int((a1 != a2).sum()))
+                assert torch.equal(a1, a2), (D, W, skips, 'acts', int((a1 != a2).sum()))
             else:   # the padding samples of the ragged last tile are whatever the clamped sample gives: compare whole tiles only
                 per_tile = n // ((R * Ns + 31) // 32)
                 full = (R * Ns) // 32 * per_tile
-                assert torch.equal(a1[:full], a2[:full]), (D, W, 'acts of the full tiles')
+                assert torch.equal(a1[:full], a2[:full]), (D, W, skips, 'acts of the full tiles')
     finally:
         lib.nerfail_mlp_fwd_select(0)
 
