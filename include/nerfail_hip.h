@@ -202,6 +202,29 @@ int nerfail_mlp_fwd_embedded_x3f(const float* packed, const void* x3f, int D, in
 int nerfail_mlp_fwd_rays_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
                              const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream);
 
+/* The folded kernel with the view-direction term computed once per RAY (additions only: version and revision words unchanged; a
+ * library without them fails the loader's symbol check). When samples_per_ray is a multiple of 32 every 32-sample tile lies
+ * inside one ray, and Wv[:, W:] enc(d) is one W/2-vector per ray. nerfail_mlp_x3f_viewbias writes
+ *     vb[r][bias_index(i)] = float( bc[i] + sum_{m = 0..26} Wv[i][W + m] * enc(d_r)[m] )
+ * - from the composed f32 bc[i] of the folded image, the terms added in this order in double (each product exact), rounded
+ * once; enc(d) the direction encoding of every MLP kernel (x, y, z, then per band sin(3), cos(3)); row r in the kernels' bias
+ * piece order (mlp_layout.h) - for the directions of `rays` [n_rays,11] or (exactly one of the two non-NULL) `viewdirs`
+ * [n_rays,3]. The _raybias entry points run it into `vb` and then the folded kernel in a form that neither encodes directions
+ * nor runs the direction part: a tile's row replaces the composed bias. raw[..., 3] is bitwise that of the plain folded
+ * kernel; raw[..., :3] is f32-accurate, not bitwise. `vb`: nerfail_mlp_x3f_raybias_floats() floats, a temporary of the call.
+ * That function returns 0 when the form does not serve the call - samples_per_ray not a multiple of 32, a shape the folded
+ * image does not cover, reg / lds forced (NERFAIL_FWD_KERNEL), or the form switched off (NERFAIL_X3_RAYBIAS=0, read once;
+ * nerfail_mlp_x3_raybias_select(0 | 1) sets it and returns the previous value, any other argument only queries): the caller
+ * then uses nerfail_mlp_fwd[_rays]_x3f, and the _raybias entry points refuse the call. Inference only. */
+size_t nerfail_mlp_x3f_raybias_floats(int D, int W, int skip, int64_t n_rays, int samples_per_ray);
+int nerfail_mlp_x3_raybias_select(int on);
+int nerfail_mlp_x3f_viewbias(const float* packed, const void* x3f, int D, int W, int skip, const float* rays, const float* viewdirs,
+                             int64_t n_rays, float* vb, void* stream);
+int nerfail_mlp_fwd_x3f_raybias(const float* packed, const void* x3f, int D, int W, int skip, const float* pts, const float* viewdirs,
+                                int64_t M, int samples_per_ray, float* raw, float* vb, void* stream);
+int nerfail_mlp_fwd_rays_x3f_raybias(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
+                                     const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* vb, void* stream);
+
 /* ---- split-precision ("f16x3") forward: same contract as nerfail_mlp_fwd, fp32-equivalent results --------
  * Every product a*w is evaluated as a_hi*w_hi + a_hi*w_lo + a_lo*w_hi on the fp16 matrix cores with fp32
  * accumulation (a_hi = fp16(a), a_lo = fp16(a - a_hi); weights pre-scaled by 2^10 inside the image). Opt-in: the

@@ -91,6 +91,11 @@ SIGNATURES = {
     'nerfail_mlp_fwd_x3f': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
     'nerfail_mlp_fwd_embedded_x3f': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i64, c_p, c_p]),
     'nerfail_mlp_fwd_rays_x3f': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p, c_p]),
+    'nerfail_mlp_x3f_raybias_floats': (ctypes.c_size_t, [c_i, c_i, c_i, c_i64, c_i]),
+    'nerfail_mlp_x3_raybias_select': (c_i, [c_i]),
+    'nerfail_mlp_x3f_viewbias': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_p, c_p]),
+    'nerfail_mlp_fwd_x3f_raybias': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p, c_p]),
+    'nerfail_mlp_fwd_rays_x3f_raybias': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p, c_p]),
     'nerfail_mlp_f16_image_bytes': (ctypes.c_size_t, [c_i, c_i, c_i]),
     'nerfail_mlp_pack_f16': (c_i, [ctypes.POINTER(MlpParams), c_p, c_p]),
     'nerfail_mlp_fwd_f16': (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),

@@ -34,6 +34,10 @@ int launch_mlp_x3(const MlpArgs& a, const void* img, int W, bool fold, hipStream
 size_t mlp_x3f_bytes(const MlpLayout& L, int W);                                    // the folded image (no feature layer)
 size_t mlp_x3f_composed_floats(const MlpLayout& L, int W);
 int pack_mlp_x3f(const float* packed, const MlpLayout& L, int W, void* out, hipStream_t s);
+bool mlp_x3_raybias_covers(const MlpLayout& L, int W, int spr);                     // the folded kernel's per-ray view-bias form
+int launch_mlp_x3_viewbias(const float* packed, const void* img, const MlpLayout& L, int W, const float* rays, const float* viewdirs,
+                           long R, float* vb, hipStream_t s);
+int launch_mlp_x3_raybias(const MlpArgs& a, const void* img, int W, float* vb, hipStream_t s);
 
 // ------------------------------------------------------------------------------------- device side
 template <int NT, bool TRAIN>
@@ -201,9 +205,26 @@ static int launch_mlp_x3_or(const char* fn, const MlpArgs& a, const void* img, i
     return launch_mlp(a, W, s);
 }
 
+// The per-ray view-bias form of the folded kernel (mlp_x3.hip) serves an inference call on the folded image whose samples per
+// ray are a multiple of 32, under the selection rules of the x3 entry points (not with reg / lds forced).
+// nerfail_mlp_x3_raybias_select / NERFAIL_X3_RAYBIAS=0 switch it off: the plain folded kernel then runs (A/B timing, tests).
+static int g_x3_raybias = [] {
+    const char* e = getenv("NERFAIL_X3_RAYBIAS");
+    return e && e[0] == '0' ? 0 : 1;
+}();
+static bool x3_raybias_runs(const MlpLayout& L, int W, int spr) {
+    return g_x3_raybias && (g_fwd_select == 0 || g_fwd_select == 3) && mlp_x3_raybias_covers(L, W, spr);
+}
+
 }  // namespace nerfail
 
 using namespace nerfail;
+
+extern "C" int nerfail_mlp_x3_raybias_select(int on) {
+    const int prev = g_x3_raybias;
+    if (on == 0 || on == 1) g_x3_raybias = on;
+    return prev;
+}
 
 extern "C" int nerfail_mlp_fwd_select(int which) {
     const int prev = g_fwd_select;
@@ -216,10 +237,11 @@ extern "C" int nerfail_mlp_fwd_select(int which) {
 // RN:381 / :399, instead of being read from a [M,3] tensor that the sampling kernels wrote). `in0` / `in1` are the two input
 // pointers of that form (xemb has one), `acts` asks for the training forward, `sel` for the bf16x3 selection with image `x3` (kX3Fold: the folded image).
 enum MlpInput { kInPts, kInEmbedded, kInRays };
-enum MlpSel { kF32, kX3, kX3Fold };
+enum MlpSel { kF32, kX3, kX3Fold, kX3Ray };   // kX3Ray: the folded kernel's per-ray view-bias form, `vb` its per-call buffer
 #define MLP_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return NERFAIL_EINVAL; } } while (0)
 static int mlp_fwd_entry(const char* fn, MlpInput form, const float* packed, MlpSel sel, const void* x3, int D, int W, int skip,
-                         const float* in0, const float* in1, int64_t M, int spr, float* raw, float* acts, bool need_acts, void* stream) {
+                         const float* in0, const float* in1, int64_t M, int spr, float* raw, float* acts, bool need_acts, void* stream,
+                         float* vb = nullptr) {
     MLP_REQUIRE(M >= 0, form == kInRays ? "n_rays is negative" : "M is negative");
     MLP_REQUIRE(form == kInEmbedded || spr >= 1, "samples_per_ray must be positive");
     MlpArgs a;
@@ -232,6 +254,11 @@ static int mlp_fwd_entry(const char* fn, MlpInput form, const float* packed, Mlp
     a.pts = form == kInPts ? in0 : nullptr; a.viewdirs = form == kInPts ? in1 : nullptr;
     a.xemb = form == kInEmbedded ? in0 : nullptr;
     a.rays = form == kInRays ? in0 : nullptr; a.z = form == kInRays ? in1 : nullptr;
+    if (sel == kX3Ray) {
+        MLP_REQUIRE(x3 != nullptr && vb != nullptr, "NULL pointer");
+        MLP_REQUIRE(x3_raybias_runs(a.lay, W, a.spr), "the per-ray view-bias form does not serve this call (nerfail_mlp_x3f_raybias_floats returns 0)");
+        return launch_mlp_x3_raybias(a, x3, W, vb, as_stream(stream));
+    }
     return sel != kF32 ? launch_mlp_x3_or(fn, a, x3, W, sel == kX3Fold, as_stream(stream)) : launch_mlp(a, W, as_stream(stream));
 }
 #undef MLP_REQUIRE
@@ -321,4 +348,33 @@ extern "C" int nerfail_mlp_fwd_embedded_x3f(const float* packed, const void* x3f
 extern "C" int nerfail_mlp_fwd_rays_x3f(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
                                         const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* acts, void* stream) {
     return mlp_fwd_entry(__func__, kInRays, packed, kX3Fold, x3f, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, acts, false, stream);
+}
+
+// ---- the folded kernel with the view-direction term computed once per ray (mlp_x3.hip: x3_viewbias_kernel, RAYBIAS)
+extern "C" size_t nerfail_mlp_x3f_raybias_floats(int D, int W, int skip, int64_t n_rays, int samples_per_ray) {
+    MlpLayout L;
+    if (n_rays <= 0 || !make_layout(D, W, skip, L) || !x3_raybias_runs(L, W, samples_per_ray)) return 0;
+    return (size_t)n_rays * (size_t)(W / 2);
+}
+
+extern "C" int nerfail_mlp_x3f_viewbias(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
+                                        const float* viewdirs, int64_t n_rays, float* vb, void* stream) {
+    MlpLayout L;
+    NF_REQUIRE(make_layout(D, W, skip, L), "unsupported (D, W)");
+    NF_REQUIRE(n_rays >= 0, "n_rays is negative");
+    if (n_rays == 0) return NERFAIL_OK;
+    NF_REQUIRE(packed != nullptr && x3f != nullptr && vb != nullptr && ((rays != nullptr) != (viewdirs != nullptr)),
+               "NULL pointer, or both of rays and viewdirs given");
+    return launch_mlp_x3_viewbias(packed, x3f, L, W, rays, viewdirs, n_rays, vb, as_stream(stream));
+}
+
+extern "C" int nerfail_mlp_fwd_x3f_raybias(const float* packed, const void* x3f, int D, int W, int skip, const float* pts,
+                                           const float* viewdirs, int64_t M, int samples_per_ray, float* raw, float* vb, void* stream) {
+    return mlp_fwd_entry(__func__, kInPts, packed, kX3Ray, x3f, D, W, skip, pts, viewdirs, M, samples_per_ray, raw, nullptr, false, stream, vb);
+}
+
+extern "C" int nerfail_mlp_fwd_rays_x3f_raybias(const float* packed, const void* x3f, int D, int W, int skip, const float* rays,
+                                                const float* z_vals, int64_t n_rays, int samples_per_ray, float* raw, float* vb,
+                                                void* stream) {
+    return mlp_fwd_entry(__func__, kInRays, packed, kX3Ray, x3f, D, W, skip, rays, z_vals, n_rays, samples_per_ray, raw, nullptr, false, stream, vb);
 }

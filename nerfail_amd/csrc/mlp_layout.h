@@ -185,6 +185,21 @@ struct MlpArgs {
 };
 int launch_mlp_lds(const MlpArgs& a, int W, hipStream_t s);      // mlp_lds.hip; NERFAIL_EINVAL when the shape is not covered
 
+// The view-direction part for lane half h from the direction itself: the ONE code every kernel that encodes a direction runs
+// (the per-ray view bias of mlp_x3.hip, x3_viewbias_kernel, has to agree with encode_sample bit for bit). The direction by
+// value: taken as an array reference, the inlined body leaves the bf16x3 kernels (mlp_x3.hip) with another register allocation.
+__device__ __forceinline__ void encode_dir(float v0, float v1, float v2, int h, float (&demb)[4 * kDirQuads]) {
+    const float vx[3] = {v0, v1, v2};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const SinCosBands sc(vx[d]);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) demb[3 * f + d] = sc.band_sel(f, h);
+    }
+    demb[12] = h ? vx[1] : vx[0];
+    demb[13] = h ? 0.f : vx[2];
+    demb[14] = 0.f; demb[15] = 0.f;
+}
 // B operands of the two encoding parts of sample s for lane half h (k-step st <-> channel enc_channel(st, h, bands)):
 // computed in registers from the raw point / view direction (one shared double-precision argument reduction per
 // coordinate, SinCosBands), or gathered from an already embedded input row (NeRF.forward's contract).
@@ -209,15 +224,7 @@ __device__ __forceinline__ void encode_sample(const MlpArgs& a, long s, int h, f
         }
         emb[30] = h ? px[1] : px[0];
         emb[31] = h ? 0.f : px[2];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const SinCosBands sc(vx[d]);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) demb[3 * f + d] = sc.band_sel(f, h);
-        }
-        demb[12] = h ? vx[1] : vx[0];
-        demb[13] = h ? 0.f : vx[2];
-        demb[14] = 0.f; demb[15] = 0.f;
+        encode_dir(vx[0], vx[1], vx[2], h, demb);
     } else {
         const float* x = a.xemb + (kPtsCh + kDirCh) * s;
 #pragma unroll
@@ -229,6 +236,37 @@ __device__ __forceinline__ void encode_sample(const MlpArgs& a, long s, int h, f
         for (int st = 0; st < 4 * kDirQuads; ++st) {
             const int c = enc_channel(st, h, 4);
             demb[st] = c >= 0 ? x[kPtsCh + c] : 0.f;
+        }
+    }
+}
+// The points half alone, for a caller that has the view-direction term elsewhere (the RAYBIAS kernel of mlp_x3.hip):
+// encode_sample without `demb`, the same statements
+__device__ __forceinline__ void encode_sample_pts(const MlpArgs& a, long s, int h, float (&emb)[4 * kEmbQuads]) {
+    if (a.xemb == nullptr) {
+        float px[3];
+        if (a.rays != nullptr) {
+            const float* ray = a.rays + NERFAIL_RAY_FLOATS * (s / a.spr);
+            const float zz = a.z[s];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) px[d] = mul_add_rn(ray[3 + d], zz, ray[d]);
+        } else {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) px[d] = a.pts[3 * s + d];
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const SinCosBands sc(px[d]);
+#pragma unroll
+            for (int f = 0; f < 10; ++f) emb[3 * f + d] = sc.band_sel(f, h);
+        }
+        emb[30] = h ? px[1] : px[0];
+        emb[31] = h ? 0.f : px[2];
+    } else {
+        const float* x = a.xemb + (kPtsCh + kDirCh) * s;
+#pragma unroll
+        for (int st = 0; st < 4 * kEmbQuads; ++st) {
+            const int c = enc_channel(st, h, 10);
+            emb[st] = c >= 0 ? x[c] : 0.f;
         }
     }
 }

@@ -54,6 +54,9 @@ struct X3Cfg {
     static constexpr int kConstMax = (kMaxDepth + 2) * kPiece + kAlphaFloats + kRgbFloats;   // as LdsCfg<8> (mlp_lds.hip)
     static constexpr int kParkQuads = kEmbQuads + kDirQuads;
     static constexpr int kParkFloats = 4 * 64 * 4 * kParkQuads;
+    // RAYBIAS form: no direction operands are parked; instead one 512-byte row of the per-ray view bias per wave
+    static constexpr int kRowFloats = 16 * NT;   // W / 2 channels
+    static constexpr int kParkFloatsRB = 4 * kRowFloats + 4 * 64 * 4 * kEmbQuads;
     static_assert((S - 2) * GPW <= 63, "vmcnt is a 6-bit counter");
     static_assert(GPW <= 8, "dma() covers 8 pieces per wave and group");
 };
@@ -153,9 +156,12 @@ __global__ void pack_x3_kernel(const float* __restrict__ packed, X3PackArgs p, u
 // map and its inverse (mlp_layout.h): column c of a hidden part is k-step hidden_step(c) of lane half hidden_half(c), and a
 // bias piece holds channel c at bias_index(c).
 // weight (row i, hidden column c) of layer l (OT32 32-row out tiles) in the f32 image
-__device__ __forceinline__ float x3f_weight(const float* __restrict__ packed, const MlpLayout& L, int l, int OT32, int i, int c) {
-    const int s = hidden_step(c), h = hidden_half(c);
+// weight (row i, k-step s of lane half h) of layer l (OT32 32-row out tiles) in the f32 image
+__device__ __forceinline__ float x3f_weight_at(const float* __restrict__ packed, const MlpLayout& L, int l, int OT32, int i, int s, int h) {
     return packed[L.w_off[l] + ((s >> 2) * OT32 + (i >> 5)) * kPiece + ((i & 31) + 32 * h) * 4 + (s & 3)];
+}
+__device__ __forceinline__ float x3f_weight(const float* __restrict__ packed, const MlpLayout& L, int l, int OT32, int i, int c) {
+    return x3f_weight_at(packed, L, l, OT32, i, hidden_step(c), hidden_half(c));
 }
 // threads [0, W/2 * W): Wc; then one per float of the constant area (bias piece D receives bc, zero behind it); then the bc piece
 __global__ void compose_x3f_kernel(const float* __restrict__ packed, MlpLayout L, float* __restrict__ cst, float* __restrict__ comp) {
@@ -186,6 +192,57 @@ __global__ void compose_x3f_kernel(const float* __restrict__ packed, MlpLayout L
         v = (float)acc;
     }
     (t < nconst ? cst[t] : comp[WV * W + pos]) = v;
+}
+
+// ---- the per-ray view bias of the RAYBIAS kernel. The direction columns of the views layer meet the same 27 encoded channels
+// for every sample of a ray: vb[r][i] = bc[i] + sum_m Wv[i][W + m] enc(d_r)[m] is computed once per ray, by a FIXED rule in the
+// style of compose_x3f_kernel - start from the composed f32 bc[i] (bias piece D of the folded image's constant area), add the
+// terms m = 0, 1, ..., 26 in this order in double (each product is exact there), round once to f32. enc(d) is encode_dir, the
+// code the MLP kernels run; the weight columns come from the f32 image through the forward column map. Row r is stored in bias
+// piece order (channel i at bias_index(i)): the MLP kernel's bias hooks read it with the addressing of a bias piece.
+// One workgroup = kVbRays rays: threads 2r + h encode lane half h of ray r into LDS (channel order), then thread (half, i) adds
+// up channel i for 16 of the rays, its 27 weights in registers. dirs: `rays` [R,11] (the view direction at floats 8..10) or,
+// when that is NULL, `viewdirs` [R,3].
+constexpr int kVbRays = 32;
+__global__ __launch_bounds__(256) void x3_viewbias_kernel(const float* __restrict__ packed, MlpLayout L, const float* __restrict__ cst,
+                                                          const float* __restrict__ rays, const float* __restrict__ viewdirs, long R,
+                                                          float* __restrict__ vb) {
+    __shared__ float enc[kVbRays][kDirCh + 1];
+    const int WV = 16 * L.NT, D = L.D;                                     // 2 * WV threads (host)
+    const int t = (int)threadIdx.x;
+    const long r0 = (long)blockIdx.x * kVbRays;
+    if (t < 2 * kVbRays) {
+        const int h = t & 1;
+        const long r = r0 + (t >> 1) < R ? r0 + (t >> 1) : R - 1;
+        const float* d = rays != nullptr ? rays + NERFAIL_RAY_FLOATS * r + 8 : viewdirs + 3 * r;
+        float demb[4 * kDirQuads];
+        encode_dir(d[0], d[1], d[2], h, demb);
+#pragma unroll
+        for (int s = 0; s < 4 * kDirQuads; ++s) {
+            const int c = enc_channel(s, h, 4);
+            if (c >= 0) enc[t >> 1][c] = demb[s];
+        }
+    }
+    const int i = t % WV, half = t / WV;
+    float w[kDirCh];
+#pragma unroll
+    for (int m = 0; m < kDirCh; ++m) {
+        w[m] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 4 * kDirQuads; ++s)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)                                    // the k-step and lane half that multiply column W + m
+                if (weight_column(-1, 0, 2 * WV, L.NT, 16 * L.NT + s, h) == 2 * WV + m)
+                    w[m] = x3f_weight_at(packed, L, D + 1, L.NT / 2, i, 16 * L.NT + s, h);
+    }
+    const float bc = cst[D * kPiece + bias_index(i)];
+    __syncthreads();
+    for (int rr = half * (kVbRays / 2); rr < (half + 1) * (kVbRays / 2) && r0 + rr < R; ++rr) {
+        double acc = (double)bc;
+#pragma unroll
+        for (int m = 0; m < kDirCh; ++m) acc += (double)w[m] * (double)enc[rr][m];
+        vb[(r0 + rr) * WV + bias_index(i)] = (float)acc;
+    }
 }
 
 // ---- the weight ring of one workgroup (the x3 counterpart of WRing in mlp_lds.hip; every member but f1 / f2 / voff / rl / rdp
@@ -449,13 +506,30 @@ __device__ __forceinline__ void x3_part(X3Ring& st, f32x4 (&out)[X3Cfg::OT][2], 
 
 // FOLD: `img` is the folded image (make_x3f_layout) - no feature layer; the views layer reads relu(h) directly, and the
 // constant area comes from behind the image's stream instead of the f32 image.
-template <int NT, int SKIP, bool FOLD>
-__global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, const void* img, int img_pieces) {
+//
+// RAYBIAS (FOLD only; a call whose 32-sample tiles each lie inside one ray: samples_per_ray % 32 == 0): the direction part of the
+// views layer is the same 128-vector for every sample of a ray, so it is not computed here at all. `vb` [rays][W/2] holds
+// bc + Wv[:, W:] enc(d) per ray in bias piece order (x3_viewbias_kernel); a tile's row takes the place of bias piece D, which the
+// hooks of layer D - 1 hand to the views layer's output tiles. No direction encoding, no parked direction operands, no
+// direction part: the stream ends one ring group earlier (that part is the image's last group).
+// One kernel text: the last argument is X3RayBias in the RAYBIAS form and an empty struct in the plain forms, whose
+// instructions are then those of a kernel without it (a shared __device__ body behind two kernels is not: the plain forms come
+// out with another register allocation).
+struct X3NoRayBias {};
+struct X3RayBias { const float* vb; };
+template <int NT, int SKIP, bool FOLD, class RB>
+__global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, const void* img, int img_pieces, RB rb) {
+    constexpr bool RAYBIAS = !__is_same(RB, X3NoRayBias);
+    const float* vb = nullptr;
+    if constexpr (RAYBIAS) vb = rb.vb;
     static_assert(NT == X3Cfg::NT, "W = 256 only");
+    static_assert(FOLD || !RAYBIAS, "the per-ray view bias replaces the COMPOSED bias bc");
     using C = X3Cfg;
     constexpr int OT = C::OT, OTV = OT / 2;
-    // ONE object (see nerf_mlp_fwd_lds_kernel): ring first, then constants, then the parked encoding operands
-    __shared__ __attribute__((aligned(16))) float smem[C::RP * kPiece + C::kConstMax + C::kParkFloats];
+    constexpr int kParkQ = RAYBIAS ? kEmbQuads : C::kParkQuads;         // parked quads per wave
+    // ONE object (see nerf_mlp_fwd_lds_kernel): ring first, then constants, then (RAYBIAS) the four waves' view-bias rows,
+    // then the parked encoding operands
+    __shared__ __attribute__((aligned(16))) float smem[C::RP * kPiece + C::kConstMax + (RAYBIAS ? C::kParkFloatsRB : C::kParkFloats)];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, j = lane & 31;                             // the encoding's (half, sample) of this lane
@@ -463,7 +537,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
     const MlpLayout& L = a.lay;
     float* const ring0 = smem;
     float* const cst = smem + C::RP * kPiece;
-    float* const park_w = cst + C::kConstMax + wave * (64 * 4 * C::kParkQuads);
+    float* const park_w = cst + C::kConstMax + (RAYBIAS ? 4 * C::kRowFloats : 0) + wave * (64 * 4 * kParkQ);
     float* const park = park_w + lane * 4;
     // the parked operand of (half n, lane group g) is the encoding lane 16n + c + 32(g & 1) wrote (pack_x3_kernel's k map)
     const float* const park_rd = park_w + (c + 32 * (g & 1)) * 4 + (g >> 1) * 256;
@@ -478,10 +552,20 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
     int lane_off = x3_lane_off(g);
     asm volatile("" : "+v"(lane_off));                                   // added once: the tile parts stay immediates
     const float* const cst_g = cst + lane_off;
+    // the heads' weights + the lane part. RAYBIAS: formed from cst_g where a head runs (the offset opaque: not hoisted), so
+    // that neither lane_off nor the two sums are lane registers live across the round (<8,2> has none to spare)
+    auto head_w = [&](unsigned off) {
+        int o = (int)(off - L.b_off[0]);
+        asm volatile("" : "+s"(o));
+        return cst_g + o;
+    };
 
     X3Ring st;
     st.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(img), 0, img_pieces * (kPiece * 4), 0x00020000);
-    st.start(ring0, lane, wave, img_pieces);
+    st.start(ring0, lane, wave, RAYBIAS ? img_pieces - C::GP : img_pieces);   // RAYBIAS: the direction group is never streamed
+    // RAYBIAS: this wave's row slot, in floats from cst (wave-uniform), and the tiles of a ray
+    int row_off = C::kConstMax + wave * C::kRowFloats;
+    const int tpr = a.spr >> 5;
 
     f32x4 P[OT][2], Q[OT][2];
     // dst[i] = bias of layer l, tile i (f32, in AGPRs), as side work of two tile-steps: the LDS read into the first sample
@@ -489,15 +573,17 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
     // t0 + 1 (when the read has landed: a copy right behind it would wait for it). Those gaps are empty in tile-steps 8..15
     // of a step, where the layers' bias tiles sit, and hold two split instructions at most below (the views layer's);
     // X3Ring::side uses gaps 0, 4, 7, 9 and shares gap 9 only in the interval's last tile-step (t = 5 mod 8: no bias copy).
-    auto bias_tile = [&](f32x4 (&dst)[OT][2], int l, int i, int t0, int t, int k) {
+    // (bias_tile_at: the piece given by its offset in floats from cst - a bias piece, or a view-bias row slot)
+    auto bias_tile_at = [&](f32x4 (&dst)[OT][2], int off, int i, int t0, int t, int k) {
         if (t == t0 && k == 10) {
-            dst[i][0] = lds_read4(cst_g + l * kPiece + x3_tile_off(i));
+            dst[i][0] = lds_read4(cst_g + off + x3_tile_off(i));
         }
         if (t == t0 + 1 && k == 11) {
             dst[i][1] = dst[i][0];
             asm volatile("" : "+a"(dst[i][1]));
         }
     };
+    auto bias_tile = [&](f32x4 (&dst)[OT][2], int l, int i, int t0, int t, int k) { bias_tile_at(dst, l * kPiece, i, t0, t, k); };
     // (outside the stream: a whole tile at once)
     auto bias_tile_now = [&](f32x4 (&dst)[OT][2], int l, int i) {
         dst[i][0] = lds_read4(cst_g + l * kPiece + x3_tile_off(i));
@@ -516,7 +602,21 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
         int jj = j;
         asm volatile("" : "+v"(jj));
         const long sraw = (long)tile * 32 + jj;
-        const long s = sraw < a.M ? sraw : a.M - 1;
+        const long s = RAYBIAS || sraw < a.M ? sraw : a.M - 1;              // RAYBIAS: M is a multiple of 32, no partial tile
+        if constexpr (RAYBIAS) {
+            // The tile's view-bias row (ray tile / tpr, wave-uniform), 512 bytes, by ONE LDS-DMA of lanes 0..31 into this wave's
+            // slot. It joins the ring's vmcnt queue as an entry OLDER than every ring DMA of this round: a boundary lets at
+            // most (S - 2) * GPW younger DMAs stay in flight, and the wave issues GPW per ring group, so the round's THIRD
+            // boundary (lds_wait_vmcnt in X3Ring::boundary) has seen the row land. Its first reader is a hook of layer D - 1,
+            // behind layer 0's four groups at the least; writer and readers are this wave alone, no barrier is involved. The
+            // slot's last reads of the round before (the same hooks) were waited for by every boundary since (lgkmcnt(0)).
+            int tp = tpr;
+            asm volatile("" : "+s"(tp));                                 // opaque per round, as spr below
+            const int row = __builtin_amdgcn_readfirstlane(tile / tp);
+            const __amdgpu_buffer_rsrc_t rrow = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float*>(vb) + (long)row * C::kRowFloats, 0, C::kRowFloats * 4, 0x00020000);
+            if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rrow, (lds_void_t*)(cst + row_off), 16, st.voff, 0, 0, 0);
+        }
         {
             float emb[4 * kEmbQuads], demb[4 * kDirQuads];
             int hh = h;
@@ -524,17 +624,19 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
             if constexpr (FOLD) {       // spr opaque per round: its reciprocal (s / spr) is then formed here, not kept live (a spill)
                 MlpArgs ar = a;
                 asm volatile("" : "+s"(ar.spr));
-                encode_sample(ar, s, hh, emb, demb);
+                if constexpr (RAYBIAS) encode_sample_pts(ar, s, hh, emb); else encode_sample(ar, s, hh, emb, demb);
             } else {
                 encode_sample(a, s, hh, emb, demb);
             }
 #pragma unroll
             for (int k = 0; k < kEmbQuads; ++k)
                 *reinterpret_cast<f32x4*>(park + k * 256) = (f32x4){emb[4 * k], emb[4 * k + 1], emb[4 * k + 2], emb[4 * k + 3]};
+            if constexpr (!RAYBIAS) {
 #pragma unroll
             for (int k = 0; k < kDirQuads; ++k)
                 *reinterpret_cast<f32x4*>(park + (kEmbQuads + k) * 256) =
                     (f32x4){demb[4 * k], demb[4 * k + 1], demb[4 * k + 2], demb[4 * k + 3]};
+            }
         }
         // k32 step u of a parked encoding from quad q0 on: element 2p + e is k-step 4Q + 2(p & 1) + e of quad
         // Q = q0 + 4u + (g >> 1) + 2(p >> 1)
@@ -563,13 +665,28 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
             if (may_skip && l == L.skip + 1) x3_part<OT, kEmbQuads / 4, false>(st, out, b_park(0), no_hook);   // cat([input_pts, h])
             // input tiles 2u, 2u+1 are last read by the split of step u (during step u-1): dead from step u on
             int lb = l + 1;                                                 // the bias piece handed to the dying input tiles
+            if constexpr (RAYBIAS) {
+                // as an offset from cst: layer D - 1 hands on the tile's view-bias row instead of piece D. (The row is half a
+                // piece: the upper tiles read what lies behind it, inside the LDS object, and are rewritten with layer 0's
+                // bias during the views layer before anything reads them - as piece D's zero half is in the plain form.)
+                // The select is two scalar instructions the compiler does not see into: written as `lb == L.D ? row_off : ...`
+                // the <8,0> and <8,2> instantiations spill some 1500 VGPRs.
+                lb *= kPiece;
+                asm volatile("s_cmp_eq_u32 %1, %2\n\ts_cselect_b32 %0, %3, %0" : "+s"(lb) : "s"(l + 1), "s"(L.D), "s"(row_off) : "scc");
+                x3_part<OT, NT, true>(st, out, b_acc(in), [&](int u, int t, int k) {
+                    if (u > 0) { bias_tile_at(in, lb, 2 * u - 2, 8, t, k); bias_tile_at(in, lb, 2 * u - 1, 9, t, k); }
+                    if (u == NT - 1) { bias_tile_at(in, lb, 2 * u, 10, t, k); bias_tile_at(in, lb, 2 * u + 1, 11, t, k); }
+                });
+            } else {
             if constexpr (FOLD) asm volatile("" : "+s"(lb));                // kept scalar: as a VGPR induction address it spills
             x3_part<OT, NT, true>(st, out, b_acc(in), [&](int u, int t, int k) {
                 if (u > 0) { bias_tile(in, lb, 2 * u - 2, 8, t, k); bias_tile(in, lb, 2 * u - 1, 9, t, k); }
                 if (u == NT - 1) { bias_tile(in, lb, 2 * u, 10, t, k); bias_tile(in, lb, 2 * u + 1, 11, t, k); }
             });
+            }
             if (FOLD && may_be_last && l == L.D - 1) {                      // folded: `out` is the last pts activation
-                x3_head<OT>(out, c_alpha + lane_off, alpha);
+                if constexpr (RAYBIAS) x3_head<OT>(out, head_w(L.alpha_off), alpha);
+                else x3_head<OT>(out, c_alpha + lane_off, alpha);
                 alpha[0] += c_alpha[NT * 32];
                 alpha[1] += c_alpha[NT * 32];
             }
@@ -586,8 +703,9 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
             // P's other tiles, dead, receive their half of the NEXT tile's layer 0 bias, the first half follows the head.
             // (alpha_linear ran on relu(Q) behind layer D - 1, inside the loop: behind the loop the kernel spills VGPRs)
             x3_part<OTV, NT, true>(st, P, b_acc(Q), [&](int u, int t, int k) { bias_tile(P, 0, OTV + u, 2, t, k); });
-            x3_part<OTV, kDirQuads / 4, false>(st, P, b_park(kEmbQuads), no_hook);
-            x3_head3<OTV>(P, c_rgb + lane_off, OTV * 16, rgb);
+            if constexpr (!RAYBIAS) x3_part<OTV, kDirQuads / 4, false>(st, P, b_park(kEmbQuads), no_hook);   // RAYBIAS: in the bias
+            if constexpr (RAYBIAS) x3_head3<OTV>(P, head_w(L.rgb_off), OTV * 16, rgb);
+            else x3_head3<OTV>(P, c_rgb + lane_off, OTV * 16, rgb);
 #pragma unroll
             for (int t = 0; t < OTV; ++t) bias_tile_now(P, 0, t);
         } else {
@@ -605,7 +723,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_fwd_x3_kernel(MlpArgs a, cons
         int je = 16 * n + c;
         asm volatile("" : "+v"(je));
         const long sout = (long)tile * 32 + je;
-        if (g < 2 && sout < a.M && tile_own < ntiles)
+        if (g < 2 && (RAYBIAS || sout < a.M) && tile_own < ntiles)
             reinterpret_cast<float4*>(a.raw)[sout] = make_float4((n ? rgb[1][0] : rgb[0][0]) + c_rgb[3 * OTV * 16 + 0],
                                                                  (n ? rgb[1][1] : rgb[0][1]) + c_rgb[3 * OTV * 16 + 1],
                                                                  (n ? rgb[1][2] : rgb[0][2]) + c_rgb[3 * OTV * 16 + 2],
@@ -661,9 +779,9 @@ template <bool FOLD>
 static void launch_x3(const MlpArgs& a, const void* img, int pieces, hipStream_t s) {
     const dim3 grid(mlp_grid_blocks((a.M + 31) / 32)), block(256);      // persistent: one 4-wave workgroup per CU
     const int skip_layer = a.lay.skip >= 0 ? a.lay.skip + 1 : -1;
-    if (skip_layer < 0) nerf_mlp_fwd_x3_kernel<8, 0, FOLD><<<grid, block, 0, s>>>(a, img, pieces);
-    else if (skip_layer & 1) nerf_mlp_fwd_x3_kernel<8, 1, FOLD><<<grid, block, 0, s>>>(a, img, pieces);
-    else nerf_mlp_fwd_x3_kernel<8, 2, FOLD><<<grid, block, 0, s>>>(a, img, pieces);
+    if (skip_layer < 0) nerf_mlp_fwd_x3_kernel<8, 0, FOLD, X3NoRayBias><<<grid, block, 0, s>>>(a, img, pieces, X3NoRayBias());
+    else if (skip_layer & 1) nerf_mlp_fwd_x3_kernel<8, 1, FOLD, X3NoRayBias><<<grid, block, 0, s>>>(a, img, pieces, X3NoRayBias());
+    else nerf_mlp_fwd_x3_kernel<8, 2, FOLD, X3NoRayBias><<<grid, block, 0, s>>>(a, img, pieces, X3NoRayBias());
 }
 
 // fold: `img` is the folded image of nerfail_mlp_pack_x3f
@@ -674,6 +792,45 @@ int launch_mlp_x3(const MlpArgs& a, const void* img, int W, bool fold, hipStream
     if (fold) launch_x3<true>(a, img, (int)X.pieces, s);
     else launch_x3<false>(a, img, (int)X.pieces, s);
     NF_LAUNCHED("nerf_mlp_fwd_x3_kernel");
+    return NERFAIL_OK;
+}
+
+// ---- the RAYBIAS form: the folded image, whole 32-sample tiles inside one ray
+bool mlp_x3_raybias_covers(const MlpLayout& L, int W, int spr) {
+    X3Layout X;
+    return mlp_x3_covers(L, W) && make_x3f_layout(L, W, X) && X.pieces > (unsigned)(X3Cfg::S * X3Cfg::GP) && spr > 0 && spr % 32 == 0;
+}
+
+// vb [R][W/2] from the directions of `rays` [R,11] or, when that is NULL, `viewdirs` [R,3]; `img` is the folded image
+int launch_mlp_x3_viewbias(const float* packed, const void* img, const MlpLayout& L, int W, const float* rays, const float* viewdirs,
+                           long R, float* vb, hipStream_t s) {
+    X3Layout X;
+    if (!mlp_x3_covers(L, W) || !make_x3f_layout(L, W, X)) { set_error("x3_viewbias_kernel: shape not covered (W = 256, even D <= 8)"); return NERFAIL_EINVAL; }
+    if (R <= 0) return NERFAIL_OK;
+    if ((R + kVbRays - 1) / kVbRays > 0x7fffffffL) { set_error("x3_viewbias_kernel: too many rays"); return NERFAIL_EINVAL; }
+    const float* cst = static_cast<const float*>(img) + (size_t)X.pieces * kPiece;
+    x3_viewbias_kernel<<<dim3((unsigned)((R + kVbRays - 1) / kVbRays)), dim3(W), 0, s>>>(packed, L, cst, rays, viewdirs, R, vb);
+    NF_LAUNCHED("x3_viewbias_kernel");
+    return NERFAIL_OK;
+}
+
+// the view bias of the call's rays into `vb`, then the RAYBIAS kernel
+int launch_mlp_x3_raybias(const MlpArgs& a, const void* img, int W, float* vb, hipStream_t s) {
+    X3Layout X;
+    if (!mlp_x3_raybias_covers(a.lay, W, a.spr) || !make_x3f_layout(a.lay, W, X) || a.M % a.spr != 0 || a.xemb != nullptr) {
+        set_error("nerf_mlp_fwd_x3_kernel (RAYBIAS): needs the folded image of a covered shape (W = 256, even D <= 8), rays or points with view directions, and samples_per_ray a multiple of 32");
+        return NERFAIL_EINVAL;
+    }
+    if (a.M >= (1L << 36)) { set_error("nerfail_mlp_fwd: M must be below 2^36 samples per call"); return NERFAIL_EINVAL; }
+    const int rc = launch_mlp_x3_viewbias(a.packed, img, a.lay, W, a.rays, a.viewdirs, a.M / a.spr, vb, s);
+    if (rc != NERFAIL_OK) return rc;
+    const dim3 grid(mlp_grid_blocks((a.M + 31) / 32)), block(256);      // persistent: one 4-wave workgroup per CU
+    const int skip_layer = a.lay.skip >= 0 ? a.lay.skip + 1 : -1;
+    const X3RayBias rb = {vb};
+    if (skip_layer < 0) nerf_mlp_fwd_x3_kernel<8, 0, true, X3RayBias><<<grid, block, 0, s>>>(a, img, (int)X.pieces, rb);
+    else if (skip_layer & 1) nerf_mlp_fwd_x3_kernel<8, 1, true, X3RayBias><<<grid, block, 0, s>>>(a, img, (int)X.pieces, rb);
+    else nerf_mlp_fwd_x3_kernel<8, 2, true, X3RayBias><<<grid, block, 0, s>>>(a, img, (int)X.pieces, rb);
+    NF_LAUNCHED("nerf_mlp_fwd_x3_kernel (RAYBIAS)");
     return NERFAIL_OK;
 }
 

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from .optim import Adam, decayed_lrate  # noqa: F401
 from .run_nerf_helpers import (NeRF, Embedder, get_embedder, get_rays, get_rays_np, img2mse, mse2psnr, to8b,  # noqa: F401
-                               sample_pdf, linspace01, mlp_forward, _cuda, _k4, _c2w12)
+                               sample_pdf, linspace01, mlp_forward, per_ray_view_bias, _cuda, _k4, _c2w12)
 
 np.random.seed(0)      # RN:23
 DEBUG = False
@@ -354,9 +354,10 @@ def _render_rays_pipeline(rays, network_fn, network_fine, user_query, N_samples,
             if p is None:
                 return _train.mlp_fwd_train_rays(fn, rays, z, acts=a_)
             return _train.mlp_fwd_train(fn, p, viewdirs, acts=a_)
-        if p is None:
-            return _mlp_rays(fn, rays, z), None                        # points formed in the kernel
-        return _mlp_points(fn, p, viewdirs), None                      # fused encode + MLP, nothing materialised
+        with per_ray_view_bias():                                          # a render: the view-direction term once per ray
+            if p is None:
+                return _mlp_rays(fn, rays, z), None                        # points formed in the kernel
+            return _mlp_points(fn, p, viewdirs), None                      # fused encode + MLP, nothing materialised
 
     # training: the saved activations of the coarse and the fine pass share ONE buffer (coarse tiles first), so that the
     # backward walks both networks in one launch per kernel

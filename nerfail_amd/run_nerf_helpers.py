@@ -281,6 +281,21 @@ class NeRF(nn.Module):
         return mlp_forward(self, raw, embedded=flat).reshape(x.shape[:-1] + (4,))
 
 
+class per_ray_view_bias:
+    """Context of a caller that accepts the per-ray view-bias form of the folded bf16x3 kernel for the inference calls it makes
+    (the renderer does, run_nerf._render_rays_pipeline): density bitwise the plain folded kernel's, colour f32-accurate but not
+    its bits. Outside such a context mlp_forward keeps the plain kernels: the rays, points and embedded forms of one batch
+    then give the same bits."""
+    depth = 0
+
+    def __enter__(self):
+        per_ray_view_bias.depth += 1
+        return self
+
+    def __exit__(self, *exc):
+        per_ray_view_bias.depth -= 1
+
+
 def mlp_forward(net, raw, pts=None, viewdirs=None, embedded=None, rays=None, z_vals=None, acts=None):
     """The ONE choice of forward entry point. Input, one of: pts [R,N,3] + viewdirs [R,3] | embedded [M,90] | packed rays
     [R,11] + z_vals [R,N] (the points o + d z are formed inside the kernel). Fills and returns `raw`. With `acts` (the
@@ -289,6 +304,9 @@ def mlp_forward(net, raw, pts=None, viewdirs=None, embedded=None, rays=None, z_v
       net.precision == 'f16x3', points only  nerfail_mlp_fwd_f16 / nerfail_mlp_fwd_f16_train on the f32 and the f16 image
       inference                              nerfail_mlp_fwd[_embedded|_rays]_x3f on the folded bf16x3 image if there is one,
                                              else ..._x3 on the unfolded one, which runs exact f32 when that is None too
+                                             (inside per_ray_view_bias(), rays / points on the folded image with
+                                             N % 32 == 0: the ..._x3f_raybias entry points - the view-direction term once
+                                             per ray - unless NERFAIL_X3_RAYBIAS=0)
       training (points, rays)                nerfail_mlp_fwd_train / nerfail_mlp_fwd_rays on the f32 image, after the joint
                                              pack: the backward needs the transposed image of the same weights"""
     lib, train = _lib.load(), acts is not None
@@ -307,6 +325,17 @@ def mlp_forward(net, raw, pts=None, viewdirs=None, embedded=None, rays=None, z_v
     else:
         fold, img = net.x3_image()
         name, images = 'nerfail_mlp_fwd%s_x3%s' % (form, 'f' if fold else ''), [net.packed(), img]
+        # a caller inside per_ray_view_bias(), folded image, rays or points with view directions, whole 32-sample tiles per ray:
+        # the view-direction term once per ray (nerfail_mlp_x3f_raybias_floats says whether the library runs that form for
+        # this call, and how large vb is)
+        n_rays = 0 if form == '_embedded' else (inputs[2] if form == '_rays' else inputs[2] // inputs[3])
+        n_vb = lib.nerfail_mlp_x3f_raybias_floats(net.D, net.W, net._skip(), n_rays, inputs[-1]) \
+            if fold and n_rays and per_ray_view_bias.depth > 0 else 0
+        if n_vb:
+            vb = torch.empty((n_vb,), dtype=torch.float32, device=raw.device)     # a temporary of the call, like raw
+            _lib.check(getattr(lib, name + '_raybias')(*[_lib.dev(i) for i in images], net.D, net.W, net._skip(), *inputs,
+                                                       _lib.dev(raw), _lib.dev(vb), _lib.stream()))
+            return raw
     tail = [_lib.dev(acts)] if train or form == '_rays' else []       # the rays entry points take acts (or NULL) always
     _lib.check(getattr(lib, name)(*[_lib.dev(i) for i in images], net.D, net.W, net._skip(), *inputs, _lib.dev(raw), *tail,
                                   _lib.stream()))
