@@ -594,6 +594,64 @@ int nerfail_copy_if(const int32_t* flag, const float* src, float* dst, int64_t n
 /* float32 -> uint8 as cv2.imwrite stores a float image (AS:401-402): clamp to [0, 255], round half to even; NaN -> 0. */
 int nerfail_export_u8(const float* src, int64_t n, unsigned char* dst, void* stream);
 
+/* ------------------------------------------------------------------ Attack evaluation (eval revision 1) -- */
+
+/* What test_for_inception (model_test.py = MT, MyDataset.py = MD) measures after an attack, on the device: the distances between
+ * every attacked view and its original (MT:256-266), each view's prediction and cross entropy (MT:292-295) and the set-level
+ * record the report is made from (MT:268-278, 298-299, 341-348, 355-399). Like the section above this one only ADDS entry points:
+ * NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays 15, and the additions are announced by nerfail_eval_revision() = 1.
+ *
+ * Image formats of one side of an (attacked, original) pair; P = pixels of a view:
+ *   U8C4   [P,4] uint8    what cv2.imread(..., IMREAD_UNCHANGED) returns for an RGBA PNG         base 4-byte aligned
+ *   U8C3   [P,3] uint8    a 3-channel file, e.g. a rendered view                                  base 4-byte aligned
+ *   F32C4  [P,4] float32  x_rgba of gauss_net, unrounded                                          base 16-byte aligned
+ *   FLAT   [P] float32    P elements without alpha logic (an image that already is a classifier  base 4-byte aligned
+ *                         input, e.g. after a resize); pairs only with FLAT
+ * 4-channel sides get the white background of MT:237-254 / MD:98-105: rgb where alpha > 0, else 255 (a NaN alpha gives white).
+ * The channel order is left as stored. A view then has n = 3 P elements (FLAT: n = P). */
+#define NERFAIL_EVAL_U8C4 0
+#define NERFAIL_EVAL_U8C3 1
+#define NERFAIL_EVAL_F32C4 2
+#define NERFAIL_EVAL_FLAT 3
+#define NERFAIL_EVAL_VIEW_DOUBLES 6
+#define NERFAIL_EVAL_RECORD_DOUBLES (16 + NERFAIL_ATTACK_MAX_CLASSES)
+int nerfail_eval_revision(void);
+
+/* MT:256-266 for n_views pairs. a_views_host / o_views_host: HOST arrays of n_views device pointers, one image each (resident
+ * views are separate allocations); at most 16 pairs travel per launch, the function loops. Per element d = |a - o| is formed in
+ * float32 (one rounded subtraction, as the reference's float tensors). rows: float64 [n_views, 6] =
+ *   {max d, min d, sum d, sum d^2, count(d != 0), n}
+ * with the sums formed in double. A NaN element makes max, min and both sums of ITS view NaN and counts as non-zero.
+ * Two stages without atomics: per-workgroup partials in scratch (nerfail_eval_scratch_bytes() bytes, contents unspecified on
+ * return), then one wave per view adds them in a fixed order. The element -> lane map and every order depend on n alone: the
+ * same bits on every run, for every format holding the same values, and whatever other views share the launch.
+ * cla_in (optional, NULL to skip; not with FLAT): float32 [n_views, 3, P], the attacked view after the white background as a
+ * planar (NCHW) image - what MyCNN consumes - written in the same pass. No byte at or beyond the end of a view is read.
+ * A wrong alignment, an unknown format, FLAT paired with another format or cla_in with FLAT is NERFAIL_EINVAL before any launch;
+ * n_views == 0 or P == 0 is a no-op. */
+size_t nerfail_eval_scratch_bytes(void);
+int nerfail_eval_view_metrics(const void* const* a_views_host, int a_format, const void* const* o_views_host, int o_format,
+                              int n_views, int64_t P, void* scratch, double* rows, float* cla_in, void* stream);
+
+/* MT:292-295. logits [B,C] float32, 1 <= C <= 32, 0 <= label < C -> pred int32 [B], ce float64 [B], with the definitions of
+ * nerfail_attack_logit_stats (one shared device function): the FIRST maximum is the prediction; CE = log-sum-exp with the maximum
+ * subtracted, minus the label's logit, in double. A row that holds a NaN predicts -1 and has CE = NaN. */
+int nerfail_eval_logit_stats(const float* logits, int B, int C, int label, int32_t* pred, double* ce, void* stream);
+
+/* MT:268-278, 298-299, 341-348: folds the rows, predictions and CEs of a batch of B views into the set record, float64
+ * [NERFAIL_EVAL_RECORD_DOUBLES], which the caller zeroes before the first batch. One lane, plain loads and stores: batches
+ * accumulate in stream order.
+ *   [0] views so far     [1] e max = max of the views' maxima     [2] e min = min of the views' minima
+ *   [3] sum of the views' means (sum d / n)       [4] sum of sqrt(sum d^2)       [5] sum of the non-zero counts
+ *   [6] PSNR min         [7] PSNR max             [8] PSNR sum                   [9] CE sum
+ *   [10] views without a prediction (pred outside 0..C-1)         [11] sum of n  [12..15] unused, left alone
+ *   [16 + k] views predicted as class k
+ * PSNR of a view = 20 log10(255 / rmse), rmse = sqrt(sum d^2 / n), rmse == 0 replaced by DBL_EPSILON (get_psnr, MT:26-39):
+ * two equal images have PSNR 361.20199909921956, stored as that constant.
+ * record[0] == 0 marks the first view: [1], [2], [6], [7] are then SET from it, not compared with the zeroed record. A NaN that
+ * enters a maximum or minimum stays (torch.max / torch.min). The report divides [3], [4], [5], [8], [9] by [0] on the host. */
+int nerfail_eval_fold(const double* rows, const int32_t* pred, const double* ce, int B, int C, double* record, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

@@ -14,6 +14,7 @@ from torch import nn
 
 from . import _lib
 from . import ops  # noqa: F401  (registers torch.ops.nerfail_mi.*)
+from ._resize import resize
 from .run_nerf_helpers import _cuda
 
 
@@ -589,12 +590,7 @@ class gauss_net(nn.Module):
 
     # -- resize of the cold tail: torchvision if present (as the reference), else the same bilinear op in torch
     def _resize(self, x, size):
-        try:
-            from torchvision.transforms import Resize
-            return Resize([size, size])(x)
-        except ImportError:
-            return torch.nn.functional.interpolate(x, size=(size, size), mode='bilinear', align_corners=False,
-                                                   antialias=True)
+        return resize(x, size)
 
     def _mm(self):
         if self._eps_minmax is None:

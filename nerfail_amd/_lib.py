@@ -13,6 +13,10 @@ LIB_PATH = os.environ.get('NERFAIL_HIP_LIB') or os.path.join(_HERE, 'lib', 'libn
 
 ABI_VERSION = 14
 ABI_REVISION = 15                        # additions since ABI_VERSION (nerfail_abi_revision): the NeRFail-S epoch statistics
+EVAL_REVISION = 1                        # nerfail_eval_revision: the attack-evaluation entry points (model_test)
+EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
+EVAL_VIEW_DOUBLES = 6                    # NERFAIL_EVAL_VIEW_DOUBLES: one view's row
+EVAL_RECORD_DOUBLES = 16 + 32            # NERFAIL_EVAL_RECORD_DOUBLES: the set record of nerfail_eval_fold
 ATTACK_ROW_FLOATS = 16                   # NERFAIL_ATTACK_ROW_FLOATS: the stats row and the epoch record of attack.nerfail_s
 MAX_DEPTH = 16
 DW_BF16X3, DW_ACCUMULATE = 1, 2          # flags of nerfail_mlp_bwd_weights
@@ -159,6 +163,11 @@ SIGNATURES = {
     'nerfail_attack_epoch_close': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
     'nerfail_copy_if': (c_i, [c_p, c_p, c_p, c_i64, c_p]),
     'nerfail_export_u8': (c_i, [c_p, c_i64, c_p, c_p]),
+    'nerfail_eval_revision': (c_i, []),
+    'nerfail_eval_scratch_bytes': (ctypes.c_size_t, []),
+    'nerfail_eval_view_metrics': (c_i, [c_p, c_i, c_p, c_i, c_i, c_i64, c_p, c_p, c_p, c_p]),
+    'nerfail_eval_logit_stats': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'nerfail_eval_fold': (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -211,6 +220,9 @@ def load():
     if v != ABI_VERSION or lib.nerfail_abi_revision() != ABI_REVISION:
         raise RuntimeError('nerfail_amd: ABI version %d revision %d, expected %d / %d - rebuild the library'
                            % (v, lib.nerfail_abi_revision(), ABI_VERSION, ABI_REVISION))
+    if lib.nerfail_eval_revision() != EVAL_REVISION:
+        raise RuntimeError('nerfail_amd: attack-evaluation revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_eval_revision(), EVAL_REVISION))
     _lib = lib
     return lib
 

@@ -27,11 +27,6 @@ __device__ __forceinline__ void pair_put(float* p, double v) {
     p[0] = hi;
     p[1] = (isfinite(hi) ? (float)(v - (double)hi) : 0.f);
 }
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- AS:319-330: per-view CE and first-maximum argmax of both logit sets, one wave. Lane l takes views l, l + 64, ...
 // (an attack batch is 8 views; the export pass a few hundred at most).
@@ -43,20 +38,9 @@ __global__ __launch_bounds__(64) void attack_logit_stats_kernel(const float* __r
     for (int b = lane; b < B; b += 64) {
 #pragma unroll
         for (int which = 0; which < 2; ++which) {
-            const float* x = (which == 0 ? ori_cla : cla) + (long)b * C;
-            float m = x[0];
-            int arg = 0;
-            bool nan = (m != m);
-            for (int c = 1; c < C; ++c) {
-                const float v = x[c];
-                nan = nan || (v != v);
-                if (v > m) { m = v; arg = c; }                  // strict: the first maximum stays
-            }
-            double s = 0.0;
-            for (int c = 0; c < C; ++c) s += exp((double)x[c] - (double)m);
-            const double lse = (double)m + log(s);
-            ce[which] += nan ? (double)NAN : (lse - (double)x[label]);
-            ok[which] += (!nan && arg == label) ? 1.f : 0.f;
+            const LogitRow r = logit_row_stats((which == 0 ? ori_cla : cla) + (long)b * C, C, label);
+            ce[which] += r.ce;
+            ok[which] += (r.arg == label) ? 1.f : 0.f;
         }
     }
     const double s0 = wave_sum_f64(ce[0]), s1 = wave_sum_f64(ce[1]);

@@ -56,6 +56,11 @@ __device__ __forceinline__ float wave_min(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 // inclusive product scan across the 64 lanes
 __device__ __forceinline__ float wave_scan_mul(float v, int lane) {
 #pragma unroll
@@ -145,6 +150,31 @@ struct SinCosBands {
         return __uint_as_float(__float_as_uint(v) ^ ((unsigned)(k & 2) << 30));
     }
 };
+
+// One row of C float32 logits (attack_NeRFail_S.py:319-330, model_test.py:292-295): arg = the FIRST maximum, ce = log-sum-exp
+// with the maximum subtracted, minus the label's logit, in double from the float32 values. A row that holds a NaN has arg = -1
+// and ce = NaN. Shared by nerfail_attack_logit_stats and nerfail_eval_logit_stats: one definition of "prediction" and "CE".
+struct LogitRow {
+    int arg;
+    double ce;
+};
+__device__ __forceinline__ LogitRow logit_row_stats(const float* __restrict__ x, int C, int label) {
+    float m = x[0];
+    int arg = 0;
+    bool nan = (m != m);
+    for (int c = 1; c < C; ++c) {
+        const float v = x[c];
+        nan = nan || (v != v);
+        if (v > m) { m = v; arg = c; }                  // strict: the first maximum stays
+    }
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += exp((double)x[c] - (double)m);
+    const double lse = (double)m + log(s);
+    LogitRow r;
+    r.arg = nan ? -1 : arg;
+    r.ce = nan ? (double)NAN : (lse - (double)x[label]);
+    return r;
+}
 
 // pts = o + d*z with the reference's rounding (multiply, then add; no FMA): RN:381
 __device__ __forceinline__ float mul_add_rn(float a, float b, float c) { return __fadd_rn(__fmul_rn(a, b), c); }

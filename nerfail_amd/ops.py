@@ -658,3 +658,86 @@ def _(src):
 
 
 ATTACK_STATS_OPS = ('attack_logit_stats', 'img_sqerr', 'img_sqerr_grad_add', 'attack_epoch_close', 'copy_if', 'export_u8')
+
+
+# ----------------------------------------------------------------------------------------------- attack evaluation (model_test.py:226-348; eval revision 1)
+_EVAL_LAYOUT = {_lib.EVAL_U8C4: (torch.uint8, 4), _lib.EVAL_U8C3: (torch.uint8, 3), _lib.EVAL_F32C4: (torch.float32, 4),
+                _lib.EVAL_FLAT: (torch.float32, 1)}
+
+
+def _eval_pixels(views, fmt, name):
+    """P of a list of views in one NERFAIL_EVAL_* format (every view: same device, dtype and size, contiguous)."""
+    if fmt not in _EVAL_LAYOUT:
+        raise ValueError('%s: unknown image format %r' % (name, fmt))
+    dtype, ch = _EVAL_LAYOUT[fmt]
+    n = views[0].numel()
+    for v in views:
+        if v.dtype != dtype or not v.is_contiguous() or v.numel() != n or n % ch:
+            raise ValueError('%s: every view must be a contiguous %s tensor of one size, a multiple of %d elements' % (name, dtype, ch))
+    return n // ch
+
+
+@custom_op(NS + '::eval_view_metrics', mutates_args=(), device_types='cuda')
+def eval_view_metrics(attacked: Sequence[Tensor], a_format: int, originals: Sequence[Tensor], o_format: int,
+                      want_cla_in: bool) -> tuple[Tensor, Tensor]:
+    """(rows float64 [B,6] = {max, min, sum, sum of squares, non-zero count, n} of |attacked - original| per view,
+    cla_in float32 [B,3,P] = the attacked views on white, planar - or an empty tensor when not wanted). One view per tensor."""
+    B = len(attacked)
+    if B < 1 or len(originals) != B:
+        raise ValueError('eval_view_metrics: as many originals as attacked views, at least one')
+    P = _eval_pixels(attacked, a_format, 'attacked')
+    if _eval_pixels(originals, o_format, 'originals') != P:
+        raise ValueError('eval_view_metrics: attacked and original views differ in size')
+    lib, dev = _lib.load(), attacked[0].device
+    rows = torch.empty((B, _lib.EVAL_VIEW_DOUBLES), dtype=torch.float64, device=dev)
+    cla_in = torch.empty((B, 3, P) if want_cla_in else (0,), dtype=torch.float32, device=dev)
+    scratch = torch.empty((lib.nerfail_eval_scratch_bytes() // 8,), dtype=torch.float64, device=dev)
+    for v in list(attacked) + list(originals):
+        _lib.dev(v, 'view')
+    _chk(lib.nerfail_eval_view_metrics((_lib.c_p * B)(*[v.data_ptr() for v in attacked]), a_format,
+                                       (_lib.c_p * B)(*[v.data_ptr() for v in originals]), o_format, B, P, _lib.c_p(scratch.data_ptr()),
+                                       _lib.c_p(rows.data_ptr()), _lib.c_p(cla_in.data_ptr()) if want_cla_in else None, _s()))
+    return rows, cla_in
+
+
+@eval_view_metrics.register_fake
+def _(attacked, a_format, originals, o_format, want_cla_in):
+    B, P = len(attacked), attacked[0].numel() // _EVAL_LAYOUT[a_format][1]
+    return (attacked[0].new_empty((B, _lib.EVAL_VIEW_DOUBLES), dtype=torch.float64),
+            attacked[0].new_empty((B, 3, P) if want_cla_in else (0,), dtype=torch.float32))
+
+
+@custom_op(NS + '::eval_logit_stats', mutates_args=(), device_types='cuda')
+def eval_logit_stats(logits: Tensor, label: int) -> tuple[Tensor, Tensor]:
+    """(pred int32 [B]: the first maximum, -1 for a row holding a NaN; ce float64 [B]) of [B,C] logits."""
+    if logits.dim() != 2:
+        raise ValueError('logits must be [B,C]')
+    lg = _lib.f32c(logits)
+    pred = torch.empty((lg.shape[0],), dtype=torch.int32, device=lg.device)
+    ce = torch.empty((lg.shape[0],), dtype=torch.float64, device=lg.device)
+    _chk(_lib.load().nerfail_eval_logit_stats(_lib.dev(lg), lg.shape[0], lg.shape[1], label, _lib.dev(pred), _lib.c_p(ce.data_ptr()), _s()))
+    return pred, ce
+
+
+@eval_logit_stats.register_fake
+def _(logits, label):
+    return logits.new_empty((logits.shape[0],), dtype=torch.int32), logits.new_empty((logits.shape[0],), dtype=torch.float64)
+
+
+@custom_op(NS + '::eval_fold', mutates_args=('record',), device_types='cuda')
+def eval_fold(rows: Tensor, pred: Tensor, ce: Tensor, num_classes: int, record: Tensor) -> None:
+    """Folds one batch's rows [B,6], predictions [B] and CEs [B] into the float64 set record (zeroed before the first batch)."""
+    B = pred.numel()
+    if record.dtype != torch.float64 or record.numel() != _lib.EVAL_RECORD_DOUBLES or not record.is_contiguous():
+        raise ValueError('record must be %d contiguous float64' % _lib.EVAL_RECORD_DOUBLES)
+    if (rows.dtype != torch.float64 or tuple(rows.shape) != (B, _lib.EVAL_VIEW_DOUBLES) or not rows.is_contiguous() or pred.dtype != torch.int32
+            or ce.dtype != torch.float64 or ce.numel() != B or not pred.is_contiguous() or not ce.is_contiguous()):
+        raise ValueError('rows must be float64 [B,6], pred int32 [B], ce float64 [B], all contiguous')
+    for t in (rows, pred, ce, record):
+        if not t.is_cuda:
+            raise RuntimeError('eval_fold: a tensor is on %s: nerfail_amd runs on the MI355X only (no CPU path)' % t.device)
+    _chk(_lib.load().nerfail_eval_fold(_lib.c_p(rows.data_ptr()), _lib.dev(pred), _lib.c_p(ce.data_ptr()), B, num_classes,
+                                       _lib.c_p(record.data_ptr()), _s()))
+
+
+EVAL_OPS = ('eval_view_metrics', 'eval_logit_stats', 'eval_fold')
