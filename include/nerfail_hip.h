@@ -652,6 +652,65 @@ int nerfail_eval_logit_stats(const float* logits, int B, int C, int label, int32
  * enters a maximum or minimum stays (torch.max / torch.min). The report divides [3], [4], [5], [8], [9] by [0] on the host. */
 int nerfail_eval_fold(const double* rows, const int32_t* pred, const double* ce, int B, int C, double* record, void* stream);
 
+/* ------------------------------------------------------------------ victim training (cls revision 1) -- */
+
+/* The first stage of the reference's pipeline, model_train.py:107-193 (= MTR; MyDataset.py = MD), on the device: the batch a
+ * DataLoader would stack, the cross entropy of nn.CrossEntropyLoss() with one label per row, torch.optim.SGD's momentum step
+ * fused with the update of MyCNN's weight image, and the epoch close. Like the two sections before it this one only ADDS entry
+ * points: NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays 15, nerfail_eval_revision() stays 1, and the additions are
+ * announced by nerfail_cls_revision() = 1. No allocation, no synchronisation, no float atomics; the same bits on every run. */
+int nerfail_cls_revision(void);
+
+/* MTR:121-123 with MD:93-105: B views of a resident store, chosen by indices that live on the DEVICE (what
+ * nerfail_index_shuffle writes). images: dense uint8 [N,P,4] (NERFAIL_EVAL_U8C4: BGRA as cv2 reads an RGBA PNG; base 16-byte
+ * aligned) or [N,P,3] (NERFAIL_EVAL_U8C3; base 4-byte aligned); labels_all int32 [N]; idx int64 [B].
+ *   x       float32 [B,3,P] planar (NCHW), channel order as stored; four-channel views on the white background of MD:98-105:
+ *           rgb where alpha > 0, else 255.
+ *   labels  int32 [B] = labels_all[idx[b]].
+ * An index outside 0..N-1 writes a view of NaN and the label -1 and reads nothing of the store. A view is read with wide loads
+ * (16 bytes per lane for U8C4, the three dwords of four pixels for U8C3) between a scalar head and tail: view i of a U8C3
+ * store starts at byte 3 P i, which is not 4-byte aligned when P is odd. No byte outside the indexed views, and none at or
+ * beyond the end of the store, is read. B <= 65535; B == 0 is a no-op. */
+int nerfail_cls_batch(const void* images, int format, const int32_t* labels_all, int64_t N, int64_t P, const int64_t* idx, int B,
+                      float* x, int32_t* labels, void* stream);
+
+/* MTR:89, 150-169. logits [B,C] float32, 1 <= C <= 32; labels int32 [B]. Per row the CE and the prediction are those of
+ * nerfail_attack_logit_stats / nerfail_eval_logit_stats (one shared device function: the FIRST maximum; log-sum-exp with the
+ * maximum subtracted, minus the label's logit, in double); a row that holds a NaN, or whose label is outside 0..C-1, is never
+ * correct and has CE NaN.
+ *   d_logits  [B,C] or NULL (the validation phase): (softmax - onehot) / B, the gradient of nn.CrossEntropyLoss()'s mean
+ *             (MTR:89, 164), evaluated in double and rounded once to float32; NaN for a row without a valid label.
+ *   row       the phase's stats row, NERFAIL_ATTACK_ROW_FLOATS float32 the caller zeroes per phase; this call adds
+ *             [0,1] the sum of the per-view CE as a (hi, lo) pair   [2] correct views   [3] views (B)   [4..15] left alone.
+ * One lane adds the B CEs to the running sum in view order, with plain loads and stores: batches accumulate in stream order.
+ * The sum of per-view CE is what MTR:168 means by loss.item() * inputs.size(0): exact here, where the reference rounds the
+ * batch mean to float32 once and multiplies it back. */
+int nerfail_cls_ce(const float* logits, const int32_t* labels, int B, int C, float* d_logits, float* row, void* stream);
+
+/* MTR:90, 165: one step of torch.optim.SGD(lr, momentum) - dampening 0, no weight decay, no Nesterov - on MyCNN, and the weight
+ * image kept in step, in ONE launch. params, grads, momentum_buf: nerfail_cnn_grad_floats(num_classes) floats each, in the
+ * layout nerfail_cnn_bwd_weights writes d_params in; packed: the image of nerfail_cnn_pack. lr and momentum are float32.
+ *   first != 0:  buf <- g                         (the step that creates torch's momentum buffer)
+ *   else:        buf <- fl(fl(mu * buf) + g)      (two roundings: buf.mul_(mu).add_(g))
+ *   then:        p <- fma(-lr, buf, p)            (one rounding: p.add_(buf, alpha = -lr))
+ * which is, bit for bit, what torch's CPU kernels compute. On return packed is bit for bit what nerfail_cnn_pack makes from the
+ * updated parameters: every updated float is written to its one to three places in the image by the lane that updated it. The
+ * floats that round a region up to a multiple of 4, in either layout, and the zero tap and channel of stage 1's forward
+ * weights are neither read nor written. All four buffers 16-byte aligned, none NULL. */
+int nerfail_cnn_sgd_step(float* params, const float* grads, float* momentum_buf, float* packed, int num_classes, float lr,
+                         float momentum, int first, void* stream);
+
+/* MTR:170-186 on one lane. train_row, val_row: the two phases' stats rows; n_train, n_val >= 1: the DATASET lengths - losses
+ * and accuracies divide by len(dataset), not by the views seen, so the views a drop_last loader skips count as wrong and as
+ * loss 0, as in the reference (MTR:170-171). best: float32 [2] = {best validation accuracy, its epoch}, initialised by the
+ * caller to {0, -1} (MTR:92). The epoch is taken exactly when its validation accuracy is > the best (MTR:181): a tie keeps the
+ * earlier epoch, a NaN is never taken; then best is updated and *flag = 1, else *flag = 0 - the best weights are one
+ * nerfail_copy_if(flag, params, best_params, n) away. Accuracies are compared as float32 (equal counts give equal floats).
+ * record: float32 [NERFAIL_ATTACK_ROW_FLOATS] = {train loss, train acc, val loss, val acc, taken, best epoch, best acc, epoch,
+ * train correct, train views, val correct, val views, 0, 0, 0, 0}. The rows are not written. */
+int nerfail_cls_epoch_close(const float* train_row, const float* val_row, int64_t n_train, int64_t n_val, float* best, int epoch,
+                            float* record, int32_t* flag, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

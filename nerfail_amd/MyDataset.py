@@ -113,3 +113,90 @@ class gauss_dataset_rand_select(gauss_dataset):
         sel = random.sample(range(ori_length), n)
         super().__init__([all_index_and_dist_name_list[i] for i in sel], [all_img_name_list[i] for i in sel],
                          [all_img_save_to_name_list[i] for i in sel], [all_img_mask_save_to_name_list[i] for i in sel], device, Ns)
+
+
+def find_classes(directory):
+    """MD:15-25: the class folders of a dataset, sorted, and their indices."""
+    classes = sorted(entry.name for entry in os.scandir(directory) if entry.is_dir())
+    if not classes:
+        raise FileNotFoundError(f"Couldn't find any class folder in {directory}.")
+    return classes, {cls_name: i for i, cls_name in enumerate(classes)}
+
+
+class MySimpleDataset(Dataset):
+    """MD:28-185 for the branch model_train.py uses (_3_channels=True, no ori_img_from, load_later=False): the classification
+    set `root/<class>/<set_name>/*.png` - same constructor, same class table, file filter (MD:81-87) and index rule
+    (start_idx + img_index), and per item the reference's float [3,H,W] white-background tensor and the label.
+
+    What differs is where the views live. The reference keeps one float tensor per view (7.7 MB at 800 x 800) and the
+    DataLoader stacks 16 of them per batch; here the set is resident as ONE uint8 store [N,H,W,ch] plus an int32 label vector
+    on the device (`store`, `labels`, row k = index `indices[k]`), and a batch is gathered from it by device indices
+    (torch.ops.nerfail_mi.cls_batch, which also makes the white background of MD:98-105) - what
+    nerfail_amd.model_train.train_classifier does. Files of mixed channel counts or sizes raise; the reference's other branches
+    raise NotImplementedError."""
+
+    def __init__(self, root, set_name, class_names_path=None, test_dir_change_dict=None, ori_img_from=None, _3_channels=False,
+                 resize_frame=False, resize_frame_size=None, device='cpu', load_later=False, return_img_before_resize=False):
+        if ori_img_from is not None:
+            raise NotImplementedError('MySimpleDataset: ori_img_from (MD:73-75, 118-142) is not ported')
+        if load_later:
+            raise NotImplementedError('MySimpleDataset: load_later=True (MD:90-91, 149-171) is not ported')
+        if not _3_channels:
+            raise NotImplementedError('MySimpleDataset: _3_channels=False (four-channel items, MD:98) is not ported')
+        if return_img_before_resize:
+            raise NotImplementedError('MySimpleDataset: return_img_before_resize=True (MD:107-108, 173-174) is not ported')
+        if resize_frame and resize_frame_size is not None:
+            raise NotImplementedError('MySimpleDataset: a resize at load time (MD:110-111) is not ported; train_classifier '
+                                      'resizes the batches of the models that need it')
+        self.classes, self.class_to_idx = find_classes(root)
+        if class_names_path is not None:
+            with open(class_names_path, 'w') as f:
+                for i_classes in self.classes:
+                    f.write(str(self.class_to_idx[i_classes]) + " -- " + i_classes + "\n")
+        self.root, self.set_name, self.device = root, set_name, device
+        self.test_dir_change_dict = test_dir_change_dict
+        self.now_index = 0
+        images, self.label_set = {}, {}
+        for class_name in self.classes:
+            self._read_one_class(class_name, set_name, images)
+        self.length = len(images)
+        self.indices = sorted(images)
+        self._row = {idx: k for k, idx in enumerate(self.indices)}
+        shapes = {images[i].shape for i in self.indices}
+        if len(shapes) > 1:
+            raise ValueError('MySimpleDataset: the files of %s/*/%s differ in size or channel count: %s'
+                             % (root, set_name, sorted(shapes)))
+        dev = torch.device(device)
+        if self.length:
+            self.store = torch.from_numpy(np.stack([images[i] for i in self.indices])).to(dev)
+        else:
+            self.store = torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=dev)
+        self.labels = torch.tensor([self.label_set[i] for i in self.indices], dtype=torch.int32).to(dev)
+
+    def _read_one_class(self, class_name, set_name, images):
+        class_path = os.path.join(self.root, class_name, set_name)
+        class_idx = self.class_to_idx[class_name]
+        if self.test_dir_change_dict is not None and class_idx in self.test_dir_change_dict.keys():
+            class_path = self.test_dir_change_dict[class_idx]
+        start_idx = self.now_index
+        for img_file in os.listdir(class_path):
+            parts = img_file.split("_")
+            if (len(parts) < 3) and ("ori" not in img_file):                                     # MD:82
+                stem = parts[1] if len(parts) == 2 else parts[0]
+                img_index = int(stem.replace(".png", "").replace(".jpg", "").replace(".jpeg", ""))
+                img_idx = start_idx + img_index
+                img = _imread_unchanged(os.path.join(class_path, img_file))
+                if img is None or img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
+                    raise ValueError('MySimpleDataset: %s is not an 8-bit image of 3 or 4 channels' % os.path.join(class_path, img_file))
+                images[img_idx] = np.ascontiguousarray(img)
+                self.label_set[img_idx] = class_idx
+                self.now_index += 1
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, idx):
+        from . import ops
+        k = self._row[idx]
+        x, _ = ops.cls_batch(self.store, self.labels, torch.tensor([k], dtype=torch.int64, device=self.store.device))
+        return x[0], self.label_set[idx]

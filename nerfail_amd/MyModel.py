@@ -11,7 +11,10 @@ pool masks and the backward fills every parameter's .grad (and x.grad when x req
 torch.ops.nerfail_mi.cnn_bwd_weights: native HIP weight gradients without float atomics, bitwise reproducible; a parameter
 with requires_grad=False gets None. model_train.py's loop (cross-entropy, SGD with momentum) runs on it unchanged. The weight
 image is rebuilt when a parameter's version moves, so every optimizer.step() is followed by one repack (18 small launches) in
-the next forward. Under torch.no_grad(), with all parameters frozen, in input_gradients() and in DeepFool a trainable module
+the next forward - unless the module was flattened: MyCNN.flatten_parameters() re-homes the 18 parameters as views of ONE
+buffer in the layout the weight gradients arrive in (ops.cnn_grad_layout), and MyCNN.sgd_step() then is torch.optim.SGD's
+momentum step and the update of the weight image in one launch (torch.ops.nerfail_mi.cnn_sgd_step): the next forward packs
+nothing. nerfail_amd.model_train.train_classifier is the loop built on it. Under torch.no_grad(), with all parameters frozen, in input_gradients() and in DeepFool a trainable module
 behaves exactly like a default one.
 
 MyCNN.input_gradients(logits, d_logits) is the backward for several right-hand sides at once: the input gradients of R
@@ -40,6 +43,7 @@ class MyCNN(nn.Module):
         self.fc2 = nn.Linear(512, num_classes)
         self.num_classes = num_classes
         self._images = ImageCache(self._params, {'packed': (self._pack, None)})
+        self._flat = None
 
     def _params(self):
         ps = []
@@ -62,6 +66,50 @@ class MyCNN(nn.Module):
         """The MFMA weight image (nerfail_cnn_pack), cached like NeRF's (_images.ImageCache): rebuilt when any parameter
         moves or is written in place."""
         return self._images.get('packed')
+
+    def _is_flat(self):
+        """True while every parameter still is the view of self._flat that flatten_parameters() made it (.to(), a deep copy
+        or load_state_dict(assign=True) re-home parameters: the module then is an ordinary one again)."""
+        flat = self._flat
+        if flat is None:
+            return False
+        layout, _ = ops.cnn_grad_layout(self.num_classes)
+        return all(p.data_ptr() == flat.data_ptr() + 4 * o and p.is_contiguous() and p.dtype == torch.float32
+                   for (o, _), p in zip(layout, self._params()))
+
+    def flatten_parameters(self):
+        """Re-homes the 18 parameters as views of ONE float32 buffer in the layout of ops.cnn_grad_layout (the layout
+        cnn_bwd_weights writes d_params in) and returns that buffer; the alignment floats between the regions are 0. The
+        Parameter objects stay the same ones, so state_dict(), load_state_dict(), torch.save and an optimizer that already holds
+        them keep working; .to() re-homes them as for any module, after which the module is no longer flat (call this again).
+        A no-op, returning the same buffer, on a module that is flat. Trainable modules only."""
+        if not self.trainable:
+            raise RuntimeError('MyCNN.flatten_parameters: construct the module with trainable=True')
+        if self._is_flat():
+            return self._flat
+        ps = self._params()
+        layout, total = ops.cnn_grad_layout(self.num_classes)
+        flat = torch.zeros((total,), dtype=torch.float32, device=ps[0].device)
+        with torch.no_grad():
+            for (o, sh), p in zip(layout, ps):
+                view = flat[o:o + p.numel()].view(sh)
+                view.copy_(p.detach())
+                p.data = view
+        self._flat = flat
+        return flat
+
+    def sgd_step(self, d_params, momentum_buf, lr, momentum, first):
+        """One torch.optim.SGD(lr, momentum) step (dampening 0, no weight decay, no Nesterov) on the flat parameters from the
+        flat gradient `d_params` of ops.cnn_bwd_weights, with `momentum_buf` (a flat float32 buffer the caller keeps; `first`
+        says that it holds nothing yet). The same launch brings the weight image up to date, so the next forward packs
+        nothing. No autograd graph, no host read."""
+        if not self._is_flat():
+            raise RuntimeError('MyCNN.sgd_step: the parameters are not flat (call flatten_parameters(); .to() un-flattens)')
+        packed = self.packed()
+        ops.cnn_sgd_step(self._flat, d_params, momentum_buf, packed, self.num_classes, float(lr), float(momentum), bool(first))
+        for p in self._params():                     # the kernel wrote through the flat buffer: tell autograd and the caches
+            torch.autograd.graph.increment_version(p)
+        self._images.adopt('packed', packed)
 
     def forward(self, x):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:

@@ -16,6 +16,11 @@ The rules, each pinned by tests/test_image_cache.py (stub packers) and tests/tes
  5. Nothing is packed before it is asked for: which images a code path needs is the caller's business.
  6. A deep copy or a second instance never sees this owner's images: the copy's parameters have other pointers.
  7. None is a legal cached value (a shape the kernel does not cover): it is neither sized nor packed again.
+ 8. adopt(name, image) takes an image the owner itself brought up to date while it wrote the parameters (a fused optimizer
+    step that updates weights and image in one launch, MyCNN.sgd_step): the key is re-read AFTER that write, `image` is
+    cached under it, and every OTHER image of the owner is dropped as after any write. The next lookup of `name` is a hit;
+    any further write drops it again (rule 2). The image's contents are the owner's promise (tests/test_hip_cls_flat.py
+    holds MyCNN to it bitwise); rule pinned by tests/test_image_cache_adopt.py.
 Known blind spot, kept as it is: a write through `.data` of an existing storage bumps no version and goes unseen."""
 
 
@@ -49,6 +54,12 @@ class ImageCache:
         if not all(n in self._images for n in names):
             self._images.update(zip(names, pack()))
         return tuple(self._images[n] for n in names)
+
+    def adopt(self, name, image):
+        """Cache `image` as the image `name` of the parameters as they are NOW; every other image is dropped."""
+        if name not in self._table:
+            raise KeyError(name)
+        self._key, self._images = self._now(), {name: image}
 
     def holds(self, name, buffer):
         """True when `buffer` is the image `name` this cache packed last (whatever happened to the parameters since)."""

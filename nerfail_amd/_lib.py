@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('NERFAIL_HIP_LIB') or os.path.join(_HERE, 'lib', 'libn
 ABI_VERSION = 14
 ABI_REVISION = 15                        # additions since ABI_VERSION (nerfail_abi_revision): the NeRFail-S epoch statistics
 EVAL_REVISION = 1                        # nerfail_eval_revision: the attack-evaluation entry points (model_test)
+CLS_REVISION = 1                         # nerfail_cls_revision: the victim-training entry points (model_train)
 EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
 EVAL_VIEW_DOUBLES = 6                    # NERFAIL_EVAL_VIEW_DOUBLES: one view's row
 EVAL_RECORD_DOUBLES = 16 + 32            # NERFAIL_EVAL_RECORD_DOUBLES: the set record of nerfail_eval_fold
@@ -168,6 +169,11 @@ SIGNATURES = {
     'nerfail_eval_view_metrics': (c_i, [c_p, c_i, c_p, c_i, c_i, c_i64, c_p, c_p, c_p, c_p]),
     'nerfail_eval_logit_stats': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     'nerfail_eval_fold': (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    'nerfail_cls_revision': (c_i, []),
+    'nerfail_cls_batch': (c_i, [c_p, c_i, c_p, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p]),
+    'nerfail_cls_ce': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    'nerfail_cnn_sgd_step': (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_i, c_p]),
+    'nerfail_cls_epoch_close': (c_i, [c_p, c_p, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -223,6 +229,9 @@ def load():
     if lib.nerfail_eval_revision() != EVAL_REVISION:
         raise RuntimeError('nerfail_amd: attack-evaluation revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_eval_revision(), EVAL_REVISION))
+    if lib.nerfail_cls_revision() != CLS_REVISION:
+        raise RuntimeError('nerfail_amd: victim-training revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_cls_revision(), CLS_REVISION))
     _lib = lib
     return lib
 

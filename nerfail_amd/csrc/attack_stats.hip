@@ -21,13 +21,6 @@ struct OriViews {
     int nv;
 };
 
-__device__ __forceinline__ double pair_get(const float* p) { return (double)p[0] + (double)p[1]; }
-__device__ __forceinline__ void pair_put(float* p, double v) {
-    const float hi = (float)v;
-    p[0] = hi;
-    p[1] = (isfinite(hi) ? (float)(v - (double)hi) : 0.f);
-}
-
 // ---- AS:319-330: per-view CE and first-maximum argmax of both logit sets, one wave. Lane l takes views l, l + 64, ...
 // (an attack batch is 8 views; the export pass a few hundred at most).
 __global__ __launch_bounds__(64) void attack_logit_stats_kernel(const float* __restrict__ cla, const float* __restrict__ ori_cla, int B,

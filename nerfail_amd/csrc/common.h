@@ -157,6 +157,8 @@ struct SinCosBands {
 struct LogitRow {
     int arg;
     double ce;
+    float m;            // the maximum, and s = sum exp(x - m): softmax_c = exp(x_c - m) / s (nerfail_cls_ce's gradient)
+    double s;
 };
 __device__ __forceinline__ LogitRow logit_row_stats(const float* __restrict__ x, int C, int label) {
     float m = x[0];
@@ -173,8 +175,22 @@ __device__ __forceinline__ LogitRow logit_row_stats(const float* __restrict__ x,
     LogitRow r;
     r.arg = nan ? -1 : arg;
     r.ce = nan ? (double)NAN : (lse - (double)x[label]);
+    r.m = m;
+    r.s = s;
     return r;
 }
+
+// A double-precision running sum kept in a float32 stats row as a (hi, lo) pair: hi = the sum rounded to float32, lo = the
+// rest (attack_stats.hip's rows, cls_train.hip's).
+__device__ __forceinline__ double pair_get(const float* p) { return (double)p[0] + (double)p[1]; }
+__device__ __forceinline__ void pair_put(float* p, double v) {
+    const float hi = (float)v;
+    p[0] = hi;
+    p[1] = (isfinite(hi) ? (float)(v - (double)hi) : 0.f);
+}
+
+// One colour byte of a BGRA dword on the white background of MT:237-254 / MD:98-105: the byte where alpha > 0, else 255.
+__device__ __forceinline__ float white_u8(unsigned w, int shift) { return (w >> 24) > 0u ? (float)((w >> shift) & 255u) : 255.f; }
 
 // pts = o + d*z with the reference's rounding (multiply, then add; no FMA): RN:381
 __device__ __forceinline__ float mul_add_rn(float a, float b, float c) { return __fadd_rn(__fmul_rn(a, b), c); }

@@ -23,8 +23,6 @@ struct EvalViews {
     const void* o[kEvalViews];
 };
 
-__device__ __forceinline__ float white_u8(unsigned w, int shift) { return (w >> 24) > 0u ? (float)((w >> shift) & 255u) : 255.f; }
-
 // The elements 3 u .. 3 u + ne - 1 of one side after the white background of MT:237-254 (4-channel formats: rgb where
 // alpha > 0, else 255; a NaN alpha fails the comparison and gives white). Image formats: unit u = pixel u, ne = 3. Consecutive
 // lanes take consecutive units, so a wave reads one contiguous piece of the image per instruction: 1 KB of F32C4 (128 bits per

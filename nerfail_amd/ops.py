@@ -741,3 +741,112 @@ def eval_fold(rows: Tensor, pred: Tensor, ce: Tensor, num_classes: int, record: 
 
 
 EVAL_OPS = ('eval_view_metrics', 'eval_logit_stats', 'eval_fold')
+
+
+# ----------------------------------------------------------------------------------------------- victim training (model_train.py:107-193; cls revision 1)
+def _cls_format(images):
+    if images.dtype != torch.uint8 or images.dim() < 3 or images.shape[-1] not in (3, 4) or not images.is_contiguous():
+        raise ValueError('images must be a contiguous uint8 store [N,...,4] (BGRA) or [N,...,3] (got %s %s)'
+                         % (images.dtype, tuple(images.shape)))
+    return _lib.EVAL_U8C4 if images.shape[-1] == 4 else _lib.EVAL_U8C3
+
+
+@custom_op(NS + '::cls_batch', mutates_args=(), device_types='cuda')
+def cls_batch(images: Tensor, labels_all: Tensor, idx: Tensor) -> tuple[Tensor, Tensor]:
+    """(x float32 [B,3,...], labels int32 [B]): the views idx (int64 [B], on the device) of a resident uint8 store [N,...,4|3] as
+    the classifier's planar input - four-channel views on the white background of MD:98-105 - and their labels. An index
+    outside 0..N-1 gives a view of NaN and the label -1."""
+    fmt = _cls_format(images)
+    N = images.shape[0]
+    if labels_all.dtype != torch.int32 or labels_all.numel() != N or idx.dtype != torch.int64 or idx.dim() != 1:
+        raise ValueError('labels_all must be int32 [N] and idx int64 [B]')
+    B = idx.shape[0]
+    P = images[0].numel() // images.shape[-1] if N else 0
+    x = torch.empty((B, 3) + tuple(images.shape[1:-1]), dtype=torch.float32, device=images.device)
+    labels = torch.empty((B,), dtype=torch.int32, device=images.device)
+    _chk(_lib.load().nerfail_cls_batch(_lib.dev(images, 'images'), fmt, _lib.dev(labels_all, 'labels_all'), N, P, _lib.dev(idx, 'idx'), B,
+                                       _lib.dev(x), _lib.dev(labels), _s()))
+    return x, labels
+
+
+@cls_batch.register_fake
+def _(images, labels_all, idx):
+    return (images.new_empty((idx.shape[0], 3) + tuple(images.shape[1:-1]), dtype=torch.float32),
+            images.new_empty((idx.shape[0],), dtype=torch.int32))
+
+
+@custom_op(NS + '::cls_ce', mutates_args=('row',), device_types='cuda')
+def cls_ce(logits: Tensor, labels: Tensor, row: Tensor, want_grad: bool) -> Tensor:
+    """Adds one batch's sum of per-view CE, correct count and B into the phase's stats row; returns d loss / d logits of
+    nn.CrossEntropyLoss()'s mean, (softmax - onehot) / B [B,C] - or an empty tensor unless want_grad."""
+    _row_ok(row)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or labels.dtype != torch.int32 or labels.numel() != logits.shape[0]:
+        raise ValueError('logits must be float32 [B,C] and labels int32 [B]')
+    B, C = logits.shape
+    d = torch.empty((B, C) if want_grad else (0,), dtype=torch.float32, device=logits.device)
+    _chk(_lib.load().nerfail_cls_ce(_lib.dev(logits, 'logits'), _lib.dev(labels, 'labels'), B, C, _lib.dev(d) if want_grad else None,
+                                    _lib.dev(row), _s()))
+    return d
+
+
+@cls_ce.register_fake
+def _(logits, labels, row, want_grad):
+    return logits.new_empty(tuple(logits.shape) if want_grad else (0,))
+
+
+@custom_op(NS + '::cnn_sgd_step', mutates_args=('params', 'momentum_buf', 'packed'), device_types='cuda')
+def cnn_sgd_step(params: Tensor, grads: Tensor, momentum_buf: Tensor, packed: Tensor, num_classes: int, lr: float, momentum: float,
+                 first: bool) -> None:
+    """One torch.optim.SGD(lr, momentum) step on MyCNN's flat parameters (cnn_grad_layout) and, in the same launch, the
+    weight image: afterwards `packed` is bitwise nerfail_cnn_pack of the updated parameters."""
+    lib = _lib.load()
+    n = lib.nerfail_cnn_grad_floats(num_classes)
+    for t, name in ((params, 'params'), (grads, 'grads'), (momentum_buf, 'momentum_buf')):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError('%s must be %d contiguous float32 (cnn_grad_layout)' % (name, n))
+    if packed.dtype != torch.float32 or packed.numel() != lib.nerfail_cnn_packed_floats(num_classes) or not packed.is_contiguous():
+        raise ValueError('packed must be the weight image of %d classes' % num_classes)
+    _chk(lib.nerfail_cnn_sgd_step(_lib.dev(params, 'params'), _lib.dev(grads, 'grads'), _lib.dev(momentum_buf, 'momentum_buf'),
+                                  _lib.dev(packed, 'packed'), num_classes, lr, momentum, int(first), _s()))
+
+
+@custom_op(NS + '::cls_epoch_close', mutates_args=('best', 'record', 'flag'), device_types='cuda')
+def cls_epoch_close(train_row: Tensor, val_row: Tensor, n_train: int, n_val: int, best: Tensor, epoch: int, record: Tensor,
+                    flag: Tensor) -> None:
+    """MTR:170-186: the two phases' rows and the DATASET lengths -> the epoch record; the strict best-so-far rule against
+    `best` (float32 [2] = {best val acc, its epoch}); flag (int32 [1])."""
+    _row_ok(train_row, 'train_row')
+    _row_ok(val_row, 'val_row')
+    _row_ok(record, 'record')
+    if best.dtype != torch.float32 or best.numel() != 2 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError('best must be float32 [2] and flag int32 [1]')
+    _chk(_lib.load().nerfail_cls_epoch_close(_lib.dev(train_row), _lib.dev(val_row), n_train, n_val, _lib.dev(best), epoch,
+                                             _lib.dev(record), _lib.dev(flag), _s()))
+
+
+@custom_op(NS + '::cnn_bwd_weights_into', mutates_args=('scratch', 'd_params'), device_types='cuda')
+def cnn_bwd_weights_into(packed: Tensor, x: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, scratch: Tensor,
+                         d_params: Tensor) -> None:
+    """cnn_bwd_weights into buffers the caller keeps across steps: d_params (cnn_grad_layout floats; the alignment floats are
+    never written, so a buffer zeroed once stays clean) and scratch (at least nerfail_cnn_bwd_weights_scratch_bytes). Bitwise
+    cnn_bwd_weights' d_params."""
+    lib = _lib.load()
+    if d_logits.dtype != torch.float32 or x.dtype != torch.float32 or d_logits.dim() != 2 or x.dim() != 4 or x.shape[0] != d_logits.shape[0]:
+        raise ValueError('cnn_bwd_weights_into: x must be float32 [B,3,H,W] and d_logits float32 [B,num_classes]')
+    B, C = d_logits.shape
+    H, W = x.shape[2], x.shape[3]
+    nb = lib.nerfail_cnn_bwd_weights_scratch_bytes(B, H, W, C)
+    if (nb == 0 or masks.numel() == 0 or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W)
+            or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C)):
+        raise ValueError('cnn_bwd_weights_into: needs the workspace and masks of a mask-keeping forward of these %d images' % B)
+    if scratch.dtype != torch.float32 or scratch.numel() * 4 < nb or d_params.dtype != torch.float32 or d_params.numel() != lib.nerfail_cnn_grad_floats(C):
+        raise ValueError('cnn_bwd_weights_into: scratch needs %d float32, d_params %d' % (nb // 4, lib.nerfail_cnn_grad_floats(C)))
+    _chk(lib.nerfail_cnn_bwd_weights(_lib.dev(packed), C, _lib.dev(x, 'x'), _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits, 'd_logits'),
+                                     B, H, W, _lib.dev(scratch, 'scratch'), _lib.dev(d_params, 'd_params'), None, _s()))
+
+
+def cnn_bwd_weights_scratch_floats(B, H, W, num_classes):
+    return _lib.load().nerfail_cnn_bwd_weights_scratch_bytes(B, H, W, num_classes) // 4
+
+
+CLS_OPS = ('cls_batch', 'cls_ce', 'cnn_bwd_weights_into', 'cnn_sgd_step', 'cls_epoch_close')
