@@ -721,17 +721,30 @@ class gauss_net(nn.Module):
         of the images unless the original logits have to be computed, alpha + pass mask kept for the rgb-only backward.
         Returns (x_rgba leaf with requires_grad, cla, ori_cla, views, aux); differentiate cla down to x_rgba with autograd,
         then hot_backward_rgb(aux, x_rgba.grad, views)."""
+        _, x_rgba, cla, ori_cla, views, aux = self._hot_and_tail(spatial_rgb, weight_and_index_list, ori_img, view_ids, export=False)
+        return x_rgba, cla, ori_cla, views, aux
+
+    def export_forward(self, spatial_rgb, weight_and_index_list, ori_img, view_ids=None):
+        """The forward of the export epoch (AS:310-317): no gradient, and the unclipped mask image `x` kept for the export.
+        Returns (x, x_rgba, cla, ori_cla, views)."""
+        with torch.no_grad():
+            return self._hot_and_tail(spatial_rgb, weight_and_index_list, ori_img, view_ids, export=True)[:5]
+
+    def _hot_and_tail(self, spatial_rgb, weight_and_index_list, ori_img, view_ids, export):
+        """The body of attack_forward (x_rgba a leaf that requires grad, aux, no x) and of export_forward (x, no aux)."""
         dev = _cuda()
         s = spatial_rgb.detach()
         if s.device != dev:
             s = s.to(dev)
         views = resolve_views(s, weight_and_index_list, ori_img, view_ids, self.keep_views_resident)
-        _, x_rgba, aux = hot_forward(s, views, self.epsilon, self._mm() if self.update_epsilon_3d else None, need_x=False, need_aux=True)
-        x_rgba.requires_grad_(True)
+        x, x_rgba, aux = hot_forward(s, views, self.epsilon, self._mm() if self.update_epsilon_3d else None, need_x=export,
+                                     need_aux=not export)
+        if not export:
+            x_rgba.requires_grad_(True)
         self._ori_keep_src = getattr(views, '_ori_keep', None)
         cla, ori_cla = self.cold_tail(x_rgba, views.ori_float, ori_key=self._ori_key(views))
         self._ori_keep_src = None
-        return x_rgba, cla, ori_cla, views, aux
+        return x, x_rgba, cla, ori_cla, views, aux
 
     # ---- all class-logit gradients of one forward in ONE pass over the inverted index (DeepFool, SURVEY 8f N1)
     def logit_gradients(self, spatial_rgb, weight_and_index_list, x, x_rgba, cla, classes):

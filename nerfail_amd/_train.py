@@ -231,16 +231,9 @@ class GradArena:
 
     def reduce_(self, group=None, timing=None):
         """THE collective of a step: one all-reduce (sum) of the whole arena, P + 2 floats. `timing`: a dict that gets HIP
-        events around it ('allreduce_events': (start, end, bytes)), as attack.sharded_perturbation_grad_rgb records them."""
+        events around it ('allreduce_events': (start, end, bytes), recorded by sharding.all_reduce_sum_)."""
         from . import sharding
-        if timing is not None and self.buf.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        sharding.all_reduce_sum_(self.buf, group)
-        if timing is not None and self.buf.is_cuda:
-            e1.record()
-            timing.setdefault('allreduce_events', []).append((e0, e1, self.nbytes))
-        return self.buf
+        return sharding.all_reduce_sum_(self.buf, group, timing)
 
 
 class RenderRaysTrain(torch.autograd.Function):

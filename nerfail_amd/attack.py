@@ -1,15 +1,16 @@
 """The attack-step arithmetic of attack_NeRFail_S.py (reference = AS), on the MI355X.
 
-`igsm_step` is AS:352-392 as one kernel. `nerfail_s_step` is one iteration of the AS:304-392 loop body
-(forward through gauss_net, CE loss, backward to the perturbation, sign step, epsilon clamp); with
-torch.distributed initialised it shards the batch's views over ranks and sums the perturbation gradient
-with ONE all-reduce (RCCL over xGMI on the GPU box, gloo in the CPU tests) before every rank applies the
-identical step - the only collective on the whole path. `nerfail_s` is the whole AS:278-442 loop as a
-product: epoch statistics, best tensor and export epoch, decided on the device (csrc/attack_stats.hip); under
-torch.distributed it adds one all-reduce of a 16-float statistics row per EPOCH.
+`igsm_step` is AS:352-392 as one kernel. One iteration of the AS:304-392 loop body is written once, as `_rgb_step`: `_share`
+takes the batch apart (view ids, size, this rank's views), `_forward_backward` runs gauss_net's forward, the optional epoch
+statistics, the CE loss (+ the beta term) and the classifier backward, and the step ends in the fused gather backward + sign
+step (one rank) or in the 3 Ns + 1 float buffer - rgb gradient, loss in the tail - that ONE all-reduce sums over the ranks
+(RCCL over xGMI on the GPU box, gloo in the CPU tests) before every rank applies the identical step: the only collective on
+the whole path. `nerfail_s_step` is that body; `nerfail_s`, the whole AS:278-442 loop as a product
+(epoch statistics, best tensor and export epoch, decided on the device, csrc/attack_stats.hip), calls it with its statistics
+and beta and adds one all-reduce of a 16-float statistics row per EPOCH. perturbation_grad, the four-channel autograd path,
+stays apart: it is what the rgb path is compared against.
 """
 import torch
-import torch.distributed as dist
 
 from . import _lib
 from . import ops  # noqa: F401  (registers torch.ops.nerfail_mi.*)
@@ -64,71 +65,112 @@ def igsm_step_rgb(spatial, grad_rgb, spatial_init, a=2.0, epsilon=32.0, targeted
     return out
 
 
+def _share(batch, group=None):
+    """THE place a batch `(weight_and_index, ori_img[, view_ids])` is taken apart. The ids: the third element, else what travels
+    with a MyDataset.collate_views list as `weight_and_index.view_ids`. Returns (this rank's views of the batch as
+    (weight_and_index, ori_img, view_ids) - the batch's own objects when the rank owns all of it, None when it owns no view -,
+    the size B of the WHOLE batch, sharded: whether the ranks' contributions are summed by a collective)."""
+    world, rank = sharding.world_and_rank(group)
+    wi, ori = batch[0], batch[1]
+    vids = batch[2] if len(batch) > 2 and batch[2] is not None else getattr(wi, 'view_ids', None)
+    B = len(vids if vids is not None else wi)
+    lo, hi = sharding.shard_range(B, rank, world)
+    if hi <= lo:                            # more ranks than views: this rank only takes part in the sum
+        parts = None
+    elif (lo, hi) == (0, B):
+        parts = (wi, ori, vids)
+    else:
+        parts = (None if wi is None else wi[lo:hi], None if ori is None else ori[lo:hi], None if vids is None else list(vids)[lo:hi])
+    return parts, B, world > 1 or sharding.force_collectives()
+
+
+def _forward_backward(net, spatial, parts, batch_total, label, stats=None, epoch=None, beta=0.):
+    """Forward of the views `parts`, their statistics (on the perturbation BEFORE this batch's update, as the reference takes
+    them), the objective (1 - |beta|) CE + beta MSE of AS:332-336 as a mean over `batch_total` views (a shard holding k of B
+    views contributes with weight k/B), backward down to x_rgba. Returns (x_rgba with its .grad, views, aux, loss, cla)."""
+    xr, cla, ori_cla, views, aux = net.attack_forward(spatial, *parts)
+    if stats is not None:
+        stats.batch(epoch, cla.detach(), ori_cla.detach(), xr, views)
+    B = float(batch_total or cla.shape[0])
+    loss = torch.nn.functional.cross_entropy(cla, label.to(cla.device).broadcast_to([cla.shape[0]]), reduction='sum') / B
+    if beta != 0.:
+        loss = (1. - abs(beta)) * loss                                # AS:332-334
+    loss.backward()
+    if beta != 0.:                                                    # d (beta mean((x_rgba - ori)^2)) / d x_rgba, mean over the WHOLE batch
+        _lib.check(_lib.load().nerfail_img_sqerr_grad_add(_lib.dev(xr.detach()), _ori_pointer_table(views), views.B, views.P, int(views.ori_u8),
+                                                          2. * float(beta) / (4. * views.P * B), _lib.dev(xr.grad), _lib.stream()))
+    return xr, views, aux, loss.detach(), cla.detach()
+
+
+def _grad_buffer(xr, views, aux, loss, out=None):
+    """The rgb gradient as [Ns,3] by the gather backward, then the loss: `out`, 3 Ns + 1 floats."""
+    from .GaussNet import hot_backward_rgb
+    if out is None:
+        out = torch.empty((3 * views.Ns + 1,), dtype=torch.float32, device=xr.device)
+    hot_backward_rgb(aux, xr.grad, views, out)
+    out[3 * views.Ns] = loss
+    return out
+
+
+def _summed_grad_rgb(net, spatial, share, label, group=None, timing=None, **objective):
+    """The 3 Ns + 1 floats of this rank's share (zeros when it owns no view), summed over the ranks by ONE all-reduce (C1: the
+    gradient and, in its tail, the loss) when sharded. Identical on every rank."""
+    parts, B, sharded = share
+    if parts is not None:
+        buf = _grad_buffer(*_forward_backward(net, spatial, parts, B, label, **objective)[:4])
+    else:
+        buf = torch.zeros((3 * (spatial.numel() // 4) + 1,), dtype=torch.float32, device=_cuda())
+    if sharded:
+        sharding.all_reduce_sum_(buf, group, timing)
+    return buf
+
+
+def _rgb_step(net, spatial, spatial_init, batch, label, a, epsilon, targeted, group=None, timing=None, **objective):
+    """THE NeRFail-S step on the rgb-gradient path: (new perturbation, loss). One rank, no collective, net.fused_sign_step: the
+    gather backward with the sign step AS:352-392 as its epilogue (the [Ns,3] gradient is never materialised); else the summed
+    buffer, then the sign step on every rank. `objective`: stats, epoch and beta of _forward_backward, as nerfail_s passes them."""
+    from .GaussNet import hot_backward_rgb_step
+    share = parts, B, sharded = _share(batch, group)
+    if parts is None or sharded or not getattr(net, 'fused_sign_step', True):
+        buf = _summed_grad_rgb(net, spatial, share, label, group, timing, **objective)
+        return igsm_step_rgb(spatial, buf, spatial_init, a, epsilon, targeted).view(spatial.shape), buf[-1]
+    xr, views, aux, loss, _ = _forward_backward(net, spatial, parts, B, label, **objective)
+    return hot_backward_rgb_step(aux, xr.grad, views, spatial, spatial_init, a, epsilon, targeted).view(spatial.shape), loss
+
+
+def _attack_batch(net, s, s_init, batch, lab, a, epsilon, targeted, beta, stats, epoch, group):
+    """One batch of an attack epoch of nerfail_s: _rgb_step with the epoch's statistics and the beta term. Returns the new
+    perturbation (the seam at which the tests record every iterate)."""
+    return _rgb_step(net, s, s_init, batch, lab, a, epsilon, targeted, group, stats=stats, epoch=epoch, beta=beta)[0]
+
+
 def perturbation_grad_rgb(net, spatial, weight_and_index, ori_img, label, batch_total=None, view_ids=None, out=None):
     """The NeRFail-S step's gradient in the form the step consumes (AS:357-392 reads grad[..., :3] only): a flat buffer of
     3 Ns + 1 floats - d(CE)/d(spatial rgb) as [Ns,3], then the loss - filled by the rgb-only backward (no `x` tensor, 5 bytes
     per pixel between forward and backward, 23 MB instead of 30.7 MB for the all-reduce, which carries the loss in the same
     collective). The three channels equal perturbation_grad()'s bit for bit."""
-    from .GaussNet import hot_backward_rgb
-    xr, cla, ori_cla, views, aux = net.attack_forward(spatial, weight_and_index, ori_img, view_ids)
-    lab = label.to(cla.device).broadcast_to([cla.shape[0]])
-    loss = torch.nn.functional.cross_entropy(cla, lab, reduction='sum') / float(batch_total or cla.shape[0])
-    loss.backward()
-    Ns = views.Ns
-    if out is None:
-        out = torch.empty((3 * Ns + 1,), dtype=torch.float32, device=xr.device)
-    hot_backward_rgb(aux, xr.grad, views, out)
-    out[3 * Ns] = loss.detach()
-    return out, cla.detach()
+    xr, views, aux, loss, cla = _forward_backward(net, spatial, (weight_and_index, ori_img, view_ids), batch_total, label)
+    return _grad_buffer(xr, views, aux, loss, out), cla
 
 
 def sharded_perturbation_grad_rgb(net, spatial, weight_and_index, ori_img, label, group=None, timing=None, view_ids=None):
     """perturbation_grad_rgb of this rank's share of the batch's views, then ONE all-reduce of the 3 Ns + 1 floats (C1: the
-    gradient and, in its tail, the loss). Identical on every rank."""
-    world, rank = sharding.world_and_rank(group)
-    if view_ids is None and getattr(weight_and_index, 'view_ids', None) is not None:
-        view_ids = weight_and_index.view_ids                # a MyDataset.collate_views batch: ids travel with the list
-    B = len(view_ids) if view_ids is not None else weight_and_index.shape[0]
-    lo, hi = sharding.shard_range(B, rank, world)
-    Ns = spatial.numel() // 4
-    if hi > lo:
-        buf, _ = perturbation_grad_rgb(net, spatial, None if weight_and_index is None else weight_and_index[lo:hi],
-                                       None if ori_img is None else ori_img[lo:hi], label, batch_total=B,
-                                       view_ids=None if view_ids is None else list(view_ids)[lo:hi])
-    else:                                   # more ranks than views: this rank only takes part in the sum
-        buf = torch.zeros((3 * Ns + 1,), dtype=torch.float32, device=_cuda())
-    if world > 1 or sharding.force_collectives():
-        if timing is not None and buf.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        sharding.all_reduce_sum_(buf, group)         # C1: the perturbation-gradient all-reduce (+ the loss in its tail)
-        if timing is not None and buf.is_cuda:
-            e1.record()
-            timing.setdefault('allreduce_events', []).append((e0, e1, buf.numel() * buf.element_size()))
-    return buf
+    gradient and, in its tail, the loss). Identical on every rank. `timing`: optional dict; gets HIP events around the
+    collective ('allreduce_events', sharding.all_reduce_sum_)."""
+    return _summed_grad_rgb(net, spatial, _share((weight_and_index, ori_img, view_ids), group), label, group, timing)
 
 
 def sharded_perturbation_grad(net, spatial, weight_and_index, ori_img, label, group=None, timing=None, view_ids=None):
     """d(mean CE over the WHOLE batch)/d(spatial), identical on every rank: this rank differentiates its contiguous
     share of the batch's views (weight k/B), then ONE all-reduce sums the [P,H,W,4] gradient (C1).
-    `timing`: optional dict; gets HIP events around the collective ('allreduce_events') for bench.py."""
-    world, rank = sharding.world_and_rank(group)
-    B = weight_and_index.shape[0]
-    lo, hi = sharding.shard_range(B, rank, world)
-    if hi > lo:
-        g, loss, _ = perturbation_grad(net, spatial, weight_and_index[lo:hi], ori_img[lo:hi], label, batch_total=B,
-                                       view_ids=None if view_ids is None else list(view_ids)[lo:hi])
-    else:                                   # more ranks than views: this rank only takes part in the sum
-        g = torch.zeros_like(spatial)
-        loss = torch.zeros((), device=spatial.device)
-    if world > 1:
-        if timing is not None and g.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        sharding.all_reduce_sum_(g, group)           # C1: the perturbation-gradient all-reduce
-        if timing is not None and g.is_cuda:
-            e1.record()
-            timing.setdefault('allreduce_events', []).append((e0, e1, g.numel() * g.element_size()))
+    `timing`: as sharded_perturbation_grad_rgb."""
+    parts, B, sharded = _share((weight_and_index, ori_img, view_ids), group)
+    if parts is not None:
+        g, loss, _ = perturbation_grad(net, spatial, parts[0], parts[1], label, batch_total=B, view_ids=parts[2])
+    else:
+        g, loss = torch.zeros_like(spatial), torch.zeros((), device=spatial.device)
+    if sharded:
+        sharding.all_reduce_sum_(g, group, timing)   # C1: the perturbation-gradient all-reduce
         sharding.all_reduce_sum_(loss, group)
     return g, loss
 
@@ -138,11 +180,8 @@ def perturbation_step_rgb(net, spatial, spatial_init, weight_and_index, ori_img,
     epilogue (GaussNet.hot_backward_rgb_step) - the [Ns,3] gradient is never materialised. Returns (new perturbation, loss);
     bit-identical to perturbation_grad_rgb + igsm_step_rgb."""
     from .GaussNet import hot_backward_rgb_step
-    xr, cla, ori_cla, views, aux = net.attack_forward(spatial, weight_and_index, ori_img, view_ids)
-    lab = label.to(cla.device).broadcast_to([cla.shape[0]])
-    loss = torch.nn.functional.cross_entropy(cla, lab, reduction='sum') / float(cla.shape[0])
-    loss.backward()
-    return hot_backward_rgb_step(aux, xr.grad, views, spatial, spatial_init, a, epsilon, targeted), loss.detach()
+    xr, views, aux, loss, _ = _forward_backward(net, spatial, (weight_and_index, ori_img, view_ids), None, label)
+    return hot_backward_rgb_step(aux, xr.grad, views, spatial, spatial_init, a, epsilon, targeted), loss
 
 
 def nerfail_s_step(net, spatial, spatial_init, weight_and_index, ori_img, label, a=2.0, epsilon=32.0,
@@ -150,15 +189,7 @@ def nerfail_s_step(net, spatial, spatial_init, weight_and_index, ori_img, label,
     """One NeRFail-S iteration (AS:304-392) on one batch of views. Sharded over ranks when torch.distributed is up:
     every rank ends with the identical perturbation tensor."""
     if getattr(net, 'deterministic', True) and getattr(net, 'rgb_grad_only', True):
-        world, _ = sharding.world_and_rank(group)
-        if world == 1 and not sharding.force_collectives() and getattr(net, 'fused_sign_step', True):
-            if view_ids is None and getattr(weight_and_index, 'view_ids', None) is not None:
-                view_ids = weight_and_index.view_ids
-            out, loss = perturbation_step_rgb(net, spatial, spatial_init, weight_and_index, ori_img, label, a, epsilon, targeted, view_ids)
-            return out.view(spatial.shape), loss
-        Ns = spatial.numel() // 4
-        buf = sharded_perturbation_grad_rgb(net, spatial, weight_and_index, ori_img, label, group, timing, view_ids)
-        return igsm_step_rgb(spatial, buf, spatial_init, a, epsilon, targeted), buf[3 * Ns]
+        return _rgb_step(net, spatial, spatial_init, (weight_and_index, ori_img, view_ids), label, a, epsilon, targeted, group, timing)
     g, loss = sharded_perturbation_grad(net, spatial, weight_and_index, ori_img, label, group, timing, view_ids)
     return igsm_step(spatial, g, spatial_init, a, epsilon, targeted), loss
 
@@ -171,8 +202,7 @@ def nerfail_s_loop(net, spatial, spatial_init, batches, label, iters, a=2.0, eps
     s = spatial
     for it in range(iters):
         for b, batch in enumerate(batches):
-            wi, ori = batch[0], batch[1]
-            s, loss = nerfail_s_step(net, s, spatial_init, wi, ori, label, a, epsilon, targeted, group,
+            s, loss = nerfail_s_step(net, s, spatial_init, batch[0], batch[1], label, a, epsilon, targeted, group,
                                      view_ids=batch[2] if len(batch) > 2 else None)
             if on_iter is not None:
                 on_iter(it, b, s, loss)
@@ -234,61 +264,13 @@ class _EpochStats:
         _lib.check(self.lib.nerfail_img_sqerr(_lib.dev(x_rgba.detach()), _ori_pointer_table(views), views.B, views.P, int(views.ori_u8),
                                               _lib.c_p(self.scratch.data_ptr()), row, _lib.stream()))
 
-    def close(self, epoch, group, world):
-        if world > 1 or sharding.force_collectives():
-            sharding.all_reduce_sum_(self.rows[epoch], group)        # the ONE extra collective of an epoch: 16 floats
+    def close(self, epoch, group):
+        sharding.all_reduce_sum_(self.rows[epoch], group)            # the ONE extra collective of an epoch (when sharded): 16 floats
         _lib.check(self.lib.nerfail_attack_epoch_close(_lib.dev(self.rows[epoch]), _lib.dev(self.best), epoch, self.targeted,
                                                        _lib.dev(self.records[epoch]), _lib.dev(self.flag), _lib.stream()))
 
     def keep_if_taken(self, s, best):
         _lib.check(self.lib.nerfail_copy_if(_lib.dev(self.flag), _lib.dev(s), _lib.dev(best), s.numel(), _lib.stream()))
-
-
-def _batch_parts(batch, lo=None, hi=None):
-    wi, ori = batch[0], batch[1]
-    vids = batch[2] if len(batch) > 2 else getattr(wi, 'view_ids', None)
-    if lo is None:
-        return wi, ori, vids
-    return (None if wi is None else wi[lo:hi]), (None if ori is None else ori[lo:hi]), (None if vids is None else list(vids)[lo:hi])
-
-
-def _batch_size(batch):
-    wi, _, vids = _batch_parts(batch)
-    return len(vids) if vids is not None else (len(wi) if isinstance(wi, (list, tuple)) else wi.shape[0])
-
-
-def _attack_batch(net, s, s_init, batch, lab, a, epsilon, targeted, beta, stats, epoch, group, world, rank):
-    """One batch of an attack epoch: forward, the batch's statistics (on the perturbation BEFORE this batch's update, as the
-    reference takes them), the objective (1 - |beta|) CE + beta MSE of AS:332-336, backward, sign step. beta == 0 on one rank
-    is perturbation_step_rgb call for call (the fused gather backward + sign step); more than one rank shards the views as
-    sharded_perturbation_grad_rgb does and sums gradient + loss in its one all-reduce."""
-    from .GaussNet import hot_backward_rgb, hot_backward_rgb_step
-    B = _batch_size(batch)
-    sharded = world > 1 or sharding.force_collectives()
-    lo, hi = sharding.shard_range(B, rank, world) if sharded else (0, B)
-    Ns = s.numel() // 4
-    beta_1 = 1. - abs(beta)                                            # AS:332-334
-    if hi > lo:
-        wi, ori, vids = _batch_parts(batch, lo, hi) if sharded else _batch_parts(batch)
-        xr, cla, ori_cla, views, aux = net.attack_forward(s, wi, ori, vids)
-        stats.batch(epoch, cla.detach(), ori_cla.detach(), xr, views)
-        loss = torch.nn.functional.cross_entropy(cla, lab.broadcast_to([cla.shape[0]]), reduction='sum') / float(B)
-        if beta != 0.:
-            loss = beta_1 * loss
-        loss.backward()
-        if beta != 0.:                                                # d (beta mean((x_rgba - ori)^2)) / d x_rgba, mean over the WHOLE batch
-            _lib.check(stats.lib.nerfail_img_sqerr_grad_add(_lib.dev(xr.detach()), _ori_pointer_table(views), views.B, views.P, int(views.ori_u8),
-                                                            2. * float(beta) / (4. * views.P * B), _lib.dev(xr.grad), _lib.stream()))
-        if not sharded and getattr(net, 'fused_sign_step', True):
-            return hot_backward_rgb_step(aux, xr.grad, views, s, s_init, a, epsilon, targeted).view(s.shape)
-        buf = torch.empty((3 * Ns + 1,), dtype=torch.float32, device=xr.device)
-        hot_backward_rgb(aux, xr.grad, views, buf)
-        buf[3 * Ns] = loss.detach()
-    else:                                                             # more ranks than views: this rank only takes part in the sum
-        buf = torch.zeros((3 * Ns + 1,), dtype=torch.float32, device=_cuda())
-    if sharded:
-        sharding.all_reduce_sum_(buf, group)
-    return igsm_step_rgb(s, buf, s_init, a, epsilon, targeted).view(s.shape)
 
 
 class _ExportBuffers:
@@ -304,35 +286,25 @@ class _ExportBuffers:
         return self.bufs[shape]
 
 
-def _export_batch(net, best, batch, index, stats, epoch, world, rank, bufs, on_export):
+def _export_batch(net, best, batch, index, stats, epoch, group, bufs, on_export):
     """AS:310-317, 394-403 for one batch (this rank's views of it): the best tensor through the forward without gradient, the
     same statistics, then x_rgba and the unclipped mask image x as uint8 to the host in ONE copy."""
-    from .GaussNet import hot_forward, resolve_views
-    B = _batch_size(batch)
-    sharded = world > 1 or sharding.force_collectives()                  # (as _attack_batch)
-    lo, hi = sharding.shard_range(B, rank, world) if sharded else (0, B)
-    if hi <= lo:
+    parts = _share(batch, group)[0]
+    if parts is None:
         return
-    wi, ori, vids = _batch_parts(batch, lo, hi) if sharded else _batch_parts(batch)
-    lib = stats.lib
-    with torch.no_grad():
-        views = resolve_views(best, wi, ori, vids, net.keep_views_resident)
-        x, x_rgba, _ = hot_forward(best, views, net.epsilon, net._mm() if net.update_epsilon_3d else None, need_x=True)
-        net._ori_keep_src = getattr(views, '_ori_keep', None)
-        cla, ori_cla = net.cold_tail(x_rgba, views.ori_float, ori_key=net._ori_key(views))
-        net._ori_keep_src = None
-        stats.batch(epoch, cla, ori_cla, x_rgba, views)
-        if on_export is None:
-            return
-        d_u8, h_u8, ev = bufs.get(tuple(x_rgba.shape), x_rgba.device)     # (free again: every call waits for its own copy below)
-        n = x_rgba.numel()
-        _lib.check(lib.nerfail_export_u8(_lib.dev(x_rgba), n, _lib.dev(d_u8[0]), _lib.stream()))
-        _lib.check(lib.nerfail_export_u8(_lib.dev(x), n, _lib.dev(d_u8[1]), _lib.stream()))
-        h_u8.copy_(d_u8, non_blocking=True)
-        ev.record()
-        ev.synchronize()
+    x, x_rgba, cla, ori_cla, views = net.export_forward(best, *parts)
+    stats.batch(epoch, cla, ori_cla, x_rgba, views)
+    if on_export is None:
+        return
+    d_u8, h_u8, ev = bufs.get(tuple(x_rgba.shape), x_rgba.device)         # (free again: every call waits for its own copy below)
+    n = x_rgba.numel()
+    _lib.check(stats.lib.nerfail_export_u8(_lib.dev(x_rgba), n, _lib.dev(d_u8[0]), _lib.stream()))
+    _lib.check(stats.lib.nerfail_export_u8(_lib.dev(x), n, _lib.dev(d_u8[1]), _lib.stream()))
+    h_u8.copy_(d_u8, non_blocking=True)
+    ev.record()
+    ev.synchronize()
     arr = h_u8.numpy()
-    on_export(index, vids, arr[0].copy(), arr[1].copy())
+    on_export(index, parts[2], arr[0].copy(), arr[1].copy())
 
 
 def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=False, beta=0., export_batches=None,
@@ -374,7 +346,7 @@ def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=
         raise ValueError('beta must be in [-1, 1] (AS:332-336)')
     dev = _cuda()
     beta = float(beta)
-    world, rank = sharding.world_and_rank(group)
+    rank = sharding.world_and_rank(group)[1]
     label_i = int(label)                                              # (a device label is read once, before the first epoch)
     lab = torch.full((), label_i, dtype=torch.int64, device=dev)
     s_init = _lib.f32c(spatial, dev)
@@ -401,15 +373,15 @@ def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=
 
     for epoch in range(epochs - 1):
         for batch in (batches(epoch) if callable(batches) else batches):
-            s = _attack_batch(net, s, s_init, batch, lab, float(a), float(epsilon), bool(targeted), beta, stats, epoch, group, world, rank)
-        stats.close(epoch, group, world)
+            s = _attack_batch(net, s, s_init, batch, lab, float(a), float(epsilon), bool(targeted), beta, stats, epoch, group)
+        stats.close(epoch, group)
         stats.keep_if_taken(s, best)
         finish(epoch)
     epoch = epochs - 1
     exp = export_batches if export_batches is not None else batches
     for i, batch in enumerate(exp(epoch) if callable(exp) else exp):
-        _export_batch(net, best, batch, i, stats, epoch, world, rank, bufs, on_export)
-    stats.close(epoch, group, world)                                  # (its decision moves no tensor: the epoch ran on `best` itself)
+        _export_batch(net, best, batch, i, stats, epoch, group, bufs, on_export)
+    stats.close(epoch, group)                                         # (its decision moves no tensor: the epoch ran on `best` itself)
     finish(epoch)
     last_attack = records[-2] if epochs > 1 else None
     return AttackResult(best, s, records, last_attack['best_epoch'] if last_attack else -1,

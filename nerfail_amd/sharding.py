@@ -57,15 +57,17 @@ def _staged(t, group):
     return t.is_cuda and str(dist.get_backend(group)) == 'gloo'
 
 
+def _collective(group=None):
+    """Is a collective issued at all: a process group is up and has more than one rank (or force_collectives())."""
+    return dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force_collectives())
+
+
 def all_reduce_(t, op, group=None):
     """In-place all-reduce with `op` over ranks. RCCL all-reduce for HIP tensors whenever the group has a device-capable backend
     ('nccl', a 'cpu:gloo,cuda:nccl' pair, or the default-initialised group that maps to it): the GPU-box path, xGMI. Only under
     a pure 'gloo' group (the CPU tests and the one-GPU rehearsal, where RCCL refuses two ranks on one device) a HIP tensor is
     staged through a pinned host buffer (kept per size), reduced there and copied back."""
-    if not (dist.is_available() and dist.is_initialized()):
-        return t
-    world = dist.get_world_size(group)
-    if world <= 1 and not force_collectives():
+    if not _collective(group):
         return t
     if _staged(t, group):
         h = _stage(t)
@@ -77,18 +79,26 @@ def all_reduce_(t, op, group=None):
     return t
 
 
-def all_reduce_sum_(t, group=None):
-    """In-place sum over ranks (all_reduce_ with SUM)."""
-    return all_reduce_(t, dist.ReduceOp.SUM, group) if dist.is_available() else t
+def all_reduce_sum_(t, group=None, timing=None):
+    """In-place sum over ranks (all_reduce_ with SUM). `timing`: optional dict; when a collective is issued on a HIP tensor it
+    gets the HIP events around it and the bytes moved, appended to timing['allreduce_events'] as (start, end, bytes)."""
+    if not _collective(group):
+        return t
+    timed = timing is not None and t.is_cuda
+    if timed:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    all_reduce_(t, dist.ReduceOp.SUM, group)
+    if timed:
+        e1.record()
+        timing.setdefault('allreduce_events', []).append((e0, e1, t.numel() * t.element_size()))
+    return t
 
 
 def broadcast_(t, src=0, group=None):
     """In-place broadcast of group rank `src`'s tensor to every rank, on the same two paths as all_reduce_: RCCL on the
     device, or - HIP tensor under pure gloo - through the pinned host buffer. `t` must be contiguous."""
-    if not (dist.is_available() and dist.is_initialized()):
-        return t
-    world = dist.get_world_size(group)
-    if world <= 1 and not force_collectives():
+    if not _collective(group):
         return t
     gsrc = dist.get_global_rank(group, src) if group is not None else src
     if _staged(t, group):

@@ -177,6 +177,37 @@ def test_beta_zero_last_is_bitwise_nerfail_s_loop(g):
         assert torch.equal(res.last, want.view(res.last.shape)), tag
 
 
+@pytest.mark.parametrize('fused', (True, False))
+def test_every_iterate_of_an_epoch_is_bitwise_nerfail_s_step(g, fused):
+    """One attack epoch of nerfail_s with beta == 0 against nerfail_s_step fed the same batches one by one, with the sign step
+    fused into the gather backward and as a kernel of its own: the loop and the step are one body, iterate by iterate."""
+    from nerfail_amd import attack
+    targeted, beta, label = AP.run_args(g, 'untargeted')
+    assert beta == 0.
+    net, s0, train, export = AP.setup(g, dev())
+    net.fused_sign_step = fused
+    calls, orig = [], attack._attack_batch
+
+    def spy(net_, s, s_init, batch, *a, **k):
+        out = orig(net_, s, s_init, batch, *a, **k)
+        calls.append((s, batch, out))
+        return out
+    attack._attack_batch = spy
+    try:
+        res = attack.nerfail_s(net, s0, train, label, 2, float(g['a']), float(g['epsilon']), targeted, beta, export_batches=export, log=None)
+    finally:
+        attack._attack_batch = orig
+    assert len(calls) == len(train) == 2
+    net2, s0b, _, _ = AP.setup(g, dev())
+    net2.fused_sign_step = fused
+    s = s0b
+    for s_in, batch, s_out in calls:
+        assert torch.equal(s_in, s)
+        s, _ = attack.nerfail_s_step(net2, s, s0b, batch[0], batch[1], torch.tensor(label, device=dev()), float(g['a']), float(g['epsilon']), targeted)
+        assert torch.equal(s, s_out) and not torch.equal(s, s_in)
+    assert torch.equal(res.last, s)
+
+
 def test_one_epoch_exports_the_initial_tensor(g):
     from nerfail_amd.GaussNet import gauss_gather
     exported = []

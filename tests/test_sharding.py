@@ -65,6 +65,20 @@ def _worker(rank, world, port, out_dir):
     out = OG.igsm_step(a['s0'], g.numpy(), a['s0'], PB.A, PB.EPS, False)
     np.save(os.path.join(out_dir, 'rank%d.npy' % rank), out)
     np.save(os.path.join(out_dir, 'grad%d.npy' % rank), g.numpy())
+    # the timed all-reduce on a CPU tensor: the same sum as without `timing`, and no event recorded (nothing is on the device)
+    timing, t = {}, torch.arange(4.) + rank
+    timed, plain = sharding.all_reduce_sum_(t.clone(), timing=timing), sharding.all_reduce_sum_(t.clone())
+    assert torch.equal(timed, plain) and torch.equal(plain, 2 * torch.arange(4.) + 1) and timing == {}
+    # the rgb form with the maps as a Python list of per-view tensors and no ids: the stacked tensor's buffer, bit for bit
+    # (one thread: the stand-in's scatter-add backward sums in thread order, so two calls on the SAME input differ otherwise)
+    import nerfail_amd.GaussNet as GNm
+    torch.set_num_threads(1)
+    attack._cuda = lambda: torch.device('cpu')
+    GNm.hot_backward_rgb = _stand_in_hot_backward_rgb
+    anet, label = _StandInAttackNet(torch.from_numpy(a['cls_w'])), torch.tensor(PB.LABEL)
+    stacked = attack.sharded_perturbation_grad_rgb(anet, s0, torch.from_numpy(wi), ori, label)
+    listed = attack.sharded_perturbation_grad_rgb(anet, s0, list(torch.from_numpy(wi)), ori, label)
+    assert float(stacked[:-1].abs().max()) > 1e-6 and float(stacked[-1]) > 0 and torch.equal(listed, stacked)
     dist.destroy_process_group()
     if rank == 0:                                               # the same product function, no process group: 1 rank
         full, loss1 = attack.sharded_perturbation_grad(net, s0, torch.from_numpy(wi), ori, torch.tensor(PB.LABEL))
@@ -100,7 +114,7 @@ class _StandInAttackNet:
         self.cls_w = cls_w
 
     def hot(self, s, wi, ori):
-        return self.full(s, wi, ori)[1]
+        return self.full(s, torch.stack(wi) if isinstance(wi, list) else wi, ori)[1]
 
     def attack_forward(self, s, wi, ori, view_ids=None):
         x_rgba = self.hot(s.detach(), wi, ori).detach().requires_grad_(True)
