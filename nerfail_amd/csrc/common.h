@@ -192,6 +192,17 @@ __device__ __forceinline__ void pair_put(float* p, double v) {
 // One colour byte of a BGRA dword on the white background of MT:237-254 / MD:98-105: the byte where alpha > 0, else 255.
 __device__ __forceinline__ float white_u8(unsigned w, int shift) { return (w >> 24) > 0u ? (float)((w >> shift) & 255u) : 255.f; }
 
+// Row of a table with last + 1 rows that a float32 index names (indices travel as float32, GN:62 / CI:148): .type(torch.long)
+// truncates, and every user of the pixel <-> 3-D-point map (K10's gather, K11's scatter, the inverted index) must resolve the
+// same float to the same row. The value is clamped to [0, last] AS A FLOAT first (v_med3_f32; NaN -> 0), so the conversion
+// itself is always in range - an out-of-range float -> int conversion is undefined in C++ and the in-bounds guarantee of a
+// memory access must not rest on it; through int32, not int64 (~10 vector instructions per index less). The
+// integer minimum behind it takes care of (float)last rounding up (last >= 2^24). Callers check last < 2^31.
+__device__ __forceinline__ int index_row(float fi, int last) {
+    const int j = (int)__builtin_amdgcn_fmed3f(fi, 0.f, (float)last);
+    return j > last ? last : j;
+}
+
 // pts = o + d*z with the reference's rounding (multiply, then add; no FMA): RN:381
 __device__ __forceinline__ float mul_add_rn(float a, float b, float c) { return __fadd_rn(__fmul_rn(a, b), c); }
 

@@ -157,13 +157,9 @@ __global__ __launch_bounds__(256) void gauss_fwd_views_kernel(const float4* __re
             const int last = (int)Ns - 1;     // (the launcher checks Ns < 2^31)
 #pragma unroll
             for (int k = 0; k < 8; ++k) {     // issue all 8 gathers before using any
-                // .type(torch.long): truncation (GN:62). Through int32 (round 4; the 64-bit conversion cost ~10 vector instructions
-                // per index, 80 of this kernel's 286 per wave). The value is clamped to [0, Ns-1] AS A FLOAT first (v_med3_f32;
-                // NaN -> 0), so the conversion itself is always in range - an out-of-range float -> int conversion is undefined in
-                // C++ and the in-bounds guarantee of the gather must not rest on it. Same row as before for every float.
-                int j = (int)__builtin_amdgcn_fmed3f(fi[k], 0.f, (float)last);
-                j = j > last ? last : j;      // ((float)last may round up)
-                rows[k] = spatial[j];         // unconditional: a per-gather "skip if w == 0" branch serialises the 8 loads
+                // .type(torch.long): truncation (GN:62), clamped to [0, Ns-1] as a float before the conversion (index_row, common.h:
+                // the one rule K11 and the inverted index share)
+                rows[k] = spatial[index_row(fi[k], last)];   // unconditional: a per-gather "skip if w == 0" branch serialises the 8 loads
             }
         }
         typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -230,9 +226,7 @@ __global__ __launch_bounds__(256) void gauss_bwd_kernel(const float* __restrict_
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         if (w[k] == 0.f) continue;
-        long j = (long)fi[k];
-        j = j < 0 ? 0 : (j >= Ns ? Ns - 1 : j);
-        float* dst = grad_spatial + 4 * j;
+        float* dst = grad_spatial + 4 * (long)index_row(fi[k], (int)Ns - 1);     // the forward's row (the launcher checks Ns < 2^31)
         atomicAdd(dst + 0, w[k] * gx.x);
         atomicAdd(dst + 1, w[k] * gx.y);
         atomicAdd(dst + 2, w[k] * gx.z);
@@ -387,6 +381,7 @@ extern "C" int nerfail_gauss_bwd(const float* weight_and_index, const float* ori
     if (B * P == 0) return NERFAIL_OK;
     NF_REQUIRE(weight_and_index != nullptr && ori_img != nullptr && x != nullptr, "NULL input pointer");
     NF_REQUIRE(grad_spatial != nullptr, "grad_spatial is NULL");
+    NF_REQUIRE(Ns < (1L << 31), "the perturbation table must have fewer than 2^31 rows");
     if (grad_x == nullptr && grad_x_rgba == nullptr) return NERFAIL_OK;
     gauss_bwd_kernel<<<dim3((unsigned)((B * P + 255) / 256)), dim3(256), 0, as_stream(stream)>>>(
         weight_and_index, (const float4*)ori_img, (const float4*)x, (const float4*)grad_x, (const float4*)grad_x_rgba, Ns,

@@ -22,8 +22,7 @@ __global__ __launch_bounds__(256) void csr_keys_kernel(const float* __restrict__
     const long bp = g >> 3;
     const int k = (int)(g & 7);
     const long b = bp / P, p = bp - b * P;
-    long j = (long)wi[((b * 2 + 1) * P + p) * 8 + k];
-    j = j < 0 ? 0 : (j >= Ns ? Ns - 1 : j);
+    const int j = index_row(wi[((b * 2 + 1) * P + p) * 8 + k], (int)Ns - 1);     // the forward's row (the caller checks Ns < 2^31 - 1)
     // A contribution with weight 0 adds w * g = 0 to its row: it is left out of the index (key Ns sorts it behind the last
     // row, row_ptr[Ns] ends before it). On real maps that is most of them: a background pixel's 3-D point (near plane,
     // NC:418-423) is far from every point of the set, all 8 Gaussian weights underflow to 0 (GN:181), and its 8
