@@ -7,8 +7,9 @@
 //   query:  one WAVE per 64 queries (an 8 x 8 pixel tile of a view, or 64 consecutive queries). The key of a candidate is
 //           (d2, index), d2 = ((dx*dx + dy*dy) + dz*dz) in float32 without FMA - exactly the brute-force arithmetic - and
 //           the 8 smallest keys win. A box of the grid (cell, 4^3 cells, 16^3 cells) or a point is skipped only when a lower
-//           bound of its distance, shrunk by the safety factor 0.999 (far above float32 rounding), is STRICTLY above the
-//           current 8th distance: nothing skipped can enter the result or tie with it, whatever the visiting order.
+//           bound of its distance - to the drawn box grown by kBinSlack, which then holds every point BINNED into it -,
+//           shrunk by the safety factor 0.999 (far above float32 rounding), is STRICTLY above the current 8th distance:
+//           nothing skipped can enter the result or tie with it, whatever the visiting order.
 //           Coherent waves (queries within 6 cells of each other) search together, wave-uniformly (see the kernel);
 //           scattered queries first walk Chebyshev shells R = 0..3 around their own cell, one lane per query, and stop
 //           when the 8th distance lies inside the visited block; what is left joins the wave search.
@@ -109,6 +110,24 @@ __global__ __launch_bounds__(256) void cell_start_kernel(const unsigned* __restr
 constexpr int kCoarse = 4;
 constexpr int kSuper = 4;         // coarse cells per side of a super block
 constexpr int kShellCap = 3;          // fine shells (beyond the query's own cell) before the coarse search takes over
+
+// A point is BINNED by cell_coord - floorf(fl(fl(v - o) * inv_cs)) - but every bound that excludes a box is taken from the box
+// as DRAWN, o + x * cs. The two disagree near a face, and the 0.999 factor is relative: it covers nothing when the bound is a few
+// float steps (points 3e-11 apart next to x = 0 in a set that spans [-1.45, 1.45]: the binning changes cell 2047 float steps of v
+// away from the drawn face - tests/knn_edge_inputs.py). So every drawn box is grown by an ABSOLUTE slack on every side before
+// a distance to it is taken: each per-axis gap e becomes max(e - slack, 0). With u = 2^-24, A = max |o_a|, E = cs * 16 * Gs (the
+// extent of the drawn blocks, >= cs * G; every face f = o + x * cs has |f| <= A + E):
+//   binning   fl(v - o), inv_cs = fl(1 / cs) and their product round once each: t = ((v - o) / cs) (1 + th), |th| <= 3.01 u, so a
+//             point binned into cell x lies within 3.01 u E of the true box [o + x cs, o + (x + 1) cs]; the same holds for the
+//             coarse cells and blocks, which are unions of cells (the clamp never acts on a point of the set: t < G / 1.0001 (1 + th));
+//   drawing   fl(x * cs) is off by <= u E, the sum fl(o + .) by <= u (A + E) (fused: the second alone); an upper face taken as
+//             fl(lo + size) rounds once more, <= u (A + E): a drawn face lies within u (2 A + 3 E) of the true one.
+// Together <= u (2 A + 6.01 E) < 6.01 u (A + E). The slack is 8 u (A + E) = 2^-21 (A + E): the rest covers its own three roundings.
+// What remains after the slack is relative - fl(lo - q), fl(e - slack), the squares, the sums, sqrtf, d2 itself: each (1 + u) -
+// and stays under the 0.999 factor as before. On a scene (A + E ~ 4, cell 0.023) the slack is 1e-4 of a cell.
+// The per-point bound of scan_uniform needs none: it is taken between a point's own coordinates and the box of the wave's
+// queries - no drawn box takes part.
+constexpr float kBinSlack = 0x1p-21f;
 
 // points per coarse cell = sum over its 16 x-rows of 4 consecutive fine cells
 __global__ __launch_bounds__(256) void coarse_count_kernel(const int* __restrict__ cell_start, int G, int Gc, int* __restrict__ cnt) {
@@ -226,6 +245,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
 #pragma unroll
     for (int k = 0; k < 8; ++k) fk[k] = kWorstKey;
     unsigned examined = 0u;             // candidate points this query computed a distance to (reported through `stats`)
+    // every drawn box grows by this much on every side before a distance to it is taken (kBinSlack; 16 * Gs cells per axis are drawn)
+    constexpr int kBlockCells = kSuper * kCoarse;
+    const float slack = kBinSlack * (fmaxf(fmaxf(fabsf(g.ox), fabsf(g.oy)), fabsf(g.oz)) + g.cs * (float)((G + kBlockCells - 1) / kBlockCells * kBlockCells));
 
     const int Gc = (G + kCoarse - 1) / kCoarse, Gs = (Gc + kSuper - 1) / kSuper;
     // ---- scattered queries: one lane per query walks the Chebyshev shells R = 0..kShellCap around its own cell (returns
@@ -271,11 +293,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
             for (int z = z0; z <= z1; ++z) {
                 const bool zface = (z == cz - R) || (z == cz + R);
                 const float cz0 = g.oz + (float)z * g.cs;
-                const float ez = fmaxf(fmaxf(cz0 - qz, qz - (cz0 + g.cs)), 0.f);
+                const float ez = fmaxf(fmaxf(cz0 - qz, qz - (cz0 + g.cs)) - slack, 0.f);
                 for (int y = y0; y <= y1; ++y) {
                     const bool yface = zface || (y == cy - R) || (y == cy + R);
                     const float cy0 = g.oy + (float)y * g.cs;
-                    const float ey = fmaxf(fmaxf(cy0 - qy, qy - (cy0 + g.cs)), 0.f);
+                    const float ey = fmaxf(fmaxf(cy0 - qy, qy - (cy0 + g.cs)) - slack, 0.f);
                     const float eyz = ey * ey + ez * ez;
                     if (R > 0 && cannot_improve_shell(eyz)) continue;              // the whole row is too far
                     // on a z / y face of the shell the whole x row belongs to it; otherwise only the two end cells x = cx -+ R do
@@ -288,7 +310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
                             for (int x = x0; x <= x1; ++x) {
                                 const int e = cell_start[row + x + 1];
                                 const float cx0 = g.ox + (float)x * g.cs;
-                                const float ex = fmaxf(fmaxf(cx0 - qx, qx - (cx0 + g.cs)), 0.f);
+                                const float ex = fmaxf(fmaxf(cx0 - qx, qx - (cx0 + g.cs)) - slack, 0.f);
                                 if (e > b && !cannot_improve_shell(ex * ex + eyz)) scan_points(sorted, b, e, qx, qy, qz, fk, examined);
                                 b = e;
                             }
@@ -299,14 +321,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
                             const int x = side ? cx + R : cx - R;
                             if (x < 0 || x >= G || (side == 1 && R == 0)) continue;
                             const float cx0 = g.ox + (float)x * g.cs;
-                            const float ex = fmaxf(fmaxf(cx0 - qx, qx - (cx0 + g.cs)), 0.f);
+                            const float ex = fmaxf(fmaxf(cx0 - qx, qx - (cx0 + g.cs)) - slack, 0.f);
                             if (cannot_improve_shell(ex * ex + eyz)) continue;
                             scan_points(sorted, cell_start[row + x], cell_start[row + x + 1], qx, qy, qz, fk, examined);
                         }
                     }
                 }
             }
-            // every unvisited point is outside the block [c-R, c+R]^3: lower bound of its distance to the query
+            // every unvisited point is BINNED outside the block [c-R, c+R]^3: lower bound of its distance to the query (the
+            // drawn faces of the block, less the slack)
             float bound = INFINITY;
             if (cx - R > 0) bound = fminf(bound, qx - (g.ox + (float)(cx - R) * g.cs));
             if (cx + R < G - 1) bound = fminf(bound, (g.ox + (float)(cx + R + 1) * g.cs) - qx);
@@ -315,6 +338,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
             if (cz - R > 0) bound = fminf(bound, qz - (g.oz + (float)(cz - R) * g.cs));
             if (cz + R < G - 1) bound = fminf(bound, (g.oz + (float)(cz + R + 1) * g.cs) - qz);
             if (bound == INFINITY) { done = true; break; }      // the block covers the whole grid
+            bound -= slack;
             if (bound > 0.f) {
                 const float sb = 0.999f * bound;
                 if (key_d2(fk[7]) < sb * sb) { done = true; break; } // strict: nothing unvisited can enter or tie
@@ -354,7 +378,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
             const float md = 0.999f * sqrtf(d2box);
             return __ballot(far && !(d8() < md * md)) != 0ull;
         };
-        auto axis_d = [](float lo, float size, float q) { return fmaxf(fmaxf(lo - q, q - (lo + size)), 0.f); };
+        auto axis_d = [&](float lo, float size, float q) { return fmaxf(fmaxf(lo - q, q - (lo + size)) - slack, 0.f); };
         // box of the wave's far queries
         const float blx = wave_minmax_uniform<false>(far ? qx : INFINITY), bhx = wave_minmax_uniform<true>(far ? qx : -INFINITY);
         const float bly = wave_minmax_uniform<false>(far ? qy : INFINITY), bhy = wave_minmax_uniform<true>(far ? qy : -INFINITY);
@@ -363,9 +387,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
         auto lane_i = [](int v, int l) { return __builtin_amdgcn_readlane(v, l); };
         auto lane_f = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
         auto wave_box_d2 = [&](float x0, float y0, float z0, float size) {   // lower bound of |q - p|, p in the cube, for EVERY far query of the wave
-            const float ddx = fmaxf(fmaxf(x0 - bhx, blx - (x0 + size)), 0.f);
-            const float ddy = fmaxf(fmaxf(y0 - bhy, bly - (y0 + size)), 0.f);
-            const float ddz = fmaxf(fmaxf(z0 - bhz, blz - (z0 + size)), 0.f);
+            const float ddx = fmaxf(fmaxf(x0 - bhx, blx - (x0 + size)) - slack, 0.f);
+            const float ddy = fmaxf(fmaxf(y0 - bhy, bly - (y0 + size)) - slack, 0.f);
+            const float ddz = fmaxf(fmaxf(z0 - bhz, blz - (z0 + size)) - slack, 0.f);
             return ddx * ddx + ddy * ddy + ddz * ddz;
         };
         auto wave_d8max = [&]() { return wave_minmax_uniform<true>(far ? d8() : 0.f); };

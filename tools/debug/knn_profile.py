@@ -60,10 +60,13 @@ started = np.sort(st)
 print('far waves started by 50 us: %d, 250 us: %d, 1000 us: %d, 2000 us: %d' % tuple(int((started <= x).sum()) for x in (50, 250, 1000, 2000)))
 ex = np.array(v[16 + 5 * NW:16 + 6 * NW], dtype=np.float64)
 nm = ~m
-print('waves WITHOUT far lanes: %d; us: median %.0f p90 %.0f p99 %.0f max %.0f; sum %.1f ms-waves; candidates per lane: median %.0f p99 %.0f max %.0f'
-      % (nm.sum(), np.median(t[nm]), np.percentile(t[nm], 90), np.percentile(t[nm], 99), t[nm].max(), t[nm].sum() / 1e3,
-         np.median(ex[nm]) / 64, np.percentile(ex[nm], 99) / 64, ex[nm].max() / 64))
-for w in np.argsort(-np.where(nm, t, 0))[:8]:
+if not nm.any():                  # (a view tile is one group: every wave of this geometry takes the wave search)
+    print('waves WITHOUT far lanes: 0')
+else:
+    print('waves WITHOUT far lanes: %d; us: median %.0f p90 %.0f p99 %.0f max %.0f; sum %.1f ms-waves; candidates per lane: median %.0f p99 %.0f max %.0f'
+          % (nm.sum(), np.median(t[nm]), np.percentile(t[nm], 90), np.percentile(t[nm], 99), t[nm].max(), t[nm].sum() / 1e3,
+             np.median(ex[nm]) / 64, np.percentile(ex[nm], 99) / 64, ex[nm].max() / 64))
+for w in np.argsort(-np.where(nm, t, 0))[:8 if nm.any() else 0]:
     print('  wave %5d (row %3d, col %3d..)  candidates per lane %7.0f  %.0f us' % (w, (w // (W // 8)) * 8, (w % (W // 8)) * 8, ex[w] / 64, t[w]))
 allst, allen = (t0 - t0.min()) / 100.0, (t0 - t0.min()) / 100.0 + t
 for mid in (125., 625., 1125., 1625., 2375., 3125.):
