@@ -711,6 +711,57 @@ int nerfail_cnn_sgd_step(float* params, const float* grads, float* momentum_buf,
 int nerfail_cls_epoch_close(const float* train_row, const float* val_row, int64_t n_train, int64_t n_val, float* best, int epoch,
                             float* record, int32_t* flag, void* stream);
 
+/* ------------------------------------------------------------------ DeepFool gate and step (deepfool revision 1) -- */
+
+/* One DeepFool iteration of the universal attack (deepfool.py:53-105 = DF) without a torch op between the classifier and the
+ * table: the break test and the margins f' on one wave, then the norms, the choice of the competing class and the update of
+ * the table in one call. Like the three sections before it this one only ADDS entry points: NERFAIL_ABI_VERSION stays 14,
+ * nerfail_abi_revision() stays 15, nerfail_eval_revision() and nerfail_cls_revision() stay 1, and the additions are announced
+ * by nerfail_deepfool_revision() = 1. nerfail_deepfool_norms and nerfail_deepfool_apply are unchanged. No allocation, no
+ * synchronisation, no atomics; the same bits on every run.
+ *
+ * The record one iteration's gate leaves for its step and for the host: 80 bytes of device memory, written with plain stores.
+ * The host reads the first two words (one copy of 8 bytes per iteration: the loop's only wait). */
+#define NERFAIL_DEEPFOOL_MAX_COMPETITORS 8
+typedef struct nerfail_deepfool_record {
+    int32_t done;      /* 1: the loop breaks before this iteration's step (DF:62-66); 0 also for a row that holds a NaN */
+    int32_t argmax;    /* first maximum of the bumped logits (DF:59); -1 when the row holds a NaN */
+    int32_t n_comp;    /* competitors: C - 1 untargeted (every k != o, ascending), 1 targeted ([target]) */
+    int32_t targeted;  /* 0 / 1 */
+    int32_t cls[NERFAIL_DEEPFOOL_MAX_COMPETITORS];   /* competitor r's class id; -1 from n_comp on */
+    float fabs[NERFAIL_DEEPFOOL_MAX_COMPETITORS];    /* |f'| of competitor r (DF:79 / :93), from the BUMPED logits; 0 from n_comp on */
+} nerfail_deepfool_record;
+int nerfail_deepfool_revision(void);
+
+/* DF:53-66 and the f' of DF:79 / :93 for one view, on one wave. cla: the [1,C] float32 logits of this iteration, 2 <= C <= 8;
+ * o: the clean argmax, 0..C-1; target: -1 untargeted, else 0..C-1. Float32, in the reference's order:
+ *   cla_b[c] = cla[c] + m1 for c == o (untargeted) or for every c != target (targeted), else cla[c]
+ *   argmax   = the FIRST maximum of cla_b;   done = argmax != o (untargeted) / argmax == target (targeted)
+ *   fabs[r]  = |cla_b[k_r] - (cla_b[o] + m2)| for the competitors k_r (the in-place bump of DF:54-57 makes the reference read
+ *              the bumped values too)
+ * A row holding a NaN (after the bump) has argmax -1 and is never done. Anything else is NERFAIL_EINVAL before the launch. */
+int nerfail_deepfool_gate(const float* cla, int C, int o, int target, float m1, float m2, nerfail_deepfool_record* record,
+                          void* stream);
+
+/* DF:68-105 once the gradients exist. grads = [n_rhs][n,4], slice 0 the original class, slice r + 1 competitor r of the
+ * record; n_rhs = record->n_comp + 1. Three launches: nerfail_deepfool_norms' first stage; one workgroup that finishes the
+ * norms (the same fixed tree, the same bits as nerfail_deepfool_norms) and chooses; nerfail_deepfool_apply's kernel. The
+ * choice, float32, one rounding per operation, no fused multiply-add:
+ *   nrm_r = sqrt(norms2_r);   value_r = fabs[r] / (nrm_r + 1e-4f), a NaN counting as +inf;   best = the FIRST minimum (the
+ *   strict < of DF:84; nothing is chosen when every value is +inf);   scale = fabs[best] / (nrm_best * nrm_best + 1e-4f) - the
+ *   norm squared again, as DF:85 does, not norms2;   targeted: competitor 0 without a comparison (DF:92-96).
+ * Nothing chosen: scale = 0, rot is left alone, *trace_slot = -1; else *trace_slot = cls[best]. A record whose n_comp is not
+ * n_rhs - 1 chooses nothing: what the device read never becomes an address outside slices 1..n_rhs-1. Then
+ *   rot += scale * (grads[best + 1] - grads[0]);   spatial_out = clamp(spatial_init + overshoot * rot, -255, 255), alpha
+ *   channel copied from spatial_init (DF:98-105).
+ * scratch: nerfail_deepfool_step_scratch_bytes(n_rhs, n) bytes, 8-byte aligned (0 for n_rhs outside 2..8 or n <= 0): the
+ * partials, then {norms2[8], best, scale}; contents unspecified on return. trace_slot: a device int32 - the caller points it
+ * at slot loop_i of a trace array. rot is updated in place; spatial_out may alias nothing else. */
+size_t nerfail_deepfool_step_scratch_bytes(int n_rhs, int64_t n);
+int nerfail_deepfool_step(const float* grads, int n_rhs, int64_t n, const nerfail_deepfool_record* record, void* scratch,
+                          size_t scratch_bytes, float overshoot, const float* spatial_init, float* rot, float* spatial_out,
+                          int32_t* trace_slot, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

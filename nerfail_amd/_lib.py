@@ -15,6 +15,9 @@ ABI_VERSION = 14
 ABI_REVISION = 15                        # additions since ABI_VERSION (nerfail_abi_revision): the NeRFail-S epoch statistics
 EVAL_REVISION = 1                        # nerfail_eval_revision: the attack-evaluation entry points (model_test)
 CLS_REVISION = 1                         # nerfail_cls_revision: the victim-training entry points (model_train)
+DEEPFOOL_REVISION = 1                    # nerfail_deepfool_revision: the DeepFool gate and step (deepfool.deepfool_native)
+DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
+DEEPFOOL_RECORD_WORDS = 4 + 2 * DEEPFOOL_MAX_COMPETITORS    # struct nerfail_deepfool_record as 32-bit words
 EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
 EVAL_VIEW_DOUBLES = 6                    # NERFAIL_EVAL_VIEW_DOUBLES: one view's row
 EVAL_RECORD_DOUBLES = 16 + 32            # NERFAIL_EVAL_RECORD_DOUBLES: the set record of nerfail_eval_fold
@@ -174,6 +177,10 @@ SIGNATURES = {
     'nerfail_cls_ce': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
     'nerfail_cnn_sgd_step': (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_i, c_p]),
     'nerfail_cls_epoch_close': (c_i, [c_p, c_p, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p]),
+    'nerfail_deepfool_revision': (c_i, []),
+    'nerfail_deepfool_gate': (c_i, [c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
+    'nerfail_deepfool_step_scratch_bytes': (ctypes.c_size_t, [c_i, c_i64]),
+    'nerfail_deepfool_step': (c_i, [c_p, c_i, c_i64, c_p, c_p, ctypes.c_size_t, c_f, c_p, c_p, c_p, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -232,6 +239,9 @@ def load():
     if lib.nerfail_cls_revision() != CLS_REVISION:
         raise RuntimeError('nerfail_amd: victim-training revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_cls_revision(), CLS_REVISION))
+    if lib.nerfail_deepfool_revision() != DEEPFOOL_REVISION:
+        raise RuntimeError('nerfail_amd: DeepFool revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_deepfool_revision(), DEEPFOOL_REVISION))
     _lib = lib
     return lib
 

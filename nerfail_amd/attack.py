@@ -386,3 +386,221 @@ def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=
     last_attack = records[-2] if epochs > 1 else None
     return AttackResult(best, s, records, last_attack['best_epoch'] if last_attack else -1,
                         last_attack['best_acc'] if last_attack else None)
+
+
+# ---------------------------------------------------------------------------------------------- the product loop (AN:269-512)
+class NerfailResult:
+    """What nerfail returns. `best`: the table the rule of AN:490-503 kept (device tensor) - the attack's result, what the export
+    epoch rendered; `last`: the table the loop ended on (after an export epoch the reference's table IS the best tensor,
+    AN:345, so `last` then aliases it until the rule replaces `best` by a copy); `m1_best`, `m2_best`, `best_acc`: what the rule
+    recorded with `best`; `stats`: one dict per PASS over the views (a pass is one turn of AN:311's while loop; `epoch` is the
+    epoch it ran as, `next_epoch` where the loop went); `need_to_log_dict`: the reference's, keyed "m1-<m1> epoch-<epoch>"
+    with the values AFTER the pass's m1 / epoch update, as AN:485 forms them."""
+
+    def __init__(self, best, last, m1_best, m2_best, best_acc, stats, need_to_log_dict):
+        self.best, self.last, self.m1_best, self.m2_best, self.best_acc = best, last, m1_best, m2_best, best_acc
+        self.stats, self.need_to_log_dict = stats, need_to_log_dict
+
+
+class _PassStats:
+    """One pass's running sums of AN:358-376 in a device row (nerfail_attack_logit_stats): what _export_batch calls `stats`."""
+
+    def __init__(self, label, dev):
+        self.lib = _lib.load()
+        self.label = int(label)
+        self.row = torch.zeros((_lib.ATTACK_ROW_FLOATS,), dtype=torch.float32, device=dev)
+
+    def batch(self, epoch, cla, ori_cla, x_rgba=None, views=None):
+        c, oc = _lib.f32c(cla), _lib.f32c(ori_cla)
+        _lib.check(self.lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], self.label, _lib.dev(self.row),
+                                                       _lib.stream()))
+
+    def read(self, minmax):
+        """THE host read of a pass: the four sums as AN:476-480 divides them, and epsilon_3d's [min, max]."""
+        v = torch.cat([self.row, minmax]).cpu().tolist()
+        return dict(test_sum=v[0] + v[1], attack_sum=v[2] + v[3], test_correct=int(v[4]), attack_correct=int(v[5]), seen=int(v[6]),
+                    epsilon_3d_min=v[-2], epsilon_3d_max=v[-1])
+
+
+def _pass_done(index, table):
+    """Called at the end of every pass with the table as the pass left it (the seam at which the tests record it)."""
+
+
+def _same_class(cla, ori_cla):
+    """AN:387-392: the raw (unbumped) argmax of the attacked logits equals the clean one. One small host read per visit."""
+    return bool(torch.argmax(cla[0]) == torch.argmax(ori_cla[0]))
+
+
+def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df_max_iter=1000, overshoot=0.02, num_classes=8,
+            m2_max_limit=10000, accumulate_incomplete=False, export_views=None, on_export=None, log=print, native=None):
+    """The NeRFail universal attack, attack_NeRFail.py:269-512 (= AN), as one call: the counterpart of nerfail_s.
+
+    `spatial`: the perturbation table [P,H,W,4]. `views`: a list of batch-1 items `(weight_and_index, ori_img[, view_id])`, or a
+    callable of the pass number that returns such a list (the reshuffled gauss_dataset_rand_select loader of AN:246-249).
+    `label`: the views' class, or the target class when `targeted`. `m1`, `m2`: the two margins (args.m1 / args.m2).
+
+    The loop is the reference's, quirks included. `while epoch < epochs` steps `epoch` itself. A pass before the last epoch
+    visits every view: open_update_epsilon_3d, the forward, the four running sums of AN:358-376 (in a device row: no host read
+    per view for them), close_update_epsilon_3d, and - only when the raw argmax of the attacked logits still equals the clean
+    one (AN:387-394) - DeepFool on the view; its perturbation is added to the table when it finished before df_max_iter (or
+    `accumulate_incomplete`), else the m2 * 10 rule of AN:410-418 counts it (m2 is reset at the start of every pass, AN:332).
+    A pass that changed nothing at epoch 0 bisects m1 downwards between m1_list = [0, m1] (AN:442-453) and runs epoch 0 again -
+    at any other epoch it jumps to the last epoch; the last epoch is the export epoch: the BEST tensor, without gradient, over
+    `export_views` (default: the views; `on_export(index, view_ids, adv_u8, mask_u8)` per view as in nerfail_s), after which m1
+    is bisected upwards and the loop returns to epoch 0 while m1 < m1_list[1] (AN:456-468) - the table is then NOT reset: it is
+    the best tensor itself. Each pass ends with its means (sums / views of the pass), print_epsilon, epsilon_3d_zero and the
+    best rule of AN:490-503 with the m1 / m2 the bisection just set.
+
+    Host reads: one per visit for the skip decision, DeepFool's own (deepfool_native: one per iteration), one per pass for the
+    record and the log lines. `native=None` runs deepfool.deepfool_native (which itself falls through to the mirror where it
+    does not apply), `native=False` the mirror deepfool.deepfool (a resident view given by name alone is handed to it as the tensors
+    the visit's forward resolved). An export epoch without views is a ValueError. The update is sequential over the views: there is nothing to
+    shard, and more than one rank is a ValueError.
+
+    Returns a NerfailResult. Every dict of `stats` holds m1 / m2 (at the end of the pass), m1_pass (the m1 the pass ran with),
+    epoch, next_epoch, test_loss, test_acc, attack_loss, attack_acc, views, skipped, attacked, completed, deepfool_iters,
+    m2_raises, taken, epsilon_3d_min, epsilon_3d_max and `visits`: per visit (position in the pass, skipped, iter_k, the chosen
+    class of every iteration or None with the mirror)."""
+    import time
+    from . import deepfool as DF
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    exp = export_views if export_views is not None else views
+    if not callable(exp) and len(exp) == 0:                               # (nothing would set tensor_not_changed: the loop could not end)
+        raise ValueError('nerfail: the export epoch needs at least one view (export_views is empty)')
+    if sharding.world_and_rank(None)[0] > 1:
+        raise ValueError('nerfail updates the table view by view: there is nothing to shard over %d ranks' % sharding.world_and_rank(None)[0])
+    dev = _cuda()
+    say = log if log is not None else (lambda *_: None)
+    label_i = int(label)
+    args_m1, args_m2 = m1, m2
+    m1_list = [0, m1]
+    table = _lib.f32c(spatial, dev).clone()
+    best = table.clone()
+    best_acc = 0 if targeted else 10000                                   # AN:294-303
+    m1_best = m2_best = 0
+    bufs = _ExportBuffers()
+    records, need_to_log = [], {}
+    epoch, n_pass = 0, 0
+    while epoch < epochs:
+        say('Attack ...... [' + str(epoch) + '/' + str(epochs) + ']')
+        since = time.time()
+        no_attack = attack_all = 0                                        # AN:329-330
+        m2 = args_m2                                                      # AN:332
+        not_changed = True
+        export = epoch == epochs - 1
+        src = (export_views if export_views is not None else views) if export else views
+        items = list(src(n_pass) if callable(src) else src)
+        if export and not items:                                          # (nothing would set tensor_not_changed: the loop could not end)
+            raise ValueError('nerfail: the export epoch needs at least one view (export_views is empty)')
+        stats = _PassStats(label_i, dev)
+        visits, skipped, attacked, completed, iters, raises = [], 0, 0, 0, 0, 0
+        pass_epoch, pass_m1 = epoch, m1
+        for i, item in enumerate(items):
+            wi, ori = item[0], item[1]
+            vid = item[2] if len(item) > 2 and item[2] is not None else None
+            vids = None if vid is None else [vid]
+            if export:
+                if i == 0:
+                    table = best                                          # AN:345: the table IS the best tensor from here on
+                    say('best m1=' + str(m1_best))
+                    say('best m2=' + str(m2_best))
+                    say('best acc=' + str(best_acc))
+                net.open_update_epsilon_3d()
+                _export_batch(net, table, (wi, ori, vids), i, stats, epoch, None, bufs, on_export)
+                not_changed = False                                       # AN:432
+                continue
+            net.open_update_epsilon_3d()
+            with torch.no_grad():
+                _, _, cla, _, ori_cla = net(table, wi, ori, view_ids=vids) if vids is not None else net(table, wi, ori)
+            stats.batch(epoch, cla, ori_cla)
+            net.close_update_epsilon_3d()
+            if not _same_class(cla, ori_cla):
+                skipped += 1
+                visits.append((i, True, 0, []))
+                continue
+            kw = dict(num_classes=num_classes, max_iter=df_max_iter, target_label=label_i if targeted else None, overshoot=overshoot,
+                      m1=m1, m2=m2)
+            if native is None or native:
+                dr, iter_k, _, _, _, classes = DF.deepfool_native((table, wi, ori), None, net, view_ids=vids, **kw)
+            else:
+                if wi is None or ori is None:                             # a resident view: the mirror takes tensors, not names
+                    wi, ori = net._last_views.wi_batch(), net._last_ori
+                dr, iter_k, _, _, _ = DF.deepfool((table, wi, ori), None, net, **kw)
+                classes = None
+            attacked += 1
+            iters += iter_k
+            visits.append((i, False, iter_k, classes))
+            if iter_k < df_max_iter or accumulate_incomplete:             # AN:405-409
+                say('iter_k < df_max_iter')
+                table += dr
+                not_changed = False
+                attack_all += 1
+                completed += iter_k < df_max_iter
+            elif m2 < m2_max_limit:                                       # AN:410-418
+                no_attack += 1
+                attack_all += 1
+                if attack_all > 10 and (no_attack / attack_all) > 0.5:
+                    m2 = m2 * 10
+                    raises += 1
+                    say('m2 is too small, times 10 to ' + str(m2))
+                    no_attack = attack_all = 0
+        if not_changed:                                                   # AN:434-472
+            if m1_list[0] < m1 - 1 and epoch == 0:
+                m1_list[1] = m1
+                m1 = int((m1 + m1_list[0]) / 2)
+                say('m1 from ' + str(m1_list[0]) + ' to ' + str(m1_list[1]) + ', m1=' + str(m1))
+                m2 = args_m2
+                epoch = 0
+            elif m1_list[0] < m1 and epoch == 0:
+                m1_list[1] = m1
+                m1 = m1_list[0]
+                say('m1 from ' + str(m1_list[0]) + ' to ' + str(m1_list[1]) + ', m1=' + str(m1))
+                m2 = args_m2
+                epoch = 0
+            else:
+                epoch = epochs - 1
+        elif epoch == epochs - 1:
+            if m1 < m1_list[1] - 1:
+                m1_list[0] = m1
+                m1 = int((m1 + m1_list[1]) / 2)
+                say('m1 from ' + str(m1_list[0]) + ' to ' + str(m1_list[1]) + ', m1=' + str(m1))
+                m2 = args_m2
+                epoch = 0
+            elif m1 < m1_list[1]:
+                m1_list[0] = m1
+                m1 = m1_list[1]
+                say('m1 from ' + str(m1_list[0]) + ' to ' + str(m1_list[1]) + ', m1=' + str(m1))
+                m2 = args_m2
+                epoch = 0
+            else:
+                epoch += 1
+        else:
+            epoch += 1
+        d = stats.read(net._mm())                                         # THE host read of the pass
+        n_views = len(items)                                              # len(now_dataloader.dataset), AN:476-480
+        nan = float('nan')
+        test_loss, test_acc = (d['test_sum'] / n_views, d['test_correct'] / n_views) if n_views else (nan, nan)
+        attack_loss, attack_acc = (d['attack_sum'] / n_views, d['attack_correct'] / n_views) if n_views else (nan, nan)
+        say('{} Loss: {:.4f} Acc: {:.4f}'.format('test', test_loss, test_acc))
+        say('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', attack_loss, attack_acc))
+        need_to_log['m1-' + str(m1) + ' epoch-' + str(epoch)] = 'time: {} Acc: {:.4f}'.format(time.time() - since, attack_acc)
+        say('epsilon_3d_min:  %s' % d['epsilon_3d_min'])                   # print_epsilon, AN:487
+        say('epsilon_3d_max:  %s' % d['epsilon_3d_max'])
+        net.epsilon_3d_zero()
+        if targeted:                                                      # AN:490-503
+            take = (attack_acc >= best_acc and m1 == m1_best) or (m1 > m1_best and attack_acc > 0)
+        else:
+            take = (attack_acc <= best_acc and m1 == m1_best) or (m1 > m1_best and attack_acc < 1)
+        if take:
+            best_acc, m1_best, m2_best = attack_acc, m1, m2
+            best = table.clone().detach()
+        records.append(dict(m1=m1, m2=m2, m1_pass=pass_m1, epoch=pass_epoch, next_epoch=epoch, test_loss=test_loss, test_acc=test_acc,
+                            attack_loss=attack_loss, attack_acc=attack_acc, views=n_views, skipped=skipped, attacked=attacked,
+                            completed=int(completed), deepfool_iters=iters, m2_raises=raises, taken=int(bool(take)),
+                            epsilon_3d_min=d['epsilon_3d_min'], epsilon_3d_max=d['epsilon_3d_max'], visits=visits,
+                            test_correct=d['test_correct'], attack_correct=d['attack_correct']))
+        _pass_done(n_pass, table)
+        n_pass += 1
+    return NerfailResult(best, table, m1_best, m2_best, best_acc, records, need_to_log)

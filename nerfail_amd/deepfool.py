@@ -10,6 +10,10 @@ class (the reference recomputes the identical tensor up to 7 times at deepfool.p
 nerfail_amd's gauss_net all class gradients of an iteration come from ONE multi-right-hand-side pass over the
 inverted index (gauss_net.logit_gradients -> nerfail_gauss_bwd_csr_multi) instead of one autograd.grad call each; the
 competing class is then chosen on the device (first minimum, NaN never chosen: deepfool.py:85's strict `<`).
+
+`deepfool_native` is the same loop in product shape for this package's gauss_net: the break test and the margins in one launch
+(nerfail_deepfool_gate), one 8-byte host read per iteration, norms + choice + update in one call (nerfail_deepfool_step), every
+buffer allocated once per call, and the class chosen in every iteration reported. `deepfool` stays exactly as it is.
 """
 import torch
 
@@ -108,3 +112,83 @@ def deepfool(net_input, e, net, num_classes=8, max_iter=20, target_label: int = 
     spatial_rgb = spatial_rgb.detach()
     rot = (spatial_rgb - spatial_rgb_0).detach()
     return rot, loop_i, ori_cla_max_index, cla_max_index, spatial_rgb
+
+
+def _native_applies(net, num_classes, universal_2d):
+    from .GaussNet import gauss_net
+    return (not universal_2d and isinstance(net, gauss_net) and getattr(net, 'deterministic', False)
+            and 2 <= int(num_classes) <= _lib.DEEPFOOL_MAX_COMPETITORS and torch.cuda.is_available())
+
+
+def deepfool_native(net_input, e, net, num_classes=8, max_iter=20, target_label: int = None, overshoot: float = 0.02,
+                    m1: float = 1, m2: float = 30, universal_2d=False, view_ids=None):
+    """deepfool(...) with the step arithmetic of an iteration in two library calls and nothing of torch between them:
+    nerfail_deepfool_gate (bump, first maximum, break test, |f'| of every competitor: deepfool.py:53-66, :79 / :93) and
+    nerfail_deepfool_step (norms, choice of the class, rot, clamp, alpha restore: deepfool.py:68-105).
+
+    Same arguments as deepfool plus `view_ids` (the view's name, handed to net: its cached inverted index and clean logits).
+    Returns SIX values: deepfool's (rot, loop_i, ori_cla_max_index, cla_max_index, spatial_rgb) and, sixth, the list of the
+    class chosen in each of the loop_i iterations (None when the call fell through). An iteration in which no class could be
+    chosen - every value_r NaN or infinite - still counts as one of the loop_i steps, as in the mirror: its entry is -1 and rot
+    is left as it was.
+
+    For `net` = this package's gauss_net on its deterministic path and 2..8 classes (2..8 gradient rows). Everything else -
+    another net, other class counts, a classifier whose row is not num_classes wide, universal_2d - falls through to
+    deepfool(...). The clean argmax `o` is read once per call (the clean image does not change during a call); per iteration:
+    net(...), gate, ONE host read of the record's first two words, net.logit_gradients, step. The first iteration uses the
+    forward of deepfool.py:33 instead of repeating it on the same table. Record, scratch, rot, the output table and the trace
+    array are allocated once per call."""
+    def mirror():
+        inp = net_input
+        if view_ids is not None and not universal_2d and (inp[1] is None or inp[2] is None):
+            with torch.no_grad():                                                           # a resident view: the mirror takes tensors
+                net(inp[0], inp[1], inp[2], view_ids=view_ids)
+            inp = (inp[0], net._last_views.wi_batch(), net._last_ori)
+        return deepfool(inp, e, net, num_classes, max_iter, target_label, overshoot, m1, m2, universal_2d) + (None,)
+    if not _native_applies(net, num_classes, universal_2d):
+        return mirror()
+    spatial_rgb, weight_and_index, ori_img = net_input
+    dev = torch.device('cuda', torch.cuda.current_device())
+    spatial_rgb_0 = _lib.f32c(torch.as_tensor(spatial_rgb), dev).clone()
+    if view_ids is None:
+        weight_and_index = _lib.f32c(torch.as_tensor(weight_and_index), dev)
+        ori_img = _lib.f32c(torch.as_tensor(ori_img), dev)
+    fwd = (lambda s: net(s, weight_and_index, ori_img, view_ids=view_ids)) if view_ids is not None else \
+          (lambda s: net(s, weight_and_index, ori_img))
+    s = spatial_rgb_0.clone().requires_grad_(True)
+    x_out, x_rgba, cla, _, ori_cla = fwd(s)                                             # deepfool.py:33
+    C = int(cla.shape[1])
+    target = -1 if target_label is None else int(target_label)
+    if cla.shape[0] != 1 or C != int(num_classes) or not -1 <= target < C:
+        return mirror()
+    ori_cla_max_index = torch.max(ori_cla, 1)[1]
+    o = int(ori_cla_max_index)                                                          # THE read of the call
+    arg = None
+    lib = _lib.load()
+    ks = [k for k in range(C) if k != o] if target < 0 else [target]
+    n_rhs, n = len(ks) + 1, spatial_rgb_0.numel() // 4
+    nb = lib.nerfail_deepfool_step_scratch_bytes(n_rhs, n)
+    scratch = torch.empty((nb // 8,), dtype=torch.float64, device=dev)
+    record = torch.zeros((_lib.DEEPFOOL_RECORD_WORDS,), dtype=torch.int32, device=dev)
+    trace = torch.full((max(int(max_iter), 1),), -1, dtype=torch.int32, device=dev)
+    rot = torch.zeros_like(spatial_rgb_0)
+    out = torch.empty_like(spatial_rgb_0)
+    loop_i = 0
+    while loop_i < max_iter:
+        if loop_i > 0:
+            s = out.detach().requires_grad_(True)
+            x_out, x_rgba, cla, _, ori_cla = fwd(s)                                     # deepfool.py:51
+        cla_c = _lib.f32c(cla)
+        _lib.check(lib.nerfail_deepfool_gate(_lib.dev(cla_c), C, o, target, float(m1), float(m2), _lib.dev(record), _lib.stream()))
+        done, arg = record[:2].tolist()                                                 # the iteration's one host read
+        if done:
+            break
+        G = net.logit_gradients(s, None, x_out, x_rgba, cla, [o] + ks)
+        _lib.check(lib.nerfail_deepfool_step(_lib.dev(G), n_rhs, n, _lib.dev(record), _lib.c_p(scratch.data_ptr()), nb, float(overshoot),
+                                             _lib.dev(spatial_rgb_0), _lib.dev(rot), _lib.dev(out), _lib.dev(trace[loop_i:loop_i + 1]),
+                                             _lib.stream()))
+        loop_i += 1
+    cla_max_index = torch.max(cla, 1)[1] if arg is None else torch.full((1,), arg, dtype=torch.int64, device=dev)
+    spatial_rgb = out if loop_i > 0 else spatial_rgb_0.clone()
+    classes = trace[:loop_i].tolist() if loop_i > 0 else []
+    return (spatial_rgb - spatial_rgb_0).detach(), loop_i, ori_cla_max_index, cla_max_index, spatial_rgb.detach(), classes
