@@ -762,6 +762,31 @@ int nerfail_deepfool_step(const float* grads, int n_rhs, int64_t n, const nerfai
                           size_t scratch_bytes, float overshoot, const float* spatial_init, float* rot, float* spatial_out,
                           int32_t* trace_slot, void* stream);
 
+/* ------------------------------------------------------------------ scene maps (scene revision 1) -- */
+
+/* The 8-NN search with create_gauss_w as its epilogue: a view's point image straight to the [2,P,8] (weight, index) map the
+ * attacks differentiate through (CI:126-163 + DW:82-97 in one launch, no [2,P,8] distance tensor in between). Like the four
+ * sections before it this one only ADDS entry points: NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays 15, the eval,
+ * cls and deepfool revisions stay 1, and the additions are announced by nerfail_scene_revision() = 1. nerfail_knn8_grid_search[_view]
+ * and nerfail_gauss_weight are unchanged. No allocation, no synchronisation, no float atomics; the same bits on every run.
+ *
+ * weight_and_index[2, n_queries, 8] (16-byte aligned): plane 0 the weights, plane 1 the indices as float32 - bit for bit what
+ * nerfail_knn8_grid_search[_view] followed by nerfail_gauss_weight(c) writes: d_k = sqrt(d2_k), g_k = exp(-(d_k/c)^2 / 2),
+ * w_k = g_k / (sum g + 0.001) if sum g > 0 else 0, the sum in k = 0..7 order.
+ * sum_d2 (a device double, may be NULL): the sum over all 8 * n_queries distances of the float32 product d * d (torch.square of
+ * DW:92), added up in double in a fixed order - one partial per workgroup in `workspace`, then a one-wave fold.
+ * grid_workspace: a grid built by nerfail_knn8_grid_build for n_points points (a count that contradicts the build this process
+ * made in that workspace is NERFAIL_EINVAL). workspace: nerfail_knn8_grid_weights_workspace_bytes(n_queries) bytes, 8-byte
+ * aligned (0 for n_queries <= 0); contents unspecified on return. c > 0. */
+int nerfail_scene_revision(void);
+size_t nerfail_knn8_grid_weights_workspace_bytes(int64_t n_queries);
+int nerfail_knn8_grid_weights_view(const float* queries, int height, int width, int64_t n_points, float c, float* weight_and_index,
+                                   double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int nerfail_knn8_grid_weights(const float* queries, int64_t n_queries, int64_t n_points, float c, float* weight_and_index,
+                              double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

@@ -16,6 +16,7 @@ ABI_REVISION = 15                        # additions since ABI_VERSION (nerfail_
 EVAL_REVISION = 1                        # nerfail_eval_revision: the attack-evaluation entry points (model_test)
 CLS_REVISION = 1                         # nerfail_cls_revision: the victim-training entry points (model_train)
 DEEPFOOL_REVISION = 1                    # nerfail_deepfool_revision: the DeepFool gate and step (deepfool.deepfool_native)
+SCENE_REVISION = 1                       # nerfail_scene_revision: the 8-NN search with the Gaussian weights as its epilogue (scene)
 DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
 DEEPFOOL_RECORD_WORDS = 4 + 2 * DEEPFOOL_MAX_COMPETITORS    # struct nerfail_deepfool_record as 32-bit words
 EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
@@ -181,6 +182,10 @@ SIGNATURES = {
     'nerfail_deepfool_gate': (c_i, [c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
     'nerfail_deepfool_step_scratch_bytes': (ctypes.c_size_t, [c_i, c_i64]),
     'nerfail_deepfool_step': (c_i, [c_p, c_i, c_i64, c_p, c_p, ctypes.c_size_t, c_f, c_p, c_p, c_p, c_p, c_p]),
+    'nerfail_scene_revision': (c_i, []),
+    'nerfail_knn8_grid_weights_workspace_bytes': (ctypes.c_size_t, [c_i64]),
+    'nerfail_knn8_grid_weights_view': (c_i, [c_p, c_i, c_i, c_i64, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p, ctypes.c_size_t, c_p]),
+    'nerfail_knn8_grid_weights': (c_i, [c_p, c_i64, c_i64, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p, ctypes.c_size_t, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -242,6 +247,9 @@ def load():
     if lib.nerfail_deepfool_revision() != DEEPFOOL_REVISION:
         raise RuntimeError('nerfail_amd: DeepFool revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_deepfool_revision(), DEEPFOOL_REVISION))
+    if lib.nerfail_scene_revision() != SCENE_REVISION:
+        raise RuntimeError('nerfail_amd: scene-maps revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_scene_revision(), SCENE_REVISION))
     _lib = lib
     return lib
 

@@ -8,6 +8,7 @@
 // indices per pixel read as two float4 pairs); K10 adds 8 random 16-B row gathers from the 30.7 MB
 // perturbation table (Infinity-Cache resident), K11 8 x 4 float atomics per pixel into it.
 #include "common.h"
+#include "gauss_weight.h"
 
 namespace nerfail {
 
@@ -23,18 +24,8 @@ __global__ __launch_bounds__(256) void gauss_weight_kernel(const float* __restri
     float4* i4 = reinterpret_cast<float4*>(out + ((b * 2 + 1) * P + p) * 8);
     const float4 da = dist4[0], db = dist4[1];
     const float d[8] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w};
-    float gk[8];
-    float ds = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float q = __fdiv_rn(d[k], c);
-        gk[k] = expf(-__fdiv_rn(__fmul_rn(q, q), 2.0f));     // exp(-(d/c)^2 / 2)
-        ds = __fadd_rn(ds, gk[k]);
-    }
-    const float dq = __fadd_rn(ds, 0.001f);
     float w[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = (ds > 0.f) ? __fdiv_rn(gk[k], dq) : 0.f;
+    gauss_weights8(d, c, w);
     w4[0] = make_float4(w[0], w[1], w[2], w[3]);
     w4[1] = make_float4(w[4], w[5], w[6], w[7]);
     i4[0] = idx4[0];

@@ -18,8 +18,11 @@
 // of 4^3 coarse cells (4^3 cells each) by the distance of their boxes and descends best first; ~1000 distances per query
 // where the brute-force scan computes 1.92 M.
 #include "common.h"
+#include "gauss_weight.h"
 
 #include <hipcub/hipcub.hpp>
+
+#include <mutex>
 
 namespace nerfail {
 
@@ -217,10 +220,15 @@ constexpr int kCoherentCells = 6;     // lanes whose queries span at most this m
 constexpr int kGroupPasses = 4;       // groups per wave before the rest goes lane by lane
 constexpr int kMinGroup = 8;
 
+// WEIGHTS: the instantiation behind nerfail_knn8_grid_weights[_view]. The search is the same code; what differs is what leaves
+// the kernel once a query's eight keys are final: `dist` receives K9's weights (gauss_weights8 of the distances, gauss_weight.h)
+// instead of the distances, `idx_f` the indices as float as before - the two planes of the attack's [2,P,8] map - and, when
+// `d2_part` is set, slot blockIdx.x of it the wave's sum of d * d over its valid queries (double; see the epilogue).
+template <bool WEIGHTS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void knn8_grid_kernel(const float* __restrict__ queries, long nq, int view_h, int view_w, const Grid* __restrict__ gp,
                                                         const float4* __restrict__ sorted, const int* __restrict__ cell_start,
                                                         const int* __restrict__ coarse_cnt, const int* __restrict__ super_cnt, float* __restrict__ dist, float* __restrict__ idx_f,
-                                                        int* __restrict__ idx_i, unsigned long long* __restrict__ stats) {
+                                                        int* __restrict__ idx_i, unsigned long long* __restrict__ stats, float gauss_c, double* __restrict__ d2_part) {
     // One wave per workgroup. view_w > 0: the queries are the [view_h, view_w] pixels of a view and a wave takes an 8 x 8 pixel
     // TILE (0.014 scene units across on a lego view, a third of a cell: the 64 searches share nearly all their candidates);
     // view_w == 0: 64 consecutive queries. Lanes past the end repeat a valid query of the wave (no early return: the search
@@ -587,6 +595,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
         for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
         if ((threadIdx.x & 63) == 0) { atomicAdd(stats, tot); atomicAdd(stats + 1, searched); }
     }
+    if constexpr (WEIGHTS) {
+        // The view's sum of d * d (the "v" of DW:92-93 before its division): every term is the float32 product torch.square
+        // forms, the sum runs in double in a fixed order - k = 0..7 in the lane, the xor butterfly over the wave (lanes past the
+        // end add 0), one slot per workgroup, knn8_d2_fold_kernel over the slots - so two runs give the same bits. No atomics.
+        if (d2_part != nullptr) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float dk = sqrt_rn(key_d2(fk[k]));
+                acc += (double)__fmul_rn(dk, dk);
+            }
+            acc = wave_sum_f64(valid ? acc : 0.0);
+            if ((threadIdx.x & 63) == 0) d2_part[blockIdx.x] = acc;
+        }
+    }
     if (!valid) return;
     // 32 bytes per query and output as two 16-byte stores (eight 4-byte stores 32 bytes apart wrote every 64-byte line of the
     // outputs in pieces: 5x the bytes at the memory side)
@@ -597,6 +620,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
         d[k] = sqrt_rn(key_d2(fk[k]));
         ji[k] = (int)(unsigned)fk[k];
         jf[k] = (float)ji[k];
+    }
+    if constexpr (WEIGHTS) {
+        float w[8];
+        gauss_weights8(d, gauss_c, w);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d[k] = w[k];
     }
     float4* __restrict__ od = reinterpret_cast<float4*>(dist + 8 * qi);
     od[0] = make_float4(d[0], d[1], d[2], d[3]);
@@ -611,6 +640,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
         oi[0] = make_int4(ji[0], ji[1], ji[2], ji[3]);
         oi[1] = make_int4(ji[4], ji[5], ji[6], ji[7]);
     }
+}
+
+// The per-workgroup partials of the WEIGHTS instantiation -> *out: one wave. Lane l owns slots l, l + 64, ...; it keeps kFoldLanes
+// running sums (slot j of its sequence goes to sum j % kFoldLanes) so that kFoldLanes loads are in flight instead of one
+// (10 000 slots per 800 x 800 view: 157 dependent round trips per lane otherwise), adds them up in index order, then the xor
+// butterfly. A fixed order whatever the device does: the same bits on every run.
+constexpr int kFoldLanes = 8;
+__global__ __launch_bounds__(64) void knn8_d2_fold_kernel(const double* __restrict__ part, long n, double* __restrict__ out) {
+    double acc[kFoldLanes];
+#pragma unroll
+    for (int u = 0; u < kFoldLanes; ++u) acc[u] = 0.0;
+    for (long i = threadIdx.x; i < n; i += 64 * kFoldLanes) {
+        double v[kFoldLanes];
+#pragma unroll
+        for (int u = 0; u < kFoldLanes; ++u) v[u] = i + 64 * u < n ? part[i + 64 * u] : 0.0;
+#pragma unroll
+        for (int u = 0; u < kFoldLanes; ++u) acc[u] += v[u];
+    }
+    double tot = acc[0];
+#pragma unroll
+    for (int u = 1; u < kFoldLanes; ++u) tot += acc[u];
+    tot = wave_sum_f64(tot);
+    if (threadIdx.x == 0) *out = tot;
 }
 
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -676,6 +728,28 @@ static GridWs carve(void* workspace, long n) {
     return w;
 }
 
+// Which point count the grid in a workspace was built for (host side, the last kBuiltSlots builds of this process): the layout of
+// a workspace follows from n_points alone, so a search that names another count would read offsets as cell ranges. The
+// weights entry points refuse a count that contradicts the record; a workspace this process never built (a copy) passes.
+constexpr int kBuiltSlots = 32;
+static struct { const void* ws; int64_t n; } g_built[kBuiltSlots];
+static int g_built_next = 0;
+static std::mutex g_built_mutex;
+static void note_built(const void* ws, int64_t n) {
+    std::lock_guard<std::mutex> lock(g_built_mutex);
+    for (int i = 0; i < kBuiltSlots; ++i)
+        if (g_built[i].ws == ws) { g_built[i].n = n; return; }
+    g_built[g_built_next].ws = ws;
+    g_built[g_built_next].n = n;
+    g_built_next = (g_built_next + 1) % kBuiltSlots;
+}
+static int64_t built_for(const void* ws) {          // -1: unknown
+    std::lock_guard<std::mutex> lock(g_built_mutex);
+    for (int i = 0; i < kBuiltSlots; ++i)
+        if (g_built[i].ws == ws) return g_built[i].n;
+    return -1;
+}
+
 extern "C" int nerfail_knn8_grid_build(const float* points, int64_t n_points, void* workspace, size_t workspace_bytes, void* stream) {
     NF_REQUIRE(n_points >= NERFAIL_KNN, "need at least 8 points");
     NF_REQUIRE(n_points < (1 << 24), "n_points must be < 2^24 (indices are stored as float32, CI:148-163)");
@@ -710,6 +784,7 @@ extern "C" int nerfail_knn8_grid_build(const float* points, int64_t n_points, vo
     const int Gs = (Gc + kSuper - 1) / kSuper;
     super_count_kernel<<<dim3((unsigned)((super_cells(G) + 255) / 256)), dim3(256), 0, s>>>(w.coarse_cnt, Gc, Gs, w.super_cnt);
     NF_LAUNCHED("super_count_kernel");
+    note_built(workspace, n_points);
     return NERFAIL_OK;
 }
 
@@ -731,9 +806,9 @@ static int grid_search(const float* queries, int64_t n_queries, int view_h, int 
     const GridWs w = carve(const_cast<void*>(workspace), n_points);
     const long waves = view_w > 0 ? (long)((view_w + 7) / 8) * ((view_h + 7) / 8) : (n_queries + 63) / 64;
     NF_REQUIRE(waves < (1L << 31), "too many queries for one launch");
-    knn8_grid_kernel<<<dim3((unsigned)waves), dim3(64), 0, as_stream(stream)>>>(
+    knn8_grid_kernel<false><<<dim3((unsigned)waves), dim3(64), 0, as_stream(stream)>>>(
         queries, n_queries, view_h, view_w, w.gp, w.sorted, w.cell_start, w.coarse_cnt, w.super_cnt, dist, idx_f32, idx_i32,
-        g_knn_stats);
+        g_knn_stats, 0.f, nullptr);
     NF_LAUNCHED("knn8_grid_kernel");
     return NERFAIL_OK;
 }
@@ -761,4 +836,65 @@ extern "C" int nerfail_knn8_grid(const float* queries, int64_t n_queries, const 
     const int rc = nerfail_knn8_grid_build(points, n_points, workspace, workspace_bytes, stream);
     if (rc != NERFAIL_OK) return rc;
     return nerfail_knn8_grid_search(queries, n_queries, n_points, dist, idx_f32, idx_i32, workspace, workspace_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------ scene revision 1
+// The search with K9 as its epilogue: the attack's [2,P,8] map straight from the view's point image (see the header).
+extern "C" int nerfail_scene_revision(void) { return 1; }
+
+static long weights_waves(int64_t n_queries, int view_h, int view_w) {
+    return view_w > 0 ? (long)((view_w + 7) / 8) * ((view_h + 7) / 8) : (long)((n_queries + 63) / 64);
+}
+
+extern "C" size_t nerfail_knn8_grid_weights_workspace_bytes(int64_t n_queries) {
+    if (n_queries <= 0) return 0;
+    // one double per workgroup: an 8 x 8 tile per wave covers a view of n pixels with at most ceil(n / 8) tiles (a view one
+    // pixel high), 64 consecutive queries per wave need fewer
+    return al256((size_t)((n_queries + 7) / 8) * sizeof(double));
+}
+
+static int grid_weights(const float* queries, int64_t n_queries, int view_h, int view_w, int64_t n_points, float c, float* weight_and_index,
+                        double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    NF_REQUIRE(n_queries > 0, "n_queries must be positive");
+    NF_REQUIRE(n_points >= NERFAIL_KNN && n_points < (1 << 24), "bad n_points");
+    NF_REQUIRE(c > 0.f, "c must be positive");
+    NF_REQUIRE(queries != nullptr && weight_and_index != nullptr, "NULL pointer");
+    NF_REQUIRE((reinterpret_cast<uintptr_t>(weight_and_index) & 15) == 0, "weight_and_index must be 16-byte aligned");
+    NF_REQUIRE((reinterpret_cast<uintptr_t>(sum_d2) & 7) == 0, "sum_d2 must be 8-byte aligned");
+    NF_REQUIRE(grid_workspace != nullptr && grid_workspace_bytes >= nerfail_knn8_grid_workspace_bytes(n_points),
+               "grid workspace too small (nerfail_knn8_grid_workspace_bytes)");
+    const int64_t built = built_for(grid_workspace);
+    NF_REQUIRE(built < 0 || built == n_points, "n_points does not match the grid built in this workspace (nerfail_knn8_grid_build)");
+    const long waves = weights_waves(n_queries, view_h, view_w);
+    NF_REQUIRE(waves < (1L << 31), "too many queries for one launch");
+    NF_REQUIRE(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 &&
+                   workspace_bytes >= nerfail_knn8_grid_weights_workspace_bytes(n_queries) && workspace_bytes >= (size_t)waves * sizeof(double),
+               "workspace too small (nerfail_knn8_grid_weights_workspace_bytes)");
+    const GridWs w = carve(const_cast<void*>(grid_workspace), n_points);
+    double* part = sum_d2 != nullptr ? (double*)workspace : nullptr;
+    knn8_grid_kernel<true><<<dim3((unsigned)waves), dim3(64), 0, as_stream(stream)>>>(
+        queries, n_queries, view_h, view_w, w.gp, w.sorted, w.cell_start, w.coarse_cnt, w.super_cnt, weight_and_index,
+        weight_and_index + 8 * n_queries, nullptr, g_knn_stats, c, part);
+    NF_LAUNCHED("knn8_grid_kernel<weights>");
+    if (sum_d2 != nullptr) {
+        knn8_d2_fold_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(part, waves, sum_d2);
+        NF_LAUNCHED("knn8_d2_fold_kernel");
+    }
+    return NERFAIL_OK;
+}
+
+extern "C" int nerfail_knn8_grid_weights(const float* queries, int64_t n_queries, int64_t n_points, float c, float* weight_and_index,
+                                         double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    return grid_weights(queries, n_queries, 0, 0, n_points, c, weight_and_index, sum_d2, grid_workspace, grid_workspace_bytes, workspace,
+                        workspace_bytes, stream);
+}
+
+extern "C" int nerfail_knn8_grid_weights_view(const float* queries, int height, int width, int64_t n_points, float c,
+                                              float* weight_and_index, double* sum_d2, const void* grid_workspace,
+                                              size_t grid_workspace_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    NF_REQUIRE(height > 0 && width > 0, "bad view size");
+    return grid_weights(queries, (int64_t)height * width, height, width, n_points, c, weight_and_index, sum_d2, grid_workspace,
+                        grid_workspace_bytes, workspace, workspace_bytes, stream);
 }

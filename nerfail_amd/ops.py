@@ -235,6 +235,60 @@ def _(dist_and_index, c):
     return torch.empty_like(dist_and_index)
 
 
+# ----------------------------------------------------------------------------------------------- K8 + K9 in one launch (scene revision 1)
+def knn8_weights_into(queries, n_points, c, grid_ws, grid_bytes, out, sum_d2):
+    """nerfail_knn8_grid_weights[_view] over a BUILT grid (scene.PointSet keeps one per scene): `out` [2,...,8] and the device
+    double `sum_d2` are overwritten. queries [H,W,3] with both sides >= 8 take the 8 x 8 pixel-tile form, anything else the flat one."""
+    lib = _lib.load()
+    Q = queries.numel() // 3
+    nb = lib.nerfail_knn8_grid_weights_workspace_bytes(Q)
+    ws = torch.empty((max(nb, 8) // 8,), dtype=torch.float64, device=queries.device)
+    d2 = _lib.c_p(sum_d2.data_ptr()) if sum_d2 is not None else None
+    if queries.dim() == 3 and queries.shape[0] >= 8 and queries.shape[1] >= 8:
+        _chk(lib.nerfail_knn8_grid_weights_view(_lib.dev(queries, 'queries'), queries.shape[0], queries.shape[1], n_points, c, _lib.dev(out), d2,
+                                                _lib.dev(grid_ws), grid_bytes, _lib.c_p(ws.data_ptr()), nb, _s()))
+    else:
+        _chk(lib.nerfail_knn8_grid_weights(_lib.dev(queries, 'queries'), Q, n_points, c, _lib.dev(out), d2, _lib.dev(grid_ws), grid_bytes,
+                                           _lib.c_p(ws.data_ptr()), nb, _s()))
+
+
+@custom_op(NS + '::knn8_weights', mutates_args=(), device_types='cuda')
+def knn8_weights(queries: Tensor, points: Tensor, c: float) -> tuple[Tensor, Tensor]:
+    """(weight_and_index [2,...,8], sum_d2 float64 [1]) of queries [...,3] in points [M,3]: the attack's map of a view - bit for
+    bit knn8 followed by gauss_weight(c) - and the sum of the squared distances (float32 squares, added in double). From 4096
+    points up ONE search kernel with the weights as its epilogue (the grid is built per call here; scene.view_map keeps it),
+    below that the brute-force scan followed by gauss_weight."""
+    lib = _lib.load()
+    M = points.shape[0]
+    lead = tuple(queries.shape[:-1])
+    Q = queries.numel() // 3
+    out = torch.empty((2,) + lead + (8,), dtype=torch.float32, device=queries.device)
+    sum_d2 = torch.zeros((1,), dtype=torch.float64, device=queries.device)
+    if not c > 0:
+        raise _lib.NerfailError('knn8_weights: c must be positive')
+    if Q == 0:
+        return out, sum_d2
+    if M >= 4096:
+        nb = lib.nerfail_knn8_grid_workspace_bytes(M)
+        ws = torch.empty((nb,), dtype=torch.uint8, device=queries.device)
+        _chk(lib.nerfail_knn8_grid_build(_lib.dev(points, 'points'), M, _lib.dev(ws), nb, _s()))
+        knn8_weights_into(queries, M, c, ws, nb, out, sum_d2)
+    else:
+        dai = torch.empty((1, 2, Q, 1, 8), dtype=torch.float32, device=queries.device)
+        _chk(lib.nerfail_knn8(_lib.dev(queries, 'queries'), Q, _lib.dev(points, 'points'), M, _lib.dev(dai[0, 0]), _lib.dev(dai[0, 1]), None, _s()))
+        _chk(lib.nerfail_gauss_weight(_lib.dev(dai), 1, Q, c, _lib.dev(out), _s()))
+        sum_d2 = torch.square(dai[0, 0]).sum(dtype=torch.float64).reshape(1)
+    return out, sum_d2
+
+
+@knn8_weights.register_fake
+def _(queries, points, c):
+    return queries.new_empty((2,) + tuple(queries.shape[:-1]) + (8,)), queries.new_empty((1,), dtype=torch.float64)
+
+
+SCENE_OPS = ('knn8_weights',)
+
+
 # ----------------------------------------------------------------------------------------------- K10 / K11 gather (GN:53-119)
 @custom_op(NS + '::gauss_gather', mutates_args=(), device_types='cuda')
 def gauss_gather(spatial: Tensor, weight_and_index: Tensor, ori_img: Tensor, epsilon: float) -> tuple[Tensor, Tensor]:

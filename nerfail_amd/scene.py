@@ -1,0 +1,199 @@
+"""Scene maps in one call: a trained NeRF to attack-ready views, on the device.
+
+The reference turns a NeRF into the pixel <-> 3-D-point maps of its attacks with three scripts glued together by the disk:
+nerf_to_coord.py (NC: one `NNN.npy` point image per view), create_index_and_dist.py (CI: `index_and_dist/<split>/<i>.pth`)
+and tools/dist_to_weight.py (DW: `index_and_weight/<split>/<i>.pth`), which the attack's dataset then loads back. The mirrors of
+those scripts (nerf_to_coord.render_path, create_index_and_dist, dist_to_weight, GaussNet.load_view_maps) keep that file
+contract. `build_scene_maps` is the same stage as a product: render (ends on the device) -> `view_map` (the 8-NN search with
+the Gaussian weights as its epilogue, one launch) -> `GaussNet.register_view` (the map, the image and the inverted index stay
+resident under a view id) - the ids it returns are what attack.nerfail_s / attack.nerfail / nerfail_s_step take as `view_ids=`.
+Nothing is written unless `save_dir` asks for it, and every map is bit for bit the file pipeline's.
+"""
+import itertools
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import ops
+from . import GaussNet as _G
+from . import nerf_to_coord as _NC
+from .create_index_and_dist import _grid_for, knn8
+from .run_nerf_helpers import _cuda
+
+GRID_FROM = 4096          # the 'auto' rule of create_index_and_dist.knn8: grid search from this many points up
+SPLITS = ('test', 'train', 'val')     # CI:110
+
+_scene_counter = itertools.count()
+
+
+class PointSet:
+    """The spatial point set of a scene (CI:57-61): `points` [M,3] on the device, `Ns` = M rows of the perturbation table.
+    From GRID_FROM points up it owns the search grid (create_index_and_dist._grid_for), built once."""
+
+    def __init__(self, points):
+        dev = _cuda()
+        self.points = _lib.f32c(torch.as_tensor(points), dev).reshape(-1, 3)
+        self.Ns = int(self.points.shape[0])
+        if self.Ns < 8:
+            raise _lib.NerfailError('PointSet: need at least 8 points (got %d)' % self.Ns)
+        self._grid = None
+        if self.Ns >= GRID_FROM:
+            self.grid()
+
+    def grid(self):
+        """(workspace, bytes) of the built grid; held here, so the cache of _grid_for may forget it."""
+        if self._grid is None:
+            self._grid = _grid_for(self.points)
+        return self._grid
+
+    @classmethod
+    def from_views(cls, pts_list):
+        """The [H,W,3] point images of the base views, stacked in list order (CI:57-61)."""
+        dev = _cuda()
+        return cls(torch.reshape(torch.stack([_lib.f32c(torch.as_tensor(p), dev) for p in pts_list]), (-1, 3)))
+
+    @classmethod
+    def from_render(cls, render_kwargs, poses, hwf, K, chunk=1024 * 32):
+        """Renders the base views `poses` [n,4,4] (nerf_to_coord.render) and stacks their pts_max."""
+        return cls.from_views([_render_pts(render_kwargs, c2w, hwf, K, chunk) for c2w in poses])
+
+
+def _render_pts(render_kwargs, c2w, hwf, K, chunk):
+    """pts_max [H,W,3] of one view, on the device (NC:160: the render of render_path, without its host copies)."""
+    H, W = int(hwf[0]), int(hwf[1])
+    c2w = torch.as_tensor(c2w)
+    with torch.no_grad():                                  # as the reference renders (NC:640)
+        pts_max = _NC.render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)[3]
+    return pts_max.reshape(H, W, 3)
+
+
+def view_map(pts_max, point_set, c=0.02, method='auto'):
+    """One view: pts_max [H,W,3] against the point set -> (weight_and_index [2,H,W,8], sum_d2), both on the device.
+
+    The map is bit for bit create_index_and_dist.index_and_dist followed by create_gauss_w(c) (CI:126-163, DW:82-97); sum_d2 (a
+    0-dim float64 tensor) is the sum over the view's 8 H W distances of the float32 square DW:92 takes, added in double.
+    method 'auto': from GRID_FROM points up the fused kernel (nerfail_knn8_grid_weights_view: no distance tensor is written),
+    below that the brute-force scan followed by K9; 'grid' / 'brute' force either."""
+    dev = _cuda()
+    if not float(c) > 0:
+        raise _lib.NerfailError('view_map: c must be positive')
+    q = _lib.f32c(torch.as_tensor(pts_max), dev)
+    if q.dim() != 3 or q.shape[2] != 3:
+        raise ValueError('pts_max must be [H,W,3] (NC:418-423), got %s' % (tuple(q.shape),))
+    if method == 'auto':
+        method = 'grid' if point_set.Ns >= GRID_FROM else 'brute'
+    if method == 'grid':
+        ws, nbytes = point_set.grid()
+        wi = torch.empty((2, q.shape[0], q.shape[1], 8), dtype=torch.float32, device=dev)
+        sum_d2 = torch.empty((), dtype=torch.float64, device=dev)
+        ops.knn8_weights_into(q, point_set.Ns, float(c), ws, nbytes, wi, sum_d2)
+        return wi, sum_d2
+    if method != 'brute':
+        raise ValueError('method must be auto, grid or brute')
+    d, i = knn8(q, point_set.points, method='brute')
+    wi = torch.ops.nerfail_mi.gauss_weight(torch.stack([d, i], 0).unsqueeze(0), float(c))[0]
+    return wi, torch.square(d).sum(dtype=torch.float64)
+
+
+class SceneMaps:
+    """What build_scene_maps returns. `point_set` / `Ns`: the scene's point set and the rows of its perturbation table;
+    `view_ids`: {split: [id, ...]} in pose order - hand them to the attack loops as `view_ids=`; `v`: the "v" of DW:92-100, the
+    mean over the views of each view's mean squared distance; `c`; `hw`: the views' (H, W)."""
+
+    def __init__(self, point_set, view_ids, v, c, hw, scene_key):
+        self.point_set, self.Ns, self.view_ids, self.v, self.c, self.hw, self.scene_key = point_set, point_set.Ns, view_ids, v, c, hw, scene_key
+
+    def batches(self, splits, batch_size):
+        """[(None, None, ids), ...]: the views of `splits` (a name or several) in order, `batch_size` per batch, as
+        attack.nerfail_s takes them when the maps and images are resident."""
+        ids = [v for s in ((splits,) if isinstance(splits, str) else splits) for v in self.view_ids[s]]
+        return [(None, None, ids[b:b + batch_size]) for b in range(0, len(ids), batch_size)]
+
+
+def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024 * 32, images=None, view_ids=None,
+                     point_set=None, keep_maps=True, save_dir=None, on_view=None):
+    """NC + CI + DW for a whole scene without the disk: every view of `poses` rendered, searched, weighted and registered.
+
+    `poses`: {split: [N,4,4]} or one array (then the split is 'test'). `mask_list`: the views of the 'test' split whose points
+    form the point set, in that order (CI:56-61) - unless `point_set` (a PointSet) is given. Per view: nerf_to_coord.render ->
+    view_map -> GaussNet.register_view(id, Ns, map, images[split][i]); the default id is (scene_key, split, i), `view_ids`
+    ({split: ids}) names them otherwise. `images`: {split: uint8 BGRA [N,H,W,4] or a list} (MyDataset.py:200), kept resident
+    next to the maps. Nothing crosses PCIe but the two counts per view the inverted-index build reads.
+    keep_maps=False: only the inverted index and the image of a view stay resident (the attack's forward needs the map, so
+    True is the default). `save_dir`: ALSO write `index_and_weight/<split>/<i>.pth` (CPU float32 [2,H,W,8]) and its
+    `<i>.idx.pth` sidecar under it - what the file pipeline leaves behind, which GaussNet.load_view_maps accepts as it is; no
+    `.npy`, no `index_and_dist`. `on_view(split, i, view_id, weight_and_index)` sees every map. Returns SceneMaps."""
+    dev = _cuda()
+    if not isinstance(poses, dict):
+        poses, images, view_ids = {'test': poses}, (None if images is None else {'test': images}), (None if view_ids is None else {'test': view_ids})
+    order = [s for s in SPLITS if s in poses] + [s for s in poses if s not in SPLITS]
+    H, W = int(hwf[0]), int(hwf[1])
+    scene_key = 'scene%d' % next(_scene_counter)
+    pts_cache = {}
+    if point_set is None:
+        if 'test' not in poses:
+            raise ValueError("the point set is made of views of the 'test' split (CI:56-61): pass poses['test'] or point_set=")
+        mask_list = [int(i) for i in mask_list]
+        if not mask_list or min(mask_list) < 0 or max(mask_list) >= len(poses['test']):
+            raise ValueError('mask_list must name views of the test split (0..%d)' % (len(poses['test']) - 1))
+        for i in sorted(set(mask_list)):                      # rendered once: as base views now, as views of their split below
+            pts_cache[i] = _render_pts(render_kwargs, poses['test'][i], hwf, K, chunk)
+        point_set = PointSet.from_views([pts_cache[i] for i in mask_list])
+    Ns = point_set.Ns
+    v_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    n_views = 0
+    out_ids = {}
+    for split in order:
+        ids = []
+        if save_dir is not None:
+            os.makedirs(os.path.join(save_dir, 'index_and_weight', split), exist_ok=True)
+        for i, c2w in enumerate(poses[split]):
+            pts = pts_cache.pop(i, None) if split == 'test' else None
+            if pts is None:
+                pts = _render_pts(render_kwargs, c2w, hwf, K, chunk)
+            wi, sum_d2 = view_map(pts, point_set, c)
+            v_sum += sum_d2 / float(8 * H * W)                # this view's mean squared distance (DW:92), on the device
+            n_views += 1
+            vid = view_ids[split][i] if view_ids is not None and split in view_ids else (scene_key, split, i)
+            img = images[split][i] if images is not None and images.get(split) is not None else None
+            if keep_maps:
+                _G.register_view(vid, Ns, wi, img)
+            else:
+                _G.view_indices([wi], Ns, [vid])
+                if img is not None:
+                    _G.register_view(vid, Ns, ori_img=img)
+            if save_dir is not None:
+                mpath = os.path.join(save_dir, 'index_and_weight', split, '%d.pth' % i)
+                torch.save(wi.cpu(), mpath)                    # DW:95-97
+                vi = _G.view_indices([wi], Ns, [vid])[0]
+                vi.src = _G._file_sig(mpath)
+                vi.save(os.path.join(save_dir, 'index_and_weight', split, '%d.idx.pth' % i))
+            if on_view is not None:
+                on_view(split, i, vid, wi)
+            ids.append(vid)
+        out_ids[split] = ids
+    v = float(v_sum) / max(n_views, 1)                        # THE host read of the call
+    return SceneMaps(point_set, out_ids, v, float(c), (H, W), scene_key)
+
+
+def perturbation_table(base_images, zero_init=True, rand_init=False, generator=None):
+    """The perturbation table the attacks start from (AS:218, 252-263): uint8 (or float) BGRA base images [n,H,W,4], or a list
+    of [H,W,4], -> float32 [n,H,W,4] on the device. rand_init: every channel drawn uniformly from [0, 255) where alpha > 0
+    (AS:254-257; `generator`: a device torch.Generator, default the global one); zero_init: the colours zeroed, the alpha
+    channel kept (AS:259-263) - applied after rand_init when both are set, as the reference applies them."""
+    dev = _cuda()
+    if isinstance(base_images, (list, tuple)):
+        base_images = torch.stack([torch.as_tensor(np.asarray(b) if not isinstance(b, torch.Tensor) else b) for b in base_images])   # AS:218
+    t = torch.as_tensor(base_images).to(dev).float().contiguous()                           # AS:252
+    if t.dim() != 4 or t.shape[3] != 4:
+        raise ValueError('base images must be [n,H,W,4] (BGRA), got %s' % (tuple(t.shape),))
+    if rand_init:
+        r = (torch.rand_like(t) if generator is None else torch.rand(t.shape, dtype=t.dtype, device=dev, generator=generator)) * 255
+        t = torch.where(t[:, :, :, 3].unsqueeze(-1) > 0, r, t)
+    if zero_init:
+        z = torch.zeros_like(t)
+        z[:, :, :, 3] = t[:, :, :, 3]
+        t = z
+    return t

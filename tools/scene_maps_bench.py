@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""The scene-map stage: the fused 8-NN + weight kernel against the chain it replaces, and scene.build_scene_maps against the
+file pipeline (nerf_to_coord.render_path -> create_index_and_dist -> dist_to_weight -> GaussNet.load_view_maps).
+
+    python tools/scene_maps_bench.py [--out FILE] [--skip-pipeline]
+
+(a) `kernel`: one 800x800 view of rendered-view geometry (synth.sphere_view_points) against the 1.92 M points of three such
+    views, grid built once. Arm `chain`: create_index_and_dist.index_and_dist (the search, then the torch.stack copy) followed
+    by create_gauss_w - what the file pipeline runs per view between its files. Arm `fused`: scene.view_map (one search launch
+    with the weights as its epilogue, plus the one-wave fold of sum_d2). Event-timed, the two arms ALTERNATED run by run in one
+    session, median of 20 after 5 warm-up; `spread` is each arm's interquartile range, min and max are given too.
+(b) `pipeline`: 8 views of 800x800 from a D8 W256 NeRF (synthetic weights, 64 + 128 samples), point set = 3 of them. Wall time
+    (host clock around a device synchronisation) of build_scene_maps, render included, against the file pipeline for the same
+    views in a fresh temporary directory on the local disk, each arm run twice in alternation (both runs reported); the render
+    alone (the same 8 views, nothing else) is timed separately, and the bytes each arm leaves on disk are counted.
+Writes one JSON object (default profiles/r23_scene_maps_bench.json) and prints it."""
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+import synth  # noqa: E402
+
+SIDE, C, WARMUP, RUNS, VIEWS, MASK = 800, 0.02, 5, 20, 8, [0, 3, 6]
+
+
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def summary(ms):
+    q1, med, q3 = (float(v) for v in np.percentile(ms, [25, 50, 75]))
+    return {'ms_median': med, 'ms_min': float(min(ms)), 'ms_max': float(max(ms)), 'spread_iqr_ms': q3 - q1, 'ms': [float(v) for v in ms]}
+
+
+def kernel_arms(dev):
+    from nerfail_amd.create_index_and_dist import index_and_dist
+    from nerfail_amd.GaussNet import create_gauss_w
+    from nerfail_amd.scene import PointSet, view_map
+    S = torch.from_numpy(np.stack([synth.sphere_view_points(SIDE, SIDE, th) for th in (-120., 0., 120.)]).reshape(-1, 3)).to(dev)
+    Q = torch.from_numpy(synth.sphere_view_points(SIDE, SIDE, 45.)).to(dev)
+    ps = PointSet(S)
+    gw = create_gauss_w(dev, C)
+
+    def chain():
+        return gw(index_and_dist(Q, ps.points, method='grid').unsqueeze(0))[0][0]
+
+    def fused():
+        return view_map(Q, ps, C)[0]
+    assert torch.equal(chain(), fused())                      # the two arms compute the same map, bit for bit
+    for _ in range(WARMUP):
+        chain()
+        fused()
+    a, b = [], []
+    for _ in range(RUNS):
+        a.append(event_ms(chain))
+        b.append(event_ms(fused))
+    res = {'shape': '%dx%d view against %d points (3 views of synth.sphere_view_points), c = %g' % (SIDE, SIDE, S.shape[0], C),
+           'chain': summary(a), 'fused': summary(b)}
+    res['fused_minus_chain_ms'] = res['fused']['ms_median'] - res['chain']['ms_median']
+    res['fused_not_slower_than_chain_by_more_than_its_spread'] = bool(res['fused_minus_chain_ms'] <= res['chain']['spread_iqr_ms'])
+    P = SIDE * SIDE
+    # what the chain moves and the fused call does not (both write the [2,P,8] map once)
+    res['bytes_not_moved_per_view'] = {'dist_idx_written_by_the_search': 2 * P * 32, 'stack_copy_read_and_written': 2 * 2 * P * 32,
+                                       'read_back_by_gauss_weight': 2 * P * 32}
+    return res
+
+
+def render_kwargs(dev):
+    from nerfail_amd import run_nerf as RN
+    from nerfail_amd.run_nerf_helpers import NeRF
+    nets = []
+    for seed in (1, 2):
+        sd = synth.nerf_state_dict(seed=seed)
+        m = NeRF(8, 256, 63, 27, 5, [4], True)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+        nets.append(m.to(dev).requires_grad_(False))
+    q = RN.FusedNetworkQuery(RN.get_embedder(10, 0)[0], RN.get_embedder(4, 0)[0])
+    return dict(network_query_fn=q, perturb=0., N_importance=128, network_fine=nets[1], N_samples=64, network_fn=nets[0], use_viewdirs=True,
+                white_bkgd=True, raw_noise_std=0., ndc=False, lindisp=False, near=2., far=6.)
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t, out
+
+
+def tree_bytes(root):
+    return sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(root) for f in fs)
+
+
+def pipeline_arms(dev):
+    from nerfail_amd import GaussNet as G, nerf_to_coord as NC
+    from nerfail_amd.create_index_and_dist import create_index_and_dist
+    from nerfail_amd.dist_to_weight import dist_to_weight
+    from nerfail_amd.scene import build_scene_maps
+    kw = render_kwargs(dev)
+    focal, K = synth.lego_intrinsics(SIDE, SIDE)
+    hwf = [SIDE, SIDE, focal]
+    poses = torch.from_numpy(np.stack([synth.pose_spherical(-180. + 45. * i, -30., 4.) for i in range(VIEWS)]).astype(np.float32))
+    chunk = 1024 * 32
+    Ns = len(MASK) * SIDE * SIDE
+
+    def render_only():
+        with torch.no_grad():
+            for c2w in poses:
+                NC.render(SIDE, SIDE, K, chunk=chunk, c2w=c2w[:3, :4], **kw)
+
+    def files(base):
+        d = os.path.join(base, 'logs', 'blender_paper_bench', 'renderonly_test_000000')
+        os.makedirs(d)
+        for s in ('train', 'val'):
+            os.makedirs(os.path.join(base, 'logs', 'blender_paper_bench', 'renderonly_%s_000000' % s))
+        with torch.no_grad():
+            NC.render_path(poses, hwf, K, chunk, kw, savedir=d)
+        create_index_and_dist('bench', '000000', MASK, basedir=base, train_img_num=0, val_img_num=0, test_img_num=VIEWS)
+        v = dist_to_weight('bench', basedir=base, test_number=VIEWS, val_number=0, train_number=0, c=C)
+        G.load_view_maps(os.path.join(base, 'logs', 'blender_paper_bench', 'index_and_weight', 'test'), list(range(VIEWS)), Ns)
+        return v
+
+    def one_call():
+        return build_scene_maps(kw, poses, hwf, K, MASK, c=C, chunk=chunk).v
+
+    def clear():
+        for c in (G._VIEW_CACHE, G._VIEW_MAPS, G._VIEW_ORI):
+            c.clear()
+    render_only()                                             # warm-up: weight images packed, kernels loaded
+    res = {'shape': '%d views %dx%d, D8 W256 NeRF, 64 + 128 samples, point set = views %s' % (VIEWS, SIDE, SIDE, MASK),
+           'render_only_s': [], 'one_call_s': [], 'file_pipeline_s': [], 'file_pipeline_bytes_on_disk': None, 'one_call_bytes_on_disk': 0}
+    devnull = open(os.devnull, 'w')
+    for _ in range(2):
+        res['render_only_s'].append(wall(render_only)[0])
+        clear()
+        t, v1 = wall(one_call)
+        res['one_call_s'].append(t)
+        clear()
+        base = tempfile.mkdtemp(prefix='scene_maps_bench_')
+        out, sys.stdout = sys.stdout, devnull                 # (the mirrors print a line per view, as the reference's scripts do)
+        try:
+            t, v2 = wall(lambda: files(base))
+        finally:
+            sys.stdout = out
+        res['file_pipeline_s'].append(t)
+        res['file_pipeline_bytes_on_disk'] = tree_bytes(base)
+        shutil.rmtree(base)
+        assert abs(v1 - v2) <= 1e-5 * v2, (v1, v2)
+    res['v'] = v1
+    res['one_call_minus_render_s'] = [a - b for a, b in zip(res['one_call_s'], res['render_only_s'])]
+    res['file_pipeline_minus_render_s'] = [a - b for a, b in zip(res['file_pipeline_s'], res['render_only_s'])]
+    res['note'] = ('wall clock around a device synchronisation; the file pipeline writes and reads a temporary directory of the local disk '
+                   '(page cache warm: written and read back within seconds); the one call renders the 8 views once, the file '
+                   'pipeline too')
+    return res
+
+
+def main():
+    dev = torch.device('cuda:0')
+    res = {'device': torch.cuda.get_device_name(0), 'warmup': WARMUP, 'runs': RUNS, 'command': 'python tools/scene_maps_bench.py',
+           'commit': subprocess.run(['git', 'rev-parse', 'HEAD'], cwd=ROOT, capture_output=True, text=True).stdout.strip()
+           or os.environ.get('NERFAIL_COMMIT', 'unknown')}
+    res['kernel'] = kernel_arms(dev)
+    if '--skip-pipeline' not in sys.argv:
+        res['pipeline'] = pipeline_arms(dev)
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'r23_scene_maps_bench.json')
+    text = json.dumps(res, indent=1)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
+        f.write(text + '\n')
+
+
+if __name__ == '__main__':
+    main()
