@@ -787,6 +787,60 @@ int nerfail_knn8_grid_weights(const float* queries, int64_t n_queries, int64_t n
                               double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ 2-D baseline (u2d revision 1) -- */
+
+/* The IGSM-2D baseline (attack_IGSM_2D.py:263-416 = IG; model/GaussNet.py:340-385 = GN; MyDataset.py:235-294 = MD) around the
+ * classifier: universal_2D_net's forward up to the classifier input in one streaming launch, and clip backward, sign step,
+ * +-epsilon clamp and the write back into the per-view table in another. Like the five sections before it this one only ADDS
+ * entry points: NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays 15, the eval, cls, deepfool and scene revisions stay 1,
+ * and the additions are announced by nerfail_u2d_revision() = 1. No allocation, no synchronisation, no float atomics; the same
+ * bits on every run. */
+int nerfail_u2d_revision(void);
+
+/* GN:356-370 with MD:247-255 for B views of a resident store, chosen by indices that live on the DEVICE. images: dense uint8
+ * [N,P,4] (NERFAIL_EVAL_U8C4; base 16-byte aligned) or [N,P,3] (NERFAIL_EVAL_U8C3; base 4-byte aligned), as for
+ * nerfail_cls_batch; idx int64 [B]; r float32 [N,P,3], view b using row idx[b] - or, with r_shared != 0, ONE [P,3] plane that
+ * every view uses (the broadcast of GN:359-363). Per element, float32:
+ *   o = the original on the white background of MD:247-255: rgb where alpha > 0, else 255 (nerfail_cls_batch's device function;
+ *       a U8C3 store is taken as is);   v = o + r (one rounded add);   x = min(max(v, 0), 255), a NaN stays a NaN (torch.clip).
+ * Outputs, each may be NULL but not both x_rgb and cls_in:
+ *   x_rgb      float32 [B,P,3]  the attacked image (GN:367)
+ *   cls_in     float32 [B,3,P]  the same values planar: the NCHW tensor of GN:369, channel order as stored
+ *   pass_mask  uint8 [B,P]      bit c set when 0 <= v_c <= 255: where torch.clip's backward lets the gradient through (both
+ *                               bounds inclusive; never for a NaN)
+ * An index outside 0..N-1 writes views of NaN and a zero mask and reads nothing of either input. A lane owns four consecutive
+ * pixels (one 16-byte load of a U8C4 store, three of r, three 16-byte stores into the planes) between a scalar head and tail,
+ * as nerfail_cls_batch cuts a view; no byte outside the indexed views (and rows of r) is read. P >= 1; B <= 65535; B == 0 is a
+ * no-op. r, x_rgb and cls_in 4-byte aligned (128-bit accesses are used wherever an address allows). */
+int nerfail_u2d_fwd(const void* images, int format, int64_t N, int64_t P, const int64_t* idx, int B, const float* r, int r_shared,
+                    float* x_rgb, float* cls_in, unsigned char* pass_mask, void* stream);
+
+/* IG:335-379 in ONE launch, in place on rows idx[b] of the table r [N,P,3]. d_cls_in: float32 [B,3,P], the gradient of the loss
+ * with respect to nerfail_u2d_fwd's cls_in; pass_mask: that call's mask. r_init: [N,P,3], or NULL for the zero table IG:250-252
+ * starts from (the same bits as a tensor of zeros, without its N P 12 bytes). Per element, float32, one rounding per operation:
+ *   g  = d where the mask bit is set, else 0 (torch.clip's backward)
+ *   r' = r - a * sign(g) when targeted, else r + a * sign(g)         (torch.sign: sign(+-0) = 0, sign(NaN) = 0; IG:343-352)
+ *   r' = max(r', init - epsilon);   r' = min(r', init + epsilon)     (in this order; a NaN on either side stays, IG:370-377)
+ * The indices of one call must be distinct (the caller guarantees it: two workgroups would otherwise update one row). A row
+ * whose index is outside 0..N-1 is skipped; no other row is read or written. epsilon >= 0 and a finite, else NERFAIL_EINVAL.
+ * P >= 1; B <= 65535; B == 0 is a no-op. */
+int nerfail_u2d_step(float* r, int64_t N, int64_t P, const int64_t* idx, int B, const float* d_cls_in,
+                     const unsigned char* pass_mask, const float* r_init, float a, float epsilon, int targeted, void* stream);
+
+/* IG:316, the image-loss statistic: adds the sum over [B,P,3] of (x_rgb - o)^2 into row[7,8] and the element count 3 P B into
+ * row[9,10] of a NERFAIL_ATTACK_ROW_FLOATS stats row; o as in nerfail_u2d_fwd, from rows idx[b] of the store. The arithmetic and
+ * the fixed summation order are nerfail_img_sqerr's: differences and squares in double, each lane its pixels in order, each
+ * workgroup its lanes, one workgroup the partials; no atomics, the same bits on every run and for a U8C4 and a U8C3 store
+ * holding the same values. A view whose index is outside 0..N-1 reads nothing and makes the sum NaN. scratch:
+ * nerfail_img_sqerr_scratch_bytes() bytes, 8-byte aligned, contents unspecified on return. */
+int nerfail_u2d_sqerr(const float* x_rgb, const void* images, int format, int64_t N, int64_t P, const int64_t* idx, int B,
+                      void* scratch, float* row, void* stream);
+
+/* IG:392-416: nerfail_attack_epoch_close with IG's STRICT rule - the epoch is taken only when its attack accuracy is < the best
+ * so far (> when targeted; IG:408, 413): a tie keeps the earlier epoch. Row, best ({10000, 0, -1, 0} untargeted, {0, 0, -1, 0}
+ * targeted, IG:255-261) and record layouts are those of nerfail_attack_epoch_close; one device function serves both. */
+int nerfail_u2d_epoch_close(const float* row, float* best, int epoch, int targeted, float* record, int32_t* flag, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

@@ -798,6 +798,51 @@ class gauss_net(nn.Module):
         return out.reshape((C,) + tuple(spatial_rgb.shape))
 
 
+def u2d_classifier_size(model_name):
+    """Side length the 2-D baselines resize the classifier input to (GN:372-380), or None for "my_model": the reference's else
+    branch resizes to 299, at which MyCNN cannot run (its seventh stage needs 4 x 4); gauss_net (GN:147) and model_test
+    (MT:195-196) leave my_model at full size, and so does this package - the ONE deviation from GN:340-385."""
+    return None if model_name == "my_model" else (224 if model_name == "vit_b_16" else 299)
+
+
+def u2d_resize(x, model_name):
+    """GN:372-380 on an NCHW batch. No call when the image already has the target size (torchvision returns it unchanged)."""
+    size = u2d_classifier_size(model_name)
+    if size is None or (x.shape[-2] == size and x.shape[-1] == size):
+        return x
+    return resize(x, size)
+
+
+class universal_2D_net(nn.Module):
+    """GN:340-385, the net of the 2-D baselines, in stock torch ops: differentiable with respect to `r` on any device.
+    forward(r, ori_img) -> (r, x_rgb, cla, ori_img, ori_cla) with x_rgb = clip(ori_img + r, 0, 255); `r` is per view
+    [B,H,W,3] or one shared plane [H,W,3] (GN:359-363). The resize rule: u2d_classifier_size / u2d_resize. The classifier sees
+    a contiguous NCHW tensor (the same values as the reference's transposed view). attack.igsm_2d computes the same x_rgb and
+    classifier input with one launch from a resident uint8 store (nerfail_u2d_fwd), bit for bit."""
+
+    def __init__(self, device, c, model, model_name):
+        super(universal_2D_net, self).__init__()
+        self.top_number = 8
+        self.c = torch.nn.Parameter(torch.tensor([c]), requires_grad=False)
+        self.device = device
+        self.model = model
+        self.model_name = model_name
+        self.theta = torch.tensor([[1, 0, 0], [0, 1, 0]], dtype=torch.float, device=device)
+
+    def forward(self, r, ori_img):
+        ori_img = torch.as_tensor(ori_img).detach().to(torch.float)       # GN:357
+        if r.size() != ori_img.size():
+            x_rgb = ori_img + r.unsqueeze(0).broadcast_to(ori_img.size())   # GN:359-363
+        else:
+            x_rgb = ori_img + r
+        x_rgb = torch.clip(x_rgb, min=0, max=255)
+        cla_x = x_rgb.transpose(2, 3).transpose(1, 2).contiguous()
+        cla_ori_img = ori_img.transpose(2, 3).transpose(1, 2).contiguous()
+        cla = self.model(u2d_resize(cla_x, self.model_name))
+        ori_cla = self.model(u2d_resize(cla_ori_img, self.model_name))
+        return r, x_rgb, cla, ori_img, ori_cla
+
+
 def _derives_from(t, src, depth=4):
     """`t` is `src` or was computed from it by at most `depth` autograd nodes."""
     want, level = src.grad_fn, [t.grad_fn]

@@ -1,6 +1,7 @@
 """Mirror of the attack datasets of MyDataset.py (reference = MD): `gauss_dataset` (MD:187-204) and
 `gauss_dataset_rand_select` (MD:207-232, seed 1003) - same constructor arguments, same 5-tuple per item
-(index, ori_img uint8 BGRA [H,W,4], img_index_and_dist float32 [2,H,W,8], save name, mask save name).
+(index, ori_img uint8 BGRA [H,W,4], img_index_and_dist float32 [2,H,W,8], save name, mask save name) - and of the 2-D
+baselines' `universal_2D_dataset` / `universal_2D_dataset_rand_select` (MD:235-294).
 
 What differs is WHERE the tensors come from. The reference reads the PNG and `torch.load`s the 41 MB map from disk for
 every item of every iteration (MD:199-204) and the DataLoader stacks eight of them into a fresh batch tensor. A view's map
@@ -113,6 +114,48 @@ class gauss_dataset_rand_select(gauss_dataset):
         sel = random.sample(range(ori_length), n)
         super().__init__([all_index_and_dist_name_list[i] for i in sel], [all_img_name_list[i] for i in sel],
                          [all_img_save_to_name_list[i] for i in sel], [all_img_mask_save_to_name_list[i] for i in sel], device, Ns)
+
+
+class universal_2D_dataset(Dataset):
+    """MD:235-259: the views of the 2-D baselines (attack_IGSM_2D.py, attack_Universal_2D.py) - same constructor arguments, same
+    item tuple (index, ori_img_3channel uint8 [H,W,3] on the white background of MD:247-255, save name, mask save name). The
+    item is stock torch on `device`; `store()` stacks the files as read (uint8 [N,H,W,4|3]) for attack.igsm_2d, which makes the
+    white background itself (nerfail_u2d_fwd)."""
+
+    def __init__(self, all_img_name_list, all_img_save_to_name_list, all_img_mask_save_to_name_list, device):
+        self.length = len(all_img_name_list)
+        self.all_img_name_list = all_img_name_list
+        self.all_img_save_to_name_list = all_img_save_to_name_list
+        self.all_img_mask_save_to_name_list = all_img_mask_save_to_name_list
+        self.device = device
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, index):
+        ori_img = torch.tensor(_imread_unchanged(self.all_img_name_list[index])).to(self.device)
+        alpha = ori_img[:, :, 3].unsqueeze(-1).broadcast_to([ori_img.size()[0], ori_img.size()[1], 3])     # MD:250-255
+        rgb = ori_img[:, :, :3]
+        ori_img_3channel = torch.where(alpha > 0, rgb, torch.ones_like(rgb) * 255)
+        return index, ori_img_3channel, self.all_img_save_to_name_list[index], self.all_img_mask_save_to_name_list[index]
+
+    def store(self, device=None):
+        """Every file as read, stacked: uint8 [N,H,W,4] (BGRA) or [N,H,W,3], on `device` (default: the dataset's)."""
+        imgs = [np.ascontiguousarray(_imread_unchanged(n)) for n in self.all_img_name_list]
+        if len({i.shape for i in imgs}) > 1:
+            raise ValueError('universal_2D_dataset: the files differ in size or channel count')
+        return torch.from_numpy(np.stack(imgs)).to(self.device if device is None else device)
+
+
+class universal_2D_dataset_rand_select(universal_2D_dataset):
+    """MD:262-294: a fixed random subset (seed 1003, random.sample) of the views."""
+
+    def __init__(self, all_img_name_list, all_img_save_to_name_list, all_img_mask_save_to_name_list, device, select_rate=0.2):
+        random.seed(1003)
+        ori_length = len(all_img_name_list)
+        sel = random.sample(range(ori_length), int(ori_length * select_rate))
+        super().__init__([all_img_name_list[i] for i in sel], [all_img_save_to_name_list[i] for i in sel],
+                         [all_img_mask_save_to_name_list[i] for i in sel], device)
 
 
 def find_classes(directory):

@@ -17,6 +17,7 @@ EVAL_REVISION = 1                        # nerfail_eval_revision: the attack-eva
 CLS_REVISION = 1                         # nerfail_cls_revision: the victim-training entry points (model_train)
 DEEPFOOL_REVISION = 1                    # nerfail_deepfool_revision: the DeepFool gate and step (deepfool.deepfool_native)
 SCENE_REVISION = 1                       # nerfail_scene_revision: the 8-NN search with the Gaussian weights as its epilogue (scene)
+U2D_REVISION = 1                         # nerfail_u2d_revision: the IGSM-2D baseline's forward, step and statistics (attack.igsm_2d)
 DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
 DEEPFOOL_RECORD_WORDS = 4 + 2 * DEEPFOOL_MAX_COMPETITORS    # struct nerfail_deepfool_record as 32-bit words
 EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
@@ -186,6 +187,11 @@ SIGNATURES = {
     'nerfail_knn8_grid_weights_workspace_bytes': (ctypes.c_size_t, [c_i64]),
     'nerfail_knn8_grid_weights_view': (c_i, [c_p, c_i, c_i, c_i64, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p, ctypes.c_size_t, c_p]),
     'nerfail_knn8_grid_weights': (c_i, [c_p, c_i64, c_i64, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p, ctypes.c_size_t, c_p]),
+    'nerfail_u2d_revision': (c_i, []),
+    'nerfail_u2d_fwd': (c_i, [c_p, c_i, c_i64, c_i64, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
+    'nerfail_u2d_step': (c_i, [c_p, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_p]),
+    'nerfail_u2d_sqerr': (c_i, [c_p, c_p, c_i, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p]),
+    'nerfail_u2d_epoch_close': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -250,6 +256,9 @@ def load():
     if lib.nerfail_scene_revision() != SCENE_REVISION:
         raise RuntimeError('nerfail_amd: scene-maps revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_scene_revision(), SCENE_REVISION))
+    if lib.nerfail_u2d_revision() != U2D_REVISION:
+        raise RuntimeError('nerfail_amd: 2-D baseline revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_u2d_revision(), U2D_REVISION))
     _lib = lib
     return lib
 

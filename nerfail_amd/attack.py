@@ -8,7 +8,8 @@ step (one rank) or in the 3 Ns + 1 float buffer - rgb gradient, loss in the tail
 the whole path. `nerfail_s_step` is that body; `nerfail_s`, the whole AS:278-442 loop as a product
 (epoch statistics, best tensor and export epoch, decided on the device, csrc/attack_stats.hip), calls it with its statistics
 and beta and adds one all-reduce of a 16-float statistics row per EPOCH. perturbation_grad, the four-channel autograd path,
-stays apart: it is what the rgb path is compared against.
+stays apart: it is what the rgb path is compared against. `nerfail` is the universal attack (attack_NeRFail.py:269-512) and `igsm_2d`
+the 2-D baseline of NeRFail-S (attack_IGSM_2D.py:263-416, csrc/u2d.hip), each as one call.
 """
 import torch
 
@@ -604,3 +605,170 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
         _pass_done(n_pass, table)
         n_pass += 1
     return NerfailResult(best, table, m1_best, m2_best, best_acc, records, need_to_log)
+
+
+# ---------------------------------------------------------------------------------------------- the product loop (IG:263-416)
+def _igsm2d_batch_done(epoch, batch_index, table):
+    """Called after every attack batch with the table as the step left it (the seam at which the tests record it)."""
+
+
+def _frozen(model):
+    """gauss_net._classifier_is_frozen's rule: every module in eval() mode and no parameter requiring grad."""
+    if not isinstance(model, torch.nn.Module):
+        return False
+    return not any(m.training for m in model.modules()) and not any(p.requires_grad for p in model.parameters())
+
+
+def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targeted=False, batch_size=4, on_export=None, log=print,
+            native=None):
+    """The IGSM-2D baseline, attack_IGSM_2D.py:263-416 (= IG), as one call: the 2-D counterpart of nerfail_s.
+
+    `model`, `model_name`: the victim classifier and the name that selects the resize in front of it (GaussNet.u2d_resize:
+    none for "my_model", 224 for "vit_b_16", else 299). `images`: the views as ONE resident uint8 store [N,H,W,4] (BGRA as cv2
+    reads an RGBA PNG; the white background of MD:247-255 is made on the device) or [N,H,W,3]; a list of such views is stacked
+    once. `label`: the views' class, or the target class when `targeted`. The perturbation is a per-view table [N,H,W,3] that
+    starts at zero (IG:250-252) and is clamped to +-epsilon around zero.
+
+    Epochs 0 .. epochs-2 attack, over batches of `batch_size` views in store order (the last one short; IG:289 iterates the full
+    dataloader in every epoch - the rand-select loader of IG:229 is built and never used). Per batch: nerfail_u2d_fwd (the
+    attacked image, the classifier's planar input, the clip's pass mask), the classifier, the batch's statistics (CE and
+    accuracy of the clean and of the attacked logits, the image loss MSE(x_rgb, ori), all of the table BEFORE this batch's
+    update, IG:306-331), the gradient of the mean CE down to the classifier input (beta is the constant 0, IG:69: the image loss
+    is a printed statistic only) and nerfail_u2d_step: clip backward, sign step, +-epsilon clamp and the write back into the
+    batch's rows in one launch. nerfail_u2d_epoch_close turns the sums into the epoch's means (divided by the number of views,
+    IG:392-400) and applies IG's STRICT rule (IG:407-416: a tie keeps the earlier epoch); nerfail_copy_if keeps the best table.
+    Epoch epochs-1 is the export epoch (IG:286-301, 381-390): the BEST table, no gradient, the same statistics, and
+    `on_export(batch_index, view_indices, adv_u8, mask_u8)` per batch with host uint8 arrays [B,H,W,3] of the attacked image
+    and of the perturbation (negative values become 0, as cv2.imwrite saturates), converted by nerfail_export_u8. With
+    epochs == 1 the zero table is exported.
+
+    The classifier. `native=None` (automatic) or True (insist): when `model` is this package's MyCNN and model_name is
+    "my_model", a step is ops.cnn_fwd with its pool masks, ops.cls_ce with a constant label vector for d loss / d logits,
+    ops.cnn_bwd_data and the step kernel - no autograd graph and no torch op between the launches. Any other classifier, or
+    native=False: the classifier input requires grad, then the resize, the model and autograd.grad. Both paths take
+    d loss / d logits of nn.CrossEntropyLoss() from ONE definition, ops.cls_ce ((softmax - onehot) / B, evaluated in double and
+    rounded once): torch's float32 backward of the same loss differs from it in the last bits, which measured flipped the sign
+    step of 103 of 5.3 million table elements between the two paths at 766 x 766; with one definition they agree bit for bit.
+    Either way the logits are at most NERFAIL_ATTACK_MAX_CLASSES = 32 wide (the statistics' limit).
+
+    As IG:266-272 does, a `model` that is an nn.Module is put in eval() mode and its parameters stop requiring grad. The clean
+    images' logits never change then and are computed once per view for the run (else once per batch, as the reference).
+
+    Host reads: one per epoch (the record, for the reference's four log lines, IG:402-405; log=None keeps the read and drops
+    the lines), plus one wait per export batch. Returns an AttackResult: `best` and `last` are [N,H,W,3]."""
+    from .GaussNet import u2d_resize
+    from .MyModel import MyCNN
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    batch_size = int(batch_size)
+    if not 1 <= batch_size <= 65535:
+        raise ValueError('batch_size must be in 1..65535')
+    dev = _cuda()
+    if isinstance(images, (list, tuple)):
+        images = torch.stack([torch.as_tensor(v) for v in images])
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] not in (3, 4):
+        raise ValueError('images must be a uint8 store [N,H,W,4] (BGRA) or [N,H,W,3]')
+    images = images.to(dev).contiguous()
+    N, H, W = images.shape[:3]
+    if N < 1:
+        raise ValueError('images holds no view')
+    can_native = isinstance(model, MyCNN) and model_name == "my_model"
+    if native and not can_native:
+        raise ValueError('igsm_2d: native=True needs this package\'s MyCNN as `model` and model_name == "my_model"')
+    use_native = can_native and (native is None or bool(native))
+    if isinstance(model, torch.nn.Module):                                # IG:266-272
+        model.train(False)
+        for p in model.parameters():
+            p.requires_grad = False
+    a, epsilon, targeted = float(a), float(epsilon), bool(targeted)
+    label_i = int(label)
+    lab32 = torch.full((batch_size,), label_i, dtype=torch.int32, device=dev)
+    table = torch.zeros((N, H, W, 3), dtype=torch.float32, device=dev)     # IG:250; its init is the zero table: r_init = NULL
+    best = torch.zeros_like(table)
+    zero_plane = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+    batches = [(lo, min(lo + batch_size, N)) for lo in range(0, N, batch_size)]
+    idx_all = torch.arange(N, dtype=torch.int64, device=dev)
+    stats = _EpochStats(epochs, targeted, label_i, dev)
+    ce_row = torch.zeros((_lib.ATTACK_ROW_FLOATS,), dtype=torch.float32, device=dev)   # ops.cls_ce's own sums: not read
+    bufs = _ExportBuffers()
+    records = []
+    lib = stats.lib
+
+    def classify(cls_in):
+        return model(u2d_resize(cls_in, model_name))
+
+    def clean_logits(lo, hi):
+        with torch.no_grad():
+            _, clean_in, _ = ops.u2d_fwd(images, idx_all[lo:hi], zero_plane, False, True, False)   # o + 0, clipped: o itself
+            return _lib.f32c(classify(clean_in))
+    ori_cla_all = torch.cat([clean_logits(lo, hi) for lo, hi in batches]) if _frozen(model) else None
+
+    def batch_stats(epoch, lo, hi, cla, x_rgb):
+        """IG:306-331 for one batch: five sums into the epoch's row, no host read."""
+        oc = ori_cla_all[lo:hi] if ori_cla_all is not None else clean_logits(lo, hi)
+        c = _lib.f32c(cla)
+        row = _lib.dev(stats.rows[epoch])
+        _lib.check(lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], label_i, row, _lib.stream()))
+        ops.u2d_sqerr(x_rgb, images, idx_all[lo:hi], stats.scratch, stats.rows[epoch])
+
+    def finish(epoch):
+        ops.u2d_epoch_close(stats.rows[epoch], stats.best, epoch, targeted, stats.records[epoch], stats.flag)
+        if epoch < epochs - 1:
+            stats.keep_if_taken(table, best)
+        d = dict(zip(STAT_FIELDS, stats.records[epoch].cpu().tolist()))    # THE host read of the epoch
+        for k in ('views', 'taken', 'best_epoch', 'epoch', 'test_correct', 'attack_correct'):
+            d[k] = int(d[k])
+        records.append(d)
+        if log is not None:
+            log('Attack ...... [%d/%d]' % (epoch, epochs))
+            log('{} Loss: {:.4f} Acc: {:.4f}'.format('test', d['test_loss'], d['test_acc']))                       # IG:402-405
+            log('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', d['attack_loss'], d['attack_acc']))
+            log('{} Beta Loss: {:.4f} Beta Img Loss: {:.4f}'.format('attack', d['attack_loss'], 0. * d['img_loss']))
+            log('{} Img Loss: {:.4f} Total Loss: {:.4f}'.format('attack', d['img_loss'], d['attack_loss']))
+
+    for epoch in range(epochs - 1):
+        for bi, (lo, hi) in enumerate(batches):
+            ib, B = idx_all[lo:hi], hi - lo
+            with torch.no_grad():
+                x_rgb, cls_in, mask = ops.u2d_fwd(images, ib, table, True, True, True)
+            if use_native:
+                with torch.no_grad():
+                    cla, ws, pool = ops.cnn_fwd(model.packed(), cls_in, model.num_classes, True)
+                    batch_stats(epoch, lo, hi, cla, x_rgb)
+                    d_logits = ops.cls_ce(cla, lab32[:B], ce_row, True)                      # (softmax - onehot) / B
+                    d_in = ops.cnn_bwd_data(model.packed(), ws, pool, d_logits, H, W)
+            else:
+                cls_in.requires_grad_()
+                cla = classify(cls_in)
+                batch_stats(epoch, lo, hi, cla.detach(), x_rgb)
+                d_logits = ops.cls_ce(_lib.f32c(cla), lab32[:B], ce_row, True)              # CrossEntropyLoss()'s gradient, as above
+                d_in = _lib.f32c(torch.autograd.grad(cla, cls_in, grad_outputs=d_logits.to(cla.dtype))[0])
+            ops.u2d_step(table, ib, d_in, mask, None, a, epsilon, targeted)
+            _igsm2d_batch_done(epoch, bi, table)
+        finish(epoch)
+    epoch = epochs - 1
+    for bi, (lo, hi) in enumerate(batches):
+        with torch.no_grad():
+            x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[lo:hi], best, True, True, False)
+            cla = classify(cls_in)
+            batch_stats(epoch, lo, hi, cla, x_rgb)
+        if on_export is None:
+            continue
+        pert = best[lo:hi]
+        if pert.data_ptr() % 16:
+            pert = pert.clone()
+        n = x_rgb.numel()
+        slot = -(-n // 16) * 16                                           # each image starts 16-byte aligned, whatever B, H and W
+        d_u8, h_u8, ev = bufs.get((slot,), dev)
+        _lib.check(lib.nerfail_export_u8(_lib.dev(x_rgb), n, _lib.dev(d_u8[0]), _lib.stream()))
+        _lib.check(lib.nerfail_export_u8(_lib.dev(pert), n, _lib.dev(d_u8[1]), _lib.stream()))
+        h_u8.copy_(d_u8, non_blocking=True)
+        ev.record()
+        ev.synchronize()
+        arr = h_u8.numpy()[:, :n].reshape((2,) + tuple(x_rgb.shape))
+        on_export(bi, list(range(lo, hi)), arr[0].copy(), arr[1].copy())
+    finish(epoch)                                                         # (its decision moves no tensor: the epoch ran on `best` itself)
+    last_attack = records[-2] if epochs > 1 else None
+    return AttackResult(best, table, records, last_attack['best_epoch'] if last_attack else -1,
+                        last_attack['best_acc'] if last_attack else None)

@@ -10,6 +10,7 @@
 // one float32 rounding of the his, ~6e-8 relative, not exact). One lane adds into the row per launch; launches on a stream are ordered: no atomics anywhere,
 // every sum has a fixed order, every result is bitwise reproducible.
 #include "common.h"
+#include "attack_close.h"
 
 namespace nerfail {
 
@@ -122,32 +123,7 @@ __global__ __launch_bounds__(256) void img_sqerr_grad_add_kernel(const float4* _
 __global__ __launch_bounds__(64) void attack_epoch_close_kernel(const float* __restrict__ row, float* __restrict__ best, int epoch,
                                                                 int targeted, float* __restrict__ record, int* __restrict__ flag) {
     if (threadIdx.x != 0) return;
-    const double views = (double)row[6];
-    const float test_loss = (float)(pair_get(row + 0) / views), attack_loss = (float)(pair_get(row + 2) / views);
-    const float test_acc = (float)((double)row[4] / views), attack_acc = (float)((double)row[5] / views);
-    const float img_loss = (float)(pair_get(row + 7) / pair_get(row + 9));
-    const float best_acc = best[0];
-    const bool take = targeted ? (attack_acc >= best_acc) : (attack_acc <= best_acc);      // false for a NaN accuracy
-    if (take) {
-        best[0] = attack_acc;
-        best[1] = attack_loss;
-        best[2] = (float)epoch;
-    }
-    flag[0] = take ? 1 : 0;
-    record[0] = test_loss;
-    record[1] = test_acc;
-    record[2] = attack_loss;
-    record[3] = attack_acc;
-    record[4] = img_loss;
-    record[5] = row[6];
-    record[6] = take ? 1.f : 0.f;
-    record[7] = take ? (float)epoch : best[2];
-    record[8] = take ? attack_acc : best_acc;
-    record[9] = take ? attack_loss : best[1];
-    record[10] = (float)epoch;
-    record[11] = row[4];
-    record[12] = row[5];
-    record[13] = record[14] = record[15] = 0.f;
+    attack_epoch_close_body(row, best, epoch, targeted, false, record, flag);      // a tie goes to the later epoch
 }
 
 // ---- the best tensor of AS:426/431: copied when the close said so. The flag word is wave-uniform (one scalar load).

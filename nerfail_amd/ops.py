@@ -904,3 +904,88 @@ def cnn_bwd_weights_scratch_floats(B, H, W, num_classes):
 
 
 CLS_OPS = ('cls_batch', 'cls_ce', 'cnn_bwd_weights_into', 'cnn_sgd_step', 'cls_epoch_close')
+
+
+# ----------------------------------------------------------------------------------------------- 2-D baseline (attack_IGSM_2D.py:263-416, GN:340-385; u2d revision 1)
+def _u2d_shapes(images, idx, name):
+    fmt = _cls_format(images)
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise ValueError('%s: idx must be int64 [B]' % name)
+    N = images.shape[0]
+    P = images[0].numel() // images.shape[-1] if N else 0
+    return fmt, N, P, idx.shape[0], tuple(images.shape[1:-1])
+
+
+@custom_op(NS + '::u2d_fwd', mutates_args=(), device_types='cuda')
+def u2d_fwd(images: Tensor, idx: Tensor, r: Tensor, want_x_rgb: bool, want_cls_in: bool, want_mask: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """GN:356-370 for the views idx (int64 [B], on the device) of a resident uint8 store [N,...,4|3]: (x_rgb float32 [B,...,3] =
+    clip(white(ori) + r, 0, 255), cls_in float32 [B,3,...] = the same planar, pass_mask uint8 [B,...] = where the clip's backward
+    passes, one bit per channel) - an empty tensor for each output not wanted. r: the table [N,...,3], view b using row idx[b],
+    or one shared plane [...,3]."""
+    fmt, N, P, B, hw = _u2d_shapes(images, idx, 'u2d_fwd')
+    if not (want_x_rgb or want_cls_in):
+        raise ValueError('u2d_fwd: x_rgb or cls_in must be wanted')
+    shared = r.dim() == images.dim() - 1
+    if r.dtype != torch.float32 or not r.is_contiguous() or r.numel() != (1 if shared else N) * P * 3:
+        raise ValueError('u2d_fwd: r must be contiguous float32 [N,...,3], or one plane [...,3]')
+    dev = images.device
+    x_rgb = torch.empty((B,) + hw + (3,) if want_x_rgb else (0,), dtype=torch.float32, device=dev)
+    cls_in = torch.empty((B, 3) + hw if want_cls_in else (0,), dtype=torch.float32, device=dev)
+    mask = torch.empty((B,) + hw if want_mask else (0,), dtype=torch.uint8, device=dev)
+    _chk(_lib.load().nerfail_u2d_fwd(_lib.dev(images, 'images'), fmt, N, P, _lib.dev(idx, 'idx'), B, _lib.dev(r, 'r'), int(shared),
+                                     _lib.dev(x_rgb) if want_x_rgb else None, _lib.dev(cls_in) if want_cls_in else None,
+                                     _lib.dev(mask) if want_mask else None, _s()))
+    return x_rgb, cls_in, mask
+
+
+@u2d_fwd.register_fake
+def _(images, idx, r, want_x_rgb, want_cls_in, want_mask):
+    B, hw = idx.shape[0], tuple(images.shape[1:-1])
+    return (images.new_empty((B,) + hw + (3,) if want_x_rgb else (0,), dtype=torch.float32),
+            images.new_empty((B, 3) + hw if want_cls_in else (0,), dtype=torch.float32),
+            images.new_empty((B,) + hw if want_mask else (0,), dtype=torch.uint8))
+
+
+@custom_op(NS + '::u2d_step', mutates_args=('r',), device_types='cuda')
+def u2d_step(r: Tensor, idx: Tensor, d_cls_in: Tensor, pass_mask: Tensor, r_init: Optional[Tensor], a: float, epsilon: float,
+             targeted: bool) -> None:
+    """IG:335-379 in place on rows idx (int64 [B], distinct) of the table r [N,...,3]: the clip's backward (pass_mask) applied to
+    d_cls_in [B,3,...], the sign step, the clamp to r_init +- epsilon (r_init None: the zero table)."""
+    if r.dtype != torch.float32 or not r.is_contiguous() or r.dim() < 3 or r.shape[-1] != 3:
+        raise ValueError('u2d_step: r must be a contiguous float32 table [N,...,3]')
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise ValueError('u2d_step: idx must be int64 [B]')
+    N, B = r.shape[0], idx.shape[0]
+    P = r[0].numel() // 3 if N else 0
+    if d_cls_in.dtype != torch.float32 or not d_cls_in.is_contiguous() or d_cls_in.numel() != B * 3 * P:
+        raise ValueError('u2d_step: d_cls_in must be contiguous float32 [B,3,...]')
+    if pass_mask.dtype != torch.uint8 or not pass_mask.is_contiguous() or pass_mask.numel() != B * P:
+        raise ValueError('u2d_step: pass_mask must be contiguous uint8 [B,...]')
+    if r_init is not None and (r_init.dtype != torch.float32 or not r_init.is_contiguous() or r_init.shape != r.shape):
+        raise ValueError('u2d_step: r_init must be a contiguous float32 tensor with the shape of r')
+    _chk(_lib.load().nerfail_u2d_step(_lib.dev(r, 'r'), N, P, _lib.dev(idx, 'idx'), B, _lib.dev(d_cls_in, 'd_cls_in'),
+                                      _lib.dev(pass_mask, 'pass_mask'), _lib.dev(r_init, 'r_init'), a, epsilon, int(targeted), _s()))
+
+
+def u2d_sqerr(x_rgb, images, idx, scratch, row):
+    """IG:316: adds sum (x_rgb - white(ori))^2 over the views idx and the element count into the stats row (nerfail_u2d_sqerr)."""
+    fmt, N, P, B, _ = _u2d_shapes(images, idx, 'u2d_sqerr')
+    _row_ok(row)
+    if x_rgb.dtype != torch.float32 or not x_rgb.is_contiguous() or x_rgb.numel() != B * P * 3:
+        raise ValueError('u2d_sqerr: x_rgb must be contiguous float32 [B,...,3]')
+    if scratch.numel() * scratch.element_size() < _lib.load().nerfail_img_sqerr_scratch_bytes():
+        raise ValueError('u2d_sqerr: scratch is smaller than nerfail_img_sqerr_scratch_bytes()')
+    _chk(_lib.load().nerfail_u2d_sqerr(_lib.dev(x_rgb, 'x_rgb'), _lib.dev(images, 'images'), fmt, N, P, _lib.dev(idx, 'idx'), B,
+                                       _lib.c_p(scratch.data_ptr()), _lib.dev(row), _s()))
+
+
+def u2d_epoch_close(row, best, epoch, targeted, record, flag):
+    """IG:392-416: attack_epoch_close with the strict rule (a tie keeps the earlier epoch)."""
+    _row_ok(row)
+    _row_ok(record, 'record')
+    if best.dtype != torch.float32 or best.numel() != 4 or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError('best must be float32 [4] and flag int32 [1]')
+    _chk(_lib.load().nerfail_u2d_epoch_close(_lib.dev(row), _lib.dev(best), epoch, int(targeted), _lib.dev(record), _lib.dev(flag), _s()))
+
+
+U2D_OPS = ('u2d_fwd', 'u2d_step')
