@@ -841,6 +841,56 @@ int nerfail_u2d_sqerr(const float* x_rgb, const void* images, int format, int64_
  * targeted, IG:255-261) and record layouts are those of nerfail_attack_epoch_close; one device function serves both. */
 int nerfail_u2d_epoch_close(const float* row, float* best, int epoch, int targeted, float* record, int32_t* flag, void* stream);
 
+/* ------------------------------------------------------------------ 2-D universal baseline (uap2d revision 1) -- */
+
+/* The UAP-2D baseline (attack_UAP_2D.py:241-358 = UA; deepfool.py:10-111 with universal_2d = DF) around the classifier: one
+ * DeepFool step on the ONE image-plane table [P,3] that every view shares (UA:219, GN:359-363), and the table's update with
+ * the +-epsilon projection of UA:317-319. Like the six sections before it this one only ADDS entry points: NERFAIL_ABI_VERSION
+ * stays 14, nerfail_abi_revision() stays 15, the eval, cls, deepfool, scene and u2d revisions stay 1, and the additions are
+ * announced by nerfail_uap2d_revision() = 1. nerfail_deepfool_step chooses with the same device function as before (its bits
+ * are unchanged). No allocation, no synchronisation, no atomics; the same bits on every run. */
+int nerfail_uap2d_revision(void);
+
+/* Float32 terms a lane of the norm kernel adds per competitor before it widens to double: two quads of four pixels, three
+ * channels each. One norm workgroup (256 lanes) covers 256 * NERFAIL_UAP2D_NORM_TERMS / 3 = 2048 pixels. */
+#define NERFAIL_UAP2D_NORM_TERMS 24
+
+/* DF:68-102 with universal_2d once the gradients exist. grads = [n_rhs][3][P] planar float32, d logit / d classifier input
+ * (nerfail_u2d_fwd's cls_in) of ONE view: row 0 the clean class o, row r + 1 competitor r of the record - what
+ * nerfail_cnn_bwd_data_multi returns for one-hot rows, or n_rhs autograd.grad calls. pass_mask: uint8 [P], nerfail_u2d_fwd's
+ * three bits per pixel of the forward the gradients belong to. r0, rot, r_out: float32 [P,3] interleaved (the table at the
+ * call's start, the accumulated direction, the table the next forward runs on). Three launches, no host in between:
+ *   norms   norms2[k-1] = sum over pixels p and channels c whose bit c of pass_mask[p] is set of (G_k - G_0)^2. A cleared bit
+ *           contributes exactly 0 whatever the gradient holds there, a NaN included (torch.clip's backward, where(pass, grad, 0)).
+ *           Pixels are taken in quads of four; lane t of workgroup b owns quads (2 b + i) * 256 + t, i = 0, 1, and adds their
+ *           NERFAIL_UAP2D_NORM_TERMS terms in float32 in the order (quad, pixel, channel) - per term one rounded subtract, one
+ *           rounded multiply, one rounded add, no fused multiply-add - then widens to double: the 64 lanes of a wave by
+ *           butterfly, the four waves in order, one partial per workgroup and competitor in scratch.
+ *   choose  one workgroup adds the partials in a fixed tree, rounds each norm to float32 once, and chooses exactly as
+ *           nerfail_deepfool_step does (one device function; see there): first minimum, a NaN never chosen, competitor 0 when
+ *           targeted. Nothing chosen: scale = 0, *trace_slot = -1; else *trace_slot = cls[best]. A record whose n_comp is not
+ *           n_rhs - 1 chooses nothing.
+ *   apply   per element, float32, one rounding per operation, no fused multiply-add:
+ *             d = G_best - G_0 where the bit is set, else 0;   rot += scale * d;
+ *             r_out = clamp(r0 + overshoot * rot, -255, 255) on all three channels (no alpha restore: DF:104), a NaN stays.
+ *           scale == 0 or best outside 1..n_rhs-1 leaves rot alone and still writes r_out. A lane owns four consecutive pixels
+ *           between a scalar head and tail cut at the 16-byte boundaries of rot; 128-bit accesses of the gradient planes and of
+ *           r0 / rot / r_out, a 32-bit one of the mask, wherever an address allows.
+ * scratch: nerfail_uap2d_step_scratch_bytes(n_rhs, P) bytes, 8-byte aligned (0 for n_rhs outside 2..8 or P outside 1..2^31):
+ * the partials, then {norms2[8], best, scale}; contents unspecified on return, except that the caller may read norms2 there.
+ * overshoot finite; every float pointer 4-byte aligned; rot is updated in place; r_out aliases nothing else. Anything else is
+ * NERFAIL_EINVAL before the first launch. */
+size_t nerfail_uap2d_step_scratch_bytes(int n_rhs, int64_t P);
+int nerfail_uap2d_step(const float* grads, int n_rhs, int64_t P, const unsigned char* pass_mask,
+                       const nerfail_deepfool_record* record, void* scratch, size_t scratch_bytes, float overshoot,
+                       const float* r0, float* rot, float* r_out, int32_t* trace_slot, void* stream);
+
+/* UA:317-319 with DF:109 in one stream, in place on the n = 3 P floats of the table; r_final: the table DeepFool ended on (its
+ * r_out), the table itself being DeepFool's r0. Per element, float32, one rounding per operation:
+ *   dr = r_final - t;   t' = t + dr;   table = clamp(t', -epsilon, +epsilon), a NaN stays (torch.clamp).
+ * epsilon >= 0 (not NaN), 1 <= n <= 3 * 2^31, both pointers 4-byte aligned, else NERFAIL_EINVAL. */
+int nerfail_uap2d_accumulate(float* table, const float* r_final, float epsilon, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

@@ -18,6 +18,8 @@ CLS_REVISION = 1                         # nerfail_cls_revision: the victim-trai
 DEEPFOOL_REVISION = 1                    # nerfail_deepfool_revision: the DeepFool gate and step (deepfool.deepfool_native)
 SCENE_REVISION = 1                       # nerfail_scene_revision: the 8-NN search with the Gaussian weights as its epilogue (scene)
 U2D_REVISION = 1                         # nerfail_u2d_revision: the IGSM-2D baseline's forward, step and statistics (attack.igsm_2d)
+UAP2D_REVISION = 1                       # nerfail_uap2d_revision: the UAP-2D baseline's DeepFool step and projection (attack.uap_2d)
+UAP2D_NORM_TERMS = 24                    # NERFAIL_UAP2D_NORM_TERMS: float32 terms per lane of nerfail_uap2d_step's norms
 DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
 DEEPFOOL_RECORD_WORDS = 4 + 2 * DEEPFOOL_MAX_COMPETITORS    # struct nerfail_deepfool_record as 32-bit words
 EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
@@ -192,6 +194,10 @@ SIGNATURES = {
     'nerfail_u2d_step': (c_i, [c_p, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_p]),
     'nerfail_u2d_sqerr': (c_i, [c_p, c_p, c_i, c_i64, c_i64, c_p, c_i, c_p, c_p, c_p]),
     'nerfail_u2d_epoch_close': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    'nerfail_uap2d_revision': (c_i, []),
+    'nerfail_uap2d_step_scratch_bytes': (ctypes.c_size_t, [c_i, c_i64]),
+    'nerfail_uap2d_step': (c_i, [c_p, c_i, c_i64, c_p, c_p, c_p, ctypes.c_size_t, c_f, c_p, c_p, c_p, c_p, c_p]),
+    'nerfail_uap2d_accumulate': (c_i, [c_p, c_p, c_f, c_i64, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -259,6 +265,9 @@ def load():
     if lib.nerfail_u2d_revision() != U2D_REVISION:
         raise RuntimeError('nerfail_amd: 2-D baseline revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_u2d_revision(), U2D_REVISION))
+    if lib.nerfail_uap2d_revision() != UAP2D_REVISION:
+        raise RuntimeError('nerfail_amd: 2-D universal baseline revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_uap2d_revision(), UAP2D_REVISION))
     _lib = lib
     return lib
 

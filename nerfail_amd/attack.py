@@ -8,8 +8,9 @@ step (one rank) or in the 3 Ns + 1 float buffer - rgb gradient, loss in the tail
 the whole path. `nerfail_s_step` is that body; `nerfail_s`, the whole AS:278-442 loop as a product
 (epoch statistics, best tensor and export epoch, decided on the device, csrc/attack_stats.hip), calls it with its statistics
 and beta and adds one all-reduce of a 16-float statistics row per EPOCH. perturbation_grad, the four-channel autograd path,
-stays apart: it is what the rgb path is compared against. `nerfail` is the universal attack (attack_NeRFail.py:269-512) and `igsm_2d`
-the 2-D baseline of NeRFail-S (attack_IGSM_2D.py:263-416, csrc/u2d.hip), each as one call.
+stays apart: it is what the rgb path is compared against. `nerfail` is the universal attack (attack_NeRFail.py:269-512), `igsm_2d`
+the 2-D baseline of NeRFail-S (attack_IGSM_2D.py:263-416, csrc/u2d.hip) and `uap_2d` the 2-D baseline of NeRFail
+(attack_UAP_2D.py:241-358, csrc/uap2d.hip), each as one call.
 """
 import torch
 
@@ -772,3 +773,206 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
     last_attack = records[-2] if epochs > 1 else None
     return AttackResult(best, table, records, last_attack['best_epoch'] if last_attack else -1,
                         last_attack['best_acc'] if last_attack else None)
+
+
+# ---------------------------------------------------------------------------------------------- the product loop (UA:241-358)
+class Uap2dResult:
+    """What uap_2d returns. `best`: the table [H,W,3] the strict rule of UA:349-358 kept (device tensor) - the attack's result,
+    what the export pass rendered; `last`: the table the loop ended on (from the export pass on the reference's table IS the best
+    tensor, UA:269, so `last` then aliases it until the rule replaces `best` by a copy); `best_acc`: the attack accuracy recorded
+    with `best` (0 / 10000 when the rule never fired); `stats`: one dict per PASS over the views (a pass is one turn of UA:241's
+    while loop; `epoch` is the epoch it ran as, `next_epoch` where the loop went)."""
+
+    def __init__(self, best, last, best_acc, stats):
+        self.best, self.last, self.best_acc, self.stats = best, last, best_acc, stats
+
+
+def _uap2d_pass_done(index, table):
+    """Called at the end of every pass with the table as the pass left it (the seam at which the tests record it)."""
+
+
+def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, targeted=False, df_max_iter=1000, overshoot=0.02,
+           num_classes=8, attack_views=None, export_views=None, on_export=None, log=print, native=None):
+    """The UAP-2D baseline, attack_UAP_2D.py:241-358 (= UA), as one call: the 2-D counterpart of nerfail.
+
+    `model`, `model_name`, `images`, `label`: as for igsm_2d (the resident uint8 store [N,H,W,4|3]; the resize rule of
+    GaussNet.u2d_resize). The perturbation is ONE table [H,W,3] that starts at zero (UA:219) and that every view shares
+    (GN:359-363). `attack_views` / `export_views`: the view indices of an attack pass / of the export pass, or a callable of the
+    pass number that returns them (the rand-select loader of UA:198); default: every view in store order. Batch size 1, as the
+    reference fixes it.
+
+    The loop is the reference's, quirks included. `while epoch < epochs` steps `epoch` itself. A pass before the last epoch
+    visits every view: nerfail_u2d_fwd on the shared table, the classifier, the four running sums of UA:275-289 (in a device row)
+    and - only when the raw argmax of the attacked logits still equals the clean one (UA:297-304) - DeepFool on the view
+    (deepfool.deepfool_2d[_native], margins m1 / m2). When it finished before df_max_iter (UA:315-319) nerfail_uap2d_accumulate
+    adds its perturbation and clamps the table to +-epsilon; a call that hits the cap changes nothing (there is no m2 rule and
+    no m1 bisection here). A pass that changed nothing jumps to the last epoch, else the epoch advances (UA:335-338). The last
+    epoch is the export pass (UA:262-270, 322-333): the BEST table, no gradient, over `export_views`, and
+    `on_export(index, view_indices, adv_u8, mask_u8, ori_u8)` per view with host uint8 arrays [1,H,W,3] of the attacked image,
+    [H,W,3] of the perturbation (negative values become 0, as cv2.imwrite saturates) and [1,H,W,3] of the clean image on its
+    white background, converted by nerfail_export_u8. Every pass, the export pass included, ends with its means (sums / views of
+    the pass) and the STRICT best rule of UA:349-358 (> targeted, < untargeted, from 0 / 10000). With epochs == 1 the zero table
+    is exported.
+
+    The classifier. As UA:244-250 does, a `model` that is an nn.Module is put in eval() mode and its parameters stop requiring
+    grad; the clean images' logits then never change and are computed once per view for the run (else at every visit).
+    `native=None` (automatic) runs deepfool.deepfool_2d_native - with this package's MyCNN under "my_model" its class gradients
+    come from ONE ops.cnn_bwd_data_multi, with any other classifier from autograd with respect to the classifier input;
+    `native=True` insists on MyCNN; `native=False` runs the mirror deepfool.deepfool_2d through GaussNet.universal_2D_net.
+
+    Host reads: one per visit for the skip decision, DeepFool's own (one per iteration), one per pass for the record and the
+    reference's log lines (log=None keeps the read and drops the lines), one wait per exported view. An export pass without
+    views is a ValueError (nothing would end the loop). The update is sequential over the views: there is nothing to shard, and
+    more than one rank is a ValueError.
+
+    Returns a Uap2dResult. Every dict of `stats` holds epoch, next_epoch, views, test_loss, test_acc, attack_loss, attack_acc,
+    test_correct, attack_correct, skipped, attacked, completed, deepfool_iters, taken and `visits`: per visit (view index,
+    skipped, iter_k, the chosen class of every iteration or None with the mirror)."""
+    from . import deepfool as DF
+    from .GaussNet import u2d_resize, universal_2D_net
+    from .MyModel import MyCNN
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    if sharding.world_and_rank(None)[0] > 1:
+        raise ValueError('uap_2d updates one table view by view: there is nothing to shard over %d ranks' % sharding.world_and_rank(None)[0])
+    dev = _cuda()
+    if isinstance(images, (list, tuple)):
+        images = torch.stack([torch.as_tensor(v) for v in images])
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] not in (3, 4):
+        raise ValueError('images must be a uint8 store [N,H,W,4] (BGRA) or [N,H,W,3]')
+    images = images.to(dev).contiguous()
+    N, H, W = images.shape[:3]
+    if N < 1:
+        raise ValueError('images holds no view')
+    if export_views is not None and not callable(export_views) and len(export_views) == 0:
+        raise ValueError('uap_2d: the export epoch needs at least one view (export_views is empty)')
+    can_native = isinstance(model, MyCNN) and model_name == "my_model"
+    if native and not can_native:
+        raise ValueError('uap_2d: native=True needs this package\'s MyCNN as `model` and model_name == "my_model"')
+    use_native = native is None or bool(native)
+    if isinstance(model, torch.nn.Module):                                # UA:244-250
+        model.train(False)
+        for p in model.parameters():
+            p.requires_grad = False
+    frozen = _frozen(model)
+    net = universal_2D_net(dev, 0.02, model, model_name)
+    epsilon, targeted, df_max_iter = float(epsilon), bool(targeted), int(df_max_iter)
+    label_i = int(label)
+    say = log if log is not None else (lambda *_: None)
+    lib = _lib.load()
+    table = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)       # UA:219
+    best = table.clone()
+    best_acc = 0 if targeted else 10000                                   # UA:234-237
+    zero_plane = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+    idx_all = torch.arange(N, dtype=torch.int64, device=dev)
+    bufs = _ExportBuffers()
+    clean = {}
+
+    def classify(cls_in):
+        return model(u2d_resize(cls_in, model_name))
+
+    def clean_logits(v):
+        if v in clean:
+            return clean[v]
+        with torch.no_grad():
+            _, clean_in, _ = ops.u2d_fwd(images, idx_all[v:v + 1], zero_plane, False, True, False)   # o + 0, clipped: o itself
+            oc = _lib.f32c(classify(clean_in))
+        if frozen:
+            clean[v] = oc
+        return oc
+
+    def views_of(src, n_pass):
+        if src is None:
+            return list(range(N))
+        vs = [int(v) for v in (src(n_pass) if callable(src) else src)]
+        if any(not 0 <= v < N for v in vs):
+            raise ValueError('uap_2d: a view index is outside the store (0..%d)' % (N - 1))
+        return vs
+
+    def export_view(i, v, x_rgb):
+        n = x_rgb.numel()
+        slot = -(-n // 16) * 16                                           # each image starts 16-byte aligned
+        d_u8, h_u8, ev = bufs.get((3 * slot // 2,), dev)                  # [2, 3 slot / 2]: three slots
+        with torch.no_grad():
+            ori, _, _ = ops.u2d_fwd(images, idx_all[v:v + 1], zero_plane, True, False, False)
+        d = d_u8.view(-1)
+        for k, src in enumerate((x_rgb, table, ori)):
+            _lib.check(lib.nerfail_export_u8(_lib.dev(src), n, _lib.dev(d[k * slot:k * slot + n]), _lib.stream()))
+        h_u8.copy_(d_u8, non_blocking=True)
+        ev.record()
+        ev.synchronize()
+        arr = h_u8.numpy().reshape(-1)
+        on_export(i, [v], arr[:n].reshape(1, H, W, 3).copy(), arr[slot:slot + n].reshape(H, W, 3).copy(),
+                  arr[2 * slot:2 * slot + n].reshape(1, H, W, 3).copy())
+
+    records = []
+    epoch, n_pass = 0, 0
+    while epoch < epochs:
+        say('Attack ...... [' + str(epoch) + '/' + str(epochs) + ']')
+        not_changed = True
+        export = epoch == epochs - 1
+        items = views_of(export_views if export else attack_views, n_pass)
+        if export and not items:                                          # (nothing would set tensor_not_changed: the loop could not end)
+            raise ValueError('uap_2d: the export epoch needs at least one view (export_views is empty)')
+        stats = _PassStats(label_i, dev)
+        visits, skipped, attacked, completed, iters = [], 0, 0, 0, 0
+        pass_epoch = epoch
+        for i, v in enumerate(items):
+            if export and i == 0:
+                table = best                                              # UA:269: the table IS the best tensor from here on
+            with torch.no_grad():
+                x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[v:v + 1], table, export and on_export is not None, True, False)
+                cla = _lib.f32c(classify(cls_in))
+            ori_cla = clean_logits(v)
+            stats.batch(epoch, cla, ori_cla)                              # UA:275-289
+            if export:
+                if on_export is not None:
+                    export_view(i, v, x_rgb)
+                not_changed = False                                       # UA:333
+                continue
+            if not _same_class(cla, ori_cla):                             # UA:297-304
+                skipped += 1
+                visits.append((v, True, 0, []))
+                continue
+            kw = dict(num_classes=num_classes, max_iter=df_max_iter, target_label=label_i if targeted else None, overshoot=overshoot,
+                      m1=m1, m2=m2)
+            if use_native:
+                _, iter_k, _, _, r_final, classes = DF.deepfool_2d_native((table, None), epsilon, net, images=images, view=v,
+                                                                          clean_logits=ori_cla, **kw)
+            else:
+                with torch.no_grad():
+                    ori, _, _ = ops.u2d_fwd(images, idx_all[v:v + 1], zero_plane, True, False, False)
+                _, iter_k, _, _, r_final = DF.deepfool_2d((table, ori), epsilon, net, **kw)
+                classes = None
+            attacked += 1
+            iters += iter_k
+            visits.append((v, False, iter_k, classes))
+            if iter_k < df_max_iter:                                      # UA:315-319
+                say('iter_k < df_max_iter')
+                ops.uap2d_accumulate(table, _lib.f32c(r_final), epsilon)
+                not_changed = False
+                completed += 1
+        if not_changed:                                                   # UA:335-338
+            epoch = epochs - 1
+        else:
+            epoch += 1
+        row = stats.row.cpu().tolist()                                    # THE host read of the pass
+        n_views = len(items)                                              # len(now_dataloader.dataset), UA:340-344
+        test_correct, attack_correct = int(row[4]), int(row[5])
+        nan = float('nan')
+        test_loss, test_acc = ((row[0] + row[1]) / n_views, test_correct / n_views) if n_views else (nan, nan)
+        attack_loss, attack_acc = ((row[2] + row[3]) / n_views, attack_correct / n_views) if n_views else (nan, nan)
+        say('{} Loss: {:.4f} Acc: {:.4f}'.format('test', test_loss, test_acc))
+        say('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', attack_loss, attack_acc))
+        take = attack_acc > best_acc if targeted else attack_acc < best_acc   # UA:349-358: strict
+        if take:
+            best_acc = attack_acc
+            best = table.clone().detach()
+        records.append(dict(epoch=pass_epoch, next_epoch=epoch, views=n_views, test_loss=test_loss, test_acc=test_acc,
+                            attack_loss=attack_loss, attack_acc=attack_acc, test_correct=test_correct, attack_correct=attack_correct,
+                            skipped=skipped, attacked=attacked, completed=completed, deepfool_iters=iters, taken=int(bool(take)),
+                            visits=visits))
+        _uap2d_pass_done(n_pass, table)
+        n_pass += 1
+    return Uap2dResult(best, table, best_acc, records)

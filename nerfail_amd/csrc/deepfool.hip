@@ -8,6 +8,7 @@
 // maximum, break test, |f'| of every competitor) and deepfool_choose_kernel (the norm finish, then the choice of the class and the
 // scale on one lane), so that nerfail_deepfool_step is norms + choose + apply with no host in between.
 #include "common.h"
+#include "deepfool_choose.h"
 
 namespace nerfail {
 
@@ -48,21 +49,6 @@ __global__ __launch_bounds__(kNormBlock) void deepfool_norms_kernel(const float4
         for (int w = 0; w < kNormBlock / 64; ++w) v += red[threadIdx.x][w];
         partial[(long)blockIdx.x * (C - 1) + threadIdx.x] = v;
     }
-}
-
-// One block of 256 adds the per-workgroup partials of class k in a fixed order: every caller gets the same bits.
-__device__ __forceinline__ double norms_finish_sum(const double* __restrict__ partial, long nblocks, int K, int k, double* red) {
-    double v = 0.;
-    for (long b = threadIdx.x; b < nblocks; b += 256) v += partial[b * K + k];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 
 __global__ __launch_bounds__(256) void deepfool_norms_finish_kernel(const double* __restrict__ partial, long nblocks, int K,
@@ -110,44 +96,15 @@ __global__ __launch_bounds__(64) void deepfool_gate_kernel(const float* __restri
 }
 
 // The finish of the norm reduction (same tree, same bits as deepfool_norms_finish_kernel), then deepfool.py:81-96 on lane 0 in
-// float32 and in the mirror's operation order: which competitor, and by how much. tail = {norms2[8], best, scale}.
+// float32 and in the mirror's operation order: which competitor, and by how much (deepfool_choose.h: nerfail_uap2d_step chooses
+// with the same function). tail = {norms2[8], best, scale}.
 __global__ __launch_bounds__(256) void deepfool_choose_kernel(const double* __restrict__ partial, long nblocks, int K,
                                                               const nerfail_deepfool_record* __restrict__ rec, float* __restrict__ norms2,
                                                               int* __restrict__ best_out, float* __restrict__ scale_out,
                                                               int* __restrict__ trace_slot) {
     __shared__ double red[256];
     __shared__ float n2[NERFAIL_DEEPFOOL_MAX_COMPETITORS];
-    for (int k = 0; k < K; ++k) {
-        const double r = norms_finish_sum(partial, nblocks, K, k, red);
-        if (threadIdx.x == 0) n2[k] = norms2[k] = (float)r;
-    }
-    if (threadIdx.x != 0) return;
-    int best = 1, cls = -1;
-    float scale = 0.f;                                                             // 0 = nothing chosen: apply leaves rot alone
-    if (rec->n_comp == K) {                                                        // a record of another shape moves nothing
-        if (rec->targeted) {                                                       // :92-96: competitor 0, no comparison
-            const float nrm = sqrt_rn(n2[0]);
-            scale = rec->fabs[0] / __fadd_rn(__fmul_rn(nrm, nrm), 1e-4f);
-            cls = rec->cls[0];
-        } else {
-            float minv = INFINITY;
-            int bi = -1;
-            for (int r = 0; r < K; ++r) {
-                float vr = rec->fabs[r] / __fadd_rn(sqrt_rn(n2[r]), 1e-4f);        // :82
-                if (vr != vr) vr = INFINITY;
-                if (vr < minv) { minv = vr; bi = r; }                              // :84's strict <: the first minimum
-            }
-            if (bi >= 0) {
-                const float nrm = sqrt_rn(n2[bi]);
-                scale = rec->fabs[bi] / __fadd_rn(__fmul_rn(nrm, nrm), 1e-4f);     // :85: the norm squared again, not norms2
-                best = bi + 1;
-                cls = rec->cls[bi];
-            }
-        }
-    }
-    best_out[0] = best;
-    scale_out[0] = scale;
-    trace_slot[0] = cls;
+    deepfool_choose_body(partial, nblocks, K, rec, norms2, best_out, scale_out, trace_slot, red, n2);
 }
 
 __global__ __launch_bounds__(256) void deepfool_apply_kernel(const float4* __restrict__ G, long n, int C, const int* __restrict__ best,

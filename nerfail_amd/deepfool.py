@@ -14,6 +14,10 @@ competing class is then chosen on the device (first minimum, NaN never chosen: d
 `deepfool_native` is the same loop in product shape for this package's gauss_net: the break test and the margins in one launch
 (nerfail_deepfool_gate), one 8-byte host read per iteration, norms + choice + update in one call (nerfail_deepfool_step), every
 buffer allocated once per call, and the class chosen in every iteration reported. `deepfool` stays exactly as it is.
+
+`deepfool(universal_2d=True)` keeps raising NotImplementedError (tests/test_hip_errors.py pins it): the 2-D baseline's DeepFool
+(attack_UAP_2D.py:306-312) is `deepfool_2d`, the same loop on the ONE image-plane table through universal_2D_net without the
+alpha restore, and `deepfool_2d_native`, its product shape around nerfail_uap2d_step (csrc/uap2d.hip).
 """
 import torch
 
@@ -192,3 +196,185 @@ def deepfool_native(net_input, e, net, num_classes=8, max_iter=20, target_label:
     spatial_rgb = out if loop_i > 0 else spatial_rgb_0.clone()
     classes = trace[:loop_i].tolist() if loop_i > 0 else []
     return (spatial_rgb - spatial_rgb_0).detach(), loop_i, ori_cla_max_index, cla_max_index, spatial_rgb.detach(), classes
+
+
+# ---------------------------------------------------------------------------------------------- the 2-D baseline's DeepFool (universal_2d)
+def deepfool_2d(net_input, e, net, num_classes=8, max_iter=20, target_label: int = None, overshoot: float = 0.02,
+                m1: float = 1, m2: float = 30):
+    """deepfool.py:10-111 with universal_2d=True (the inner loop of attack_UAP_2D.py:306-312), in stock torch through
+    GaussNet.universal_2D_net: the replacement of `deepfool(universal_2d=True)`, which keeps raising. `net_input` =
+    (table [H,W,3] - the ONE plane every view shares -, ori_img [1,H,W,3]); the same 5-tuple return (dr, loop_i,
+    ori_cla_max_index, cla_max_index, table after the last step). Any device, the CPU included; the table's dtype is kept.
+
+    The control flow is `deepfool`'s without the alpha restore (deepfool.py:104): the clamp to +-255 acts on all three channels.
+    As there, the clean class's gradient is computed once per iteration instead of once per competitor."""
+    table, ori_img = net_input
+    table = torch.as_tensor(table)
+    r_0 = table.clone().detach()
+    r = table.detach().clone().requires_grad_(True)
+    _, _, cla, _, ori_cla = net(r, ori_img)                                             # deepfool.py:31
+    cla_max_index = torch.max(cla, 1)[1]
+    ori_cla_max_index = torch.max(ori_cla, 1)[1]
+    rot = torch.zeros_like(r_0)
+    loop_i = 0
+    while loop_i < max_iter:
+        r = r.detach().clone().requires_grad_(True)
+        _, _, cla, _, ori_cla = net(r, ori_img)                                         # deepfool.py:49
+        ori_cla_max_index = torch.max(ori_cla, 1)[1]
+        o = int(ori_cla_max_index)
+        bump = torch.zeros_like(cla)                                                    # deepfool.py:53-57 (+m1), out of place
+        if target_label is None:
+            bump[:, o] = m1
+        else:
+            bump[:, :int(target_label)] = m1
+            bump[:, int(target_label) + 1:] = m1
+        cla = cla + bump
+        cla_max_index = torch.max(cla, 1)[1]
+        if (target_label is None) and int(cla_max_index) != o:
+            break
+        if (target_label is not None) and int(cla_max_index) == int(target_label):
+            break
+        ks = [k for k in range(num_classes) if k != o] if target_label is None else [int(target_label)]
+        f_prime = (cla[0, ks] - (cla[0, o] + m2)).detach()                              # deepfool.py:79
+        grad_o = _grad(cla[:, o].sum(), r)
+        grad_prime = torch.stack([_grad(cla[:, k].sum(), r) for k in ks]) - grad_o.unsqueeze(0)   # deepfool.py:80 for every k
+        nrm = torch.linalg.vector_norm(grad_prime.reshape(len(ks), -1), dim=1)
+        if target_label is None:
+            value_r = torch.abs(f_prime) / (nrm + 0.0001)                               # deepfool.py:82
+            value_r = torch.where(torch.isnan(value_r), torch.full_like(value_r, float('inf')), value_r)
+            best = torch.argmin(value_r)                                                # first minimum = strict `<` scan
+            scale = torch.abs(f_prime[best]) / ((nrm[best] ** 2) + 0.0001)              # deepfool.py:85
+            scale = torch.where(torch.isinf(value_r[best]), torch.zeros_like(scale), scale)   # nothing chosen: dr = 0
+        else:
+            best = torch.zeros((), dtype=torch.int64, device=nrm.device)
+            scale = torch.abs(f_prime[0]) / ((nrm[0] ** 2) + 0.0001)                    # deepfool.py:92-96
+        rot = (rot + scale * grad_prime[best]).detach()
+        r = torch.clamp((r_0 + (overshoot * rot)).detach(), -255, 255)                  # deepfool.py:100-101, all three channels
+        loop_i += 1
+    r = r.detach()
+    return (r - r_0).detach(), loop_i, ori_cla_max_index, cla_max_index, r
+
+
+def _native_2d_applies(net, num_classes):
+    from .GaussNet import universal_2D_net
+    return (isinstance(net, universal_2D_net) and 2 <= int(num_classes) <= _lib.DEEPFOOL_MAX_COMPETITORS and torch.cuda.is_available())
+
+
+def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_label: int = None, overshoot: float = 0.02,
+                       m1: float = 1, m2: float = 30, images=None, view=None, clean_logits=None):
+    """deepfool_2d(...) in product shape: per iteration ops.u2d_fwd on the shared plane (the classifier's planar input and the
+    clip's pass mask in one launch), the classifier on the attacked image only, nerfail_deepfool_gate, ONE host read of the
+    record's first two words, the class gradients with respect to the classifier input, and nerfail_uap2d_step (norms through
+    the pass mask, the choice, rot, the +-255 clamp: three launches). The clean logits do not change during a call: the clean
+    argmax `o` is read once.
+
+    Same arguments as deepfool_2d plus `images` / `view`: a resident uint8 store [N,H,W,4|3] and the view's index in it (`view` may
+    be left out for a one-view store; an index outside the store is a ValueError) (else
+    ori_img, which then must hold whole numbers in 0..255, is taken as a one-view store), and `clean_logits` [1,C] of that view
+    (else the classifier runs once on the clean image). Class gradients: with this package's MyCNN under model_name "my_model",
+    ops.cnn_fwd with its pool masks and ONE ops.cnn_bwd_data_multi over the one-hot rows [o] + ks; with any other classifier
+    one autograd.grad per row with respect to the classifier input, stacked. Record, scratch, rot, the one-hot rows and the
+    trace array are allocated once per call.
+
+    Returns SIX values: deepfool_2d's five and the list of the class chosen in each of the loop_i iterations (-1 where nothing
+    could be chosen). What the native path does not cover - a net that is not universal_2D_net, classes outside 2..8, a
+    classifier row that is not num_classes wide, a batch of more than one view, no GPU - falls through to deepfool_2d and
+    returns None as the sixth value."""
+    from . import ops
+    from .GaussNet import u2d_resize
+    from .MyModel import MyCNN
+    table, ori_img = net_input
+    if images is not None:
+        if view is None:
+            if images.shape[0] != 1:
+                raise ValueError('deepfool_2d_native: `images` holds %d views: `view` must name one' % images.shape[0])
+            view = 0
+        if not 0 <= int(view) < images.shape[0]:
+            raise ValueError('deepfool_2d_native: view %d is outside the store (0..%d)' % (int(view), images.shape[0] - 1))
+    elif ori_img is None:
+        raise ValueError('deepfool_2d_native: net_input holds no image and no store was given')
+
+    def mirror():
+        ori = ori_img
+        if ori is None:                                                                 # a resident view: the mirror takes a tensor
+            with torch.no_grad():
+                r = torch.as_tensor(table).to(images.device)
+                ori, _, _ = ops.u2d_fwd(images, torch.full((1,), int(view), dtype=torch.int64, device=images.device),
+                                        torch.zeros_like(r, dtype=torch.float32), True, False, False)
+        return deepfool_2d((table, ori), e, net, num_classes, max_iter, target_label, overshoot, m1, m2) + (None,)
+    if not _native_2d_applies(net, num_classes):
+        return mirror()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    if images is None:
+        ori = torch.as_tensor(ori_img).to(dev)
+        store = ori.to(torch.uint8).contiguous()
+        if ori.dim() != 4 or ori.shape[0] != 1 or ori.shape[-1] != 3 or not bool((store == ori).all()):
+            return mirror()
+        view = 0
+    else:
+        store = images
+    C = int(num_classes)
+    target = -1 if target_label is None else int(target_label)
+    if not -1 <= target < C:
+        return mirror()
+    model, name = net.model, net.model_name
+    cnn = isinstance(model, MyCNN) and name == "my_model"
+    r_0 = _lib.f32c(torch.as_tensor(table), dev).clone()
+    hw = tuple(r_0.shape[:-1])
+    P = r_0.numel() // 3
+    idx = torch.full((1,), int(view), dtype=torch.int64, device=dev)
+    if clean_logits is None:
+        with torch.no_grad():
+            _, clean_in, _ = ops.u2d_fwd(store, idx, torch.zeros_like(r_0), False, True, False)
+            clean_logits = model(u2d_resize(clean_in, name))
+    if clean_logits.dim() != 2 or clean_logits.shape[0] != 1 or clean_logits.shape[1] != C:
+        return mirror()
+    ori_cla_max_index = torch.max(clean_logits, 1)[1]
+    o = int(ori_cla_max_index)                                                          # THE read of the call
+    ks = [k for k in range(C) if k != o] if target < 0 else [target]
+    rows = [o] + ks
+    n_rhs = len(rows)
+    lib = _lib.load()
+    scratch, _ = ops.uap2d_step_scratch(n_rhs, P, dev)
+    record = torch.zeros((_lib.DEEPFOOL_RECORD_WORDS,), dtype=torch.int32, device=dev)
+    trace = torch.full((max(int(max_iter), 1),), -1, dtype=torch.int32, device=dev)
+    rot = torch.zeros_like(r_0)
+    out = torch.empty_like(r_0)
+    onehot = torch.zeros((n_rhs, 1, C), dtype=torch.float32, device=dev)
+    onehot[torch.arange(n_rhs, device=dev), 0, torch.tensor(rows, device=dev)] = 1.
+    cur, arg, cla = r_0, None, None
+    loop_i = 0
+    while loop_i < max_iter:
+        with torch.no_grad():
+            _, cls_in, mask = ops.u2d_fwd(store, idx, cur, False, True, True)           # deepfool.py:49 up to the classifier
+        if cnn:
+            with torch.no_grad():
+                cla, ws, pool = ops.cnn_fwd(model.packed(), cls_in, C, True)
+        else:
+            cls_in.requires_grad_()
+            cla = model(u2d_resize(cls_in, name))
+            if cla.dim() != 2 or cla.shape[0] != 1 or cla.shape[1] != C:
+                return mirror()
+        cla_c = _lib.f32c(cla)
+        _lib.check(lib.nerfail_deepfool_gate(_lib.dev(cla_c), C, o, target, float(m1), float(m2), _lib.dev(record), _lib.stream()))
+        done, arg = record[:2].tolist()                                                 # the iteration's one host read
+        if done:
+            break
+        if cnn:
+            with torch.no_grad():
+                G = ops.cnn_bwd_data_multi(model.packed(), ws, pool, onehot, hw[0], hw[1])
+        else:
+            G = _lib.f32c(torch.stack([torch.autograd.grad(cla[0, k], cls_in, retain_graph=True)[0] for k in rows]))
+        ops.uap2d_step(G, mask.view(-1), record, scratch, overshoot, r_0, rot, out, trace[loop_i:loop_i + 1])
+        cur = out
+        loop_i += 1
+    if arg is None:                                                                     # max_iter < 1: deepfool.py:31's forward alone
+        with torch.no_grad():
+            _, cls_in, _ = ops.u2d_fwd(store, idx, cur, False, True, False)
+            cla = model(u2d_resize(cls_in, name))
+        cla_max_index = torch.max(cla, 1)[1]
+    else:
+        cla_max_index = torch.full((1,), arg, dtype=torch.int64, device=dev)
+    r = out if loop_i > 0 else r_0.clone()
+    classes = trace[:loop_i].tolist() if loop_i > 0 else []
+    return (r - r_0).detach(), loop_i, ori_cla_max_index, cla_max_index, r.detach(), classes

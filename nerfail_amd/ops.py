@@ -989,3 +989,44 @@ def u2d_epoch_close(row, best, epoch, targeted, record, flag):
 
 
 U2D_OPS = ('u2d_fwd', 'u2d_step')
+
+
+# ----------------------------------------------------------------------------------------------- 2-D universal baseline (attack_UAP_2D.py:241-358; uap2d revision 1)
+def uap2d_step_scratch(n_rhs, P, device):
+    """(scratch as float64, its size in bytes) of uap2d_step: the partials, then {norms2[8], best, scale}."""
+    nb = _lib.load().nerfail_uap2d_step_scratch_bytes(int(n_rhs), int(P))
+    if nb == 0:
+        raise ValueError('uap2d_step: n_rhs must be in 2..8 and P in 1..2^31 (got %d, %d)' % (n_rhs, P))
+    return torch.empty((nb // 8,), dtype=torch.float64, device=device), nb
+
+
+def uap2d_step(grads, pass_mask, record, scratch, overshoot, r0, rot, r_out, trace_slot):
+    """DF:68-102 with universal_2d in one call (nerfail_uap2d_step): grads float32 [n_rhs,...] holding n_rhs x 3 x P planar
+    class gradients of ONE view, row 0 the clean class; pass_mask uint8 [P] of that view's u2d_fwd; record: the gate's;
+    r0 / rot / r_out float32 [P,3] interleaved (views into larger buffers allowed, as long as each is dense); trace_slot: one
+    int32. rot is updated in place, r_out written."""
+    P = pass_mask.numel()
+    n_rhs = grads.shape[0]
+    for t, name in ((grads, 'grads'), (r0, 'r0'), (rot, 'rot'), (r_out, 'r_out')):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('uap2d_step: %s must be contiguous float32' % name)
+    if grads.numel() != n_rhs * 3 * P or r0.numel() != 3 * P or rot.numel() != 3 * P or r_out.numel() != 3 * P:
+        raise ValueError('uap2d_step: grads must hold n_rhs x 3 x P floats and r0, rot, r_out 3 P each (P = %d)' % P)
+    if pass_mask.dtype != torch.uint8 or not pass_mask.is_contiguous():
+        raise ValueError('uap2d_step: pass_mask must be contiguous uint8 [P]')
+    if record.dtype != torch.int32 or record.numel() != _lib.DEEPFOOL_RECORD_WORDS or trace_slot.dtype != torch.int32 or trace_slot.numel() != 1:
+        raise ValueError('uap2d_step: record must be int32 [%d] and trace_slot int32 [1]' % _lib.DEEPFOOL_RECORD_WORDS)
+    nb = scratch.numel() * scratch.element_size()
+    _chk(_lib.load().nerfail_uap2d_step(_lib.dev(grads, 'grads'), n_rhs, P, _lib.dev(pass_mask, 'pass_mask'), _lib.dev(record, 'record'),
+                                        _lib.c_p(scratch.data_ptr()), nb, float(overshoot), _lib.dev(r0, 'r0'), _lib.dev(rot, 'rot'),
+                                        _lib.dev(r_out, 'r_out'), _lib.dev(trace_slot, 'trace_slot'), _s()))
+
+
+def uap2d_accumulate(table, r_final, epsilon):
+    """UA:317-319 with DF:109 in place: table <- clamp(table + (r_final - table), -epsilon, +epsilon) (nerfail_uap2d_accumulate)."""
+    for t, name in ((table, 'table'), (r_final, 'r_final')):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('uap2d_accumulate: %s must be contiguous float32' % name)
+    if table.numel() != r_final.numel():
+        raise ValueError('uap2d_accumulate: table and r_final differ in size')
+    _chk(_lib.load().nerfail_uap2d_accumulate(_lib.dev(table, 'table'), _lib.dev(r_final, 'r_final'), float(epsilon), table.numel(), _s()))
