@@ -891,6 +891,36 @@ int nerfail_uap2d_step(const float* grads, int n_rhs, int64_t P, const unsigned 
  * epsilon >= 0 (not NaN), 1 <= n <= 3 * 2^31, both pointers 4-byte aligned, else NERFAIL_EINVAL. */
 int nerfail_uap2d_accumulate(float* table, const float* r_final, float epsilon, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------ poisoned retrain hand-off (poison revision 1) -- */
+
+/* The hand-off from an attack's export epoch to the NeRF that is retrained on the attacked views (README "retrain";
+ * load_blender.py = LB, run_nerf.py = RN), without the disk: the reference writes PNGs (AS:401-402), decodes them (LB:62-65) and
+ * composites them on white (RN:587-588); here one pass over the float export fills a resident uint8 store and a resident float32
+ * target store. Like the seven sections before it this one only ADDS entry points: NERFAIL_ABI_VERSION stays 14,
+ * nerfail_abi_revision() stays 15, the eval, cls, deepfool, scene, u2d and uap2d revisions stay 1, and the additions are announced
+ * by nerfail_poison_revision() = 1. nerfail_export_u8 is unchanged and rounds with the same device function. No allocation, no
+ * synchronisation, no atomics, plain vector stores; the same bits on every run. */
+int nerfail_poison_revision(void);
+
+/* x: the export of B views, float32 [B,P,4] in BGRA order (x_rgba of NeRFail-S / NeRFail; 16-byte aligned) or [B,P,3] in BGR order
+ * (x_rgb of IGSM-2D / UAP-2D; 4-byte aligned), `channels` saying which. slots_host: a HOST array of B slot numbers, each in
+ * 0..n_slots-1, distinct within the call; view b goes to slot slots_host[b] of both stores:
+ *   adv_u8  uint8 [n_slots,P,channels]  q = rintf(min(max(v, 0), 255)) per element (NaN -> 0), channel order as given: bit for bit
+ *                                       what nerfail_export_u8 writes for the view, i.e. what cv2.imread(..., IMREAD_UNCHANGED)
+ *                                       returns for the PNG cv2.imwrite makes of it.
+ *   target  float32 [n_slots,P,3]       in RGB order, bit for bit what the file path makes of that uint8 image: every byte becomes
+ *                                       u = (float)((double)q / 255.0) (LB:65: a float64 divide, then the cast); a 4-channel pixel is
+ *                                       composited on white as fadd_rn(fmul_rn(u_c, u_a), fsub_rn(1.f, u_a)) (RN:588: three float32
+ *                                       roundings, no fused multiply-add); a 3-channel pixel is taken as it is (RN:587).
+ * Slots that no view of the call names are neither read nor written. A lane owns four consecutive pixels (16-byte loads and
+ * stores) where a view's place in the stores allows it - both store bases 16-byte aligned and slot * P a multiple of 4 (for 3
+ * channels also x 16-byte aligned and b * P a multiple of 4) - with a scalar tail; any other view is written pixel by pixel.
+ * At most 16 views travel per launch, the function loops. Refused with NERFAIL_EINVAL before any launch: channels other than 3 or
+ * 4, B outside 0..65535, P outside 1..2^31, n_slots < 1, a NULL pointer, a slot outside 0..n_slots-1, a slot named twice, x not
+ * aligned as above, adv_u8 or target not 4-byte aligned. B == 0 is a no-op. */
+int nerfail_export_train_views(const float* x, int channels, int B, int64_t P, const int32_t* slots_host, int64_t n_slots,
+                               unsigned char* adv_u8, float* target, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

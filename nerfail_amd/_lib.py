@@ -19,7 +19,8 @@ DEEPFOOL_REVISION = 1                    # nerfail_deepfool_revision: the DeepFo
 SCENE_REVISION = 1                       # nerfail_scene_revision: the 8-NN search with the Gaussian weights as its epilogue (scene)
 U2D_REVISION = 1                         # nerfail_u2d_revision: the IGSM-2D baseline's forward, step and statistics (attack.igsm_2d)
 UAP2D_REVISION = 1                       # nerfail_uap2d_revision: the UAP-2D baseline's DeepFool step and projection (attack.uap_2d)
-UAP2D_NORM_TERMS = 24                    # NERFAIL_UAP2D_NORM_TERMS: float32 terms per lane of nerfail_uap2d_step's norms
+POISON_REVISION = 1                      # nerfail_poison_revision: the export -> training-target hand-off (retrain.PoisonedTrainSet)
+UAP2D_NORM_TERMS = 24                   # NERFAIL_UAP2D_NORM_TERMS: float32 terms per lane of nerfail_uap2d_step's norms
 DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
 DEEPFOOL_RECORD_WORDS = 4 + 2 * DEEPFOOL_MAX_COMPETITORS    # struct nerfail_deepfool_record as 32-bit words
 EVAL_U8C4, EVAL_U8C3, EVAL_F32C4, EVAL_FLAT = 0, 1, 2, 3    # NERFAIL_EVAL_*: image formats of nerfail_eval_view_metrics
@@ -198,6 +199,8 @@ SIGNATURES = {
     'nerfail_uap2d_step_scratch_bytes': (ctypes.c_size_t, [c_i, c_i64]),
     'nerfail_uap2d_step': (c_i, [c_p, c_i, c_i64, c_p, c_p, c_p, ctypes.c_size_t, c_f, c_p, c_p, c_p, c_p, c_p]),
     'nerfail_uap2d_accumulate': (c_i, [c_p, c_p, c_f, c_i64, c_p]),
+    'nerfail_poison_revision': (c_i, []),
+    'nerfail_export_train_views': (c_i, [c_p, c_i, c_i, c_i64, c_p, c_i64, c_p, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -268,6 +271,9 @@ def load():
     if lib.nerfail_uap2d_revision() != UAP2D_REVISION:
         raise RuntimeError('nerfail_amd: 2-D universal baseline revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_uap2d_revision(), UAP2D_REVISION))
+    if lib.nerfail_poison_revision() != POISON_REVISION:
+        raise RuntimeError('nerfail_amd: poisoned-retrain revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_poison_revision(), POISON_REVISION))
     _lib = lib
     return lib
 

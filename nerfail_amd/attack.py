@@ -288,14 +288,17 @@ class _ExportBuffers:
         return self.bufs[shape]
 
 
-def _export_batch(net, best, batch, index, stats, epoch, group, bufs, on_export):
+def _export_batch(net, best, batch, index, stats, epoch, group, bufs, on_export, export_sink=None):
     """AS:310-317, 394-403 for one batch (this rank's views of it): the best tensor through the forward without gradient, the
-    same statistics, then x_rgba and the unclipped mask image x as uint8 to the host in ONE copy."""
+    same statistics, then x_rgba and the unclipped mask image x as uint8 to the host in ONE copy. `export_sink` takes x_rgba on
+    the device first (retrain.PoisonedTrainSet); without on_export nothing is copied to the host."""
     parts = _share(batch, group)[0]
     if parts is None:
         return
     x, x_rgba, cla, ori_cla, views = net.export_forward(best, *parts)
     stats.batch(epoch, cla, ori_cla, x_rgba, views)
+    if export_sink is not None:
+        export_sink.put(parts[2], x_rgba)
     if on_export is None:
         return
     d_u8, h_u8, ev = bufs.get(tuple(x_rgba.shape), x_rgba.device)         # (free again: every call waits for its own copy below)
@@ -338,7 +341,23 @@ def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=
     accumulates the statistics of the views it owns, ONE extra all-reduce per epoch sums the stats row before the close, so
     every rank takes the same decisions and ends with the same `best`. on_export is called on every rank for its own views.
 
+    nerfail_s_into(export_sink, ...) is this call with a device-side sink behind the export epoch.
+
     Returns an AttackResult (best, last, stats, best_epoch, best_acc)."""
+    return _nerfail_s(None, net, spatial, batches, label, epochs, a, epsilon, targeted, beta, export_batches, on_export, log, group)
+
+
+def nerfail_s_into(export_sink, net, spatial, batches, label, epochs, *args, **kwargs):
+    """nerfail_s(net, spatial, batches, label, epochs, ...) with an export sink: an object with put(view_ids, x_rgba) -
+    retrain.PoisonedTrainSet - that receives every export batch's x_rgba [B,H,W,4] as a device tensor, before and independently
+    of on_export (the export batches then need view ids). With on_export None no image is copied to the host. A function of
+    its own because nerfail_s's parameter list is pinned as it is; nerfail, igsm_2d and uap_2d take `export_sink=` directly."""
+    return _nerfail_s(export_sink, net, spatial, batches, label, epochs, *args, **kwargs)
+
+
+def _nerfail_s(export_sink, net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=False, beta=0., export_batches=None,
+               on_export=None, log=print, group=None):
+    """The body of nerfail_s (its defaults repeated for nerfail_s_into's pass-through)."""
     if not (getattr(net, 'deterministic', True) and getattr(net, 'rgb_grad_only', True)):
         raise ValueError('nerfail_s runs the deterministic rgb-gradient step path (net.deterministic and net.rgb_grad_only)')
     epochs = int(epochs)
@@ -382,7 +401,7 @@ def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=
     epoch = epochs - 1
     exp = export_batches if export_batches is not None else batches
     for i, batch in enumerate(exp(epoch) if callable(exp) else exp):
-        _export_batch(net, best, batch, i, stats, epoch, group, bufs, on_export)
+        _export_batch(net, best, batch, i, stats, epoch, group, bufs, on_export, export_sink)
     stats.close(epoch, group)                                         # (its decision moves no tensor: the epoch ran on `best` itself)
     finish(epoch)
     last_attack = records[-2] if epochs > 1 else None
@@ -434,7 +453,8 @@ def _same_class(cla, ori_cla):
 
 
 def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df_max_iter=1000, overshoot=0.02, num_classes=8,
-            m2_max_limit=10000, accumulate_incomplete=False, export_views=None, on_export=None, log=print, native=None):
+            m2_max_limit=10000, accumulate_incomplete=False, export_views=None, on_export=None, log=print, native=None,
+            export_sink=None):
     """The NeRFail universal attack, attack_NeRFail.py:269-512 (= AN), as one call: the counterpart of nerfail_s.
 
     `spatial`: the perturbation table [P,H,W,4]. `views`: a list of batch-1 items `(weight_and_index, ori_img[, view_id])`, or a
@@ -457,7 +477,7 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
     record and the log lines. `native=None` runs deepfool.deepfool_native (which itself falls through to the mirror where it
     does not apply), `native=False` the mirror deepfool.deepfool (a resident view given by name alone is handed to it as the tensors
     the visit's forward resolved). An export epoch without views is a ValueError. The update is sequential over the views: there is nothing to
-    shard, and more than one rank is a ValueError.
+    shard, and more than one rank is a ValueError. `export_sink`: as for nerfail_s - put([view_id], x_rgba) per exported view.
 
     Returns a NerfailResult. Every dict of `stats` holds m1 / m2 (at the end of the pass), m1_pass (the m1 the pass ran with),
     epoch, next_epoch, test_loss, test_acc, attack_loss, attack_acc, views, skipped, attacked, completed, deepfool_iters,
@@ -510,7 +530,7 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
                     say('best m2=' + str(m2_best))
                     say('best acc=' + str(best_acc))
                 net.open_update_epsilon_3d()
-                _export_batch(net, table, (wi, ori, vids), i, stats, epoch, None, bufs, on_export)
+                _export_batch(net, table, (wi, ori, vids), i, stats, epoch, None, bufs, on_export, export_sink)
                 not_changed = False                                       # AN:432
                 continue
             net.open_update_epsilon_3d()
@@ -621,7 +641,7 @@ def _frozen(model):
 
 
 def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targeted=False, batch_size=4, on_export=None, log=print,
-            native=None):
+            native=None, export_sink=None):
     """The IGSM-2D baseline, attack_IGSM_2D.py:263-416 (= IG), as one call: the 2-D counterpart of nerfail_s.
 
     `model`, `model_name`: the victim classifier and the name that selects the resize in front of it (GaussNet.u2d_resize:
@@ -641,7 +661,9 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
     Epoch epochs-1 is the export epoch (IG:286-301, 381-390): the BEST table, no gradient, the same statistics, and
     `on_export(batch_index, view_indices, adv_u8, mask_u8)` per batch with host uint8 arrays [B,H,W,3] of the attacked image
     and of the perturbation (negative values become 0, as cv2.imwrite saturates), converted by nerfail_export_u8. With
-    epochs == 1 the zero table is exported.
+    epochs == 1 the zero table is exported. `export_sink`: an object with put(view_indices, x_rgb) - retrain.PoisonedTrainSet -
+    that receives every export batch's attacked image [B,H,W,3] as a device tensor, before and independently of on_export; with
+    on_export None no image is copied to the host. None (the default) leaves the loop as it is.
 
     The classifier. `native=None` (automatic) or True (insist): when `model` is this package's MyCNN and model_name is
     "my_model", a step is ops.cnn_fwd with its pool masks, ops.cls_ce with a constant label vector for d loss / d logits,
@@ -754,6 +776,8 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
             x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[lo:hi], best, True, True, False)
             cla = classify(cls_in)
             batch_stats(epoch, lo, hi, cla, x_rgb)
+        if export_sink is not None:
+            export_sink.put(list(range(lo, hi)), x_rgb)
         if on_export is None:
             continue
         pert = best[lo:hi]
@@ -792,7 +816,7 @@ def _uap2d_pass_done(index, table):
 
 
 def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, targeted=False, df_max_iter=1000, overshoot=0.02,
-           num_classes=8, attack_views=None, export_views=None, on_export=None, log=print, native=None):
+           num_classes=8, attack_views=None, export_views=None, on_export=None, log=print, native=None, export_sink=None):
     """The UAP-2D baseline, attack_UAP_2D.py:241-358 (= UA), as one call: the 2-D counterpart of nerfail.
 
     `model`, `model_name`, `images`, `label`: as for igsm_2d (the resident uint8 store [N,H,W,4|3]; the resize rule of
@@ -812,7 +836,8 @@ def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, 
     [H,W,3] of the perturbation (negative values become 0, as cv2.imwrite saturates) and [1,H,W,3] of the clean image on its
     white background, converted by nerfail_export_u8. Every pass, the export pass included, ends with its means (sums / views of
     the pass) and the STRICT best rule of UA:349-358 (> targeted, < untargeted, from 0 / 10000). With epochs == 1 the zero table
-    is exported.
+    is exported. `export_sink`: as for igsm_2d - put([view_index], x_rgb [1,H,W,3]) per exported view, on the device, before and
+    independently of on_export.
 
     The classifier. As UA:244-250 does, a `model` that is an nn.Module is put in eval() mode and its parameters stop requiring
     grad; the clean images' logits then never change and are computed once per view for the run (else at every visit).
@@ -922,11 +947,14 @@ def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, 
             if export and i == 0:
                 table = best                                              # UA:269: the table IS the best tensor from here on
             with torch.no_grad():
-                x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[v:v + 1], table, export and on_export is not None, True, False)
+                want_x = export and (on_export is not None or export_sink is not None)
+                x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[v:v + 1], table, want_x, True, False)
                 cla = _lib.f32c(classify(cls_in))
             ori_cla = clean_logits(v)
             stats.batch(epoch, cla, ori_cla)                              # UA:275-289
             if export:
+                if export_sink is not None:
+                    export_sink.put([v], x_rgb)
                 if on_export is not None:
                     export_view(i, v, x_rgb)
                 not_changed = False                                       # UA:333

@@ -142,9 +142,7 @@ __global__ __launch_bounds__(256) void copy_if_kernel(const int* __restrict__ fl
     for (long i = done + t; i < n; i += stride) dst[i] = src[i];
 }
 
-// ---- AS:401-402: what cv2.imwrite makes of a float image. fmaxf(NaN, 0) = 0.
-__device__ __forceinline__ unsigned to_u8(float v) { return (unsigned)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
-
+// ---- AS:401-402: what cv2.imwrite makes of a float image (to_u8, common.h).
 __global__ __launch_bounds__(256) void export_u8_kernel(const float* __restrict__ src, long n, unsigned char* __restrict__ dst) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
     const long n4 = n >> 2;

@@ -192,6 +192,10 @@ __device__ __forceinline__ void pair_put(float* p, double v) {
 // One colour byte of a BGRA dword on the white background of MT:237-254 / MD:98-105: the byte where alpha > 0, else 255.
 __device__ __forceinline__ float white_u8(unsigned w, int shift) { return (w >> 24) > 0u ? (float)((w >> shift) & 255u) : 255.f; }
 
+// What cv2.imwrite makes of one float of an image (AS:401-402): clamp to [0, 255], round half to even; fmaxf(NaN, 0) = 0.
+// Shared by nerfail_export_u8 and nerfail_export_train_views: one definition of the rounding.
+__device__ __forceinline__ unsigned to_u8(float v) { return (unsigned)rintf(fminf(fmaxf(v, 0.f), 255.f)); }
+
 // Row of a table with last + 1 rows that a float32 index names (indices travel as float32, GN:62 / CI:148): .type(torch.long)
 // truncates, and every user of the pixel <-> 3-D-point map (K10's gather, K11's scatter, the inverted index) must resolve the
 // same float to the same row. The value is clamped to [0, last] AS A FLOAT first (v_med3_f32; NaN -> 0), so the conversion

@@ -1030,3 +1030,36 @@ def uap2d_accumulate(table, r_final, epsilon):
     if table.numel() != r_final.numel():
         raise ValueError('uap2d_accumulate: table and r_final differ in size')
     _chk(_lib.load().nerfail_uap2d_accumulate(_lib.dev(table, 'table'), _lib.dev(r_final, 'r_final'), float(epsilon), table.numel(), _s()))
+
+
+# ----------------------------------------------------------------------------------------------- poisoned retrain hand-off (LB:62-65, RN:587-588; poison revision 1)
+@custom_op(NS + '::export_train_views', mutates_args=('adv_u8', 'target'), device_types='cuda')
+def export_train_views(x: Tensor, slots: Sequence[int], adv_u8: Tensor, target: Tensor) -> None:
+    """The export of B views, x float32 [B,...,4] (BGRA) or [B,...,3] (BGR), into slots `slots` (host ints, distinct) of two
+    resident stores: adv_u8 uint8 [n,...,C], bit for bit export_u8(x[b]), and target float32 [n,...,3] in RGB order, bit for bit
+    what load_blender_data(train_dir=...) and training_images(white_bkgd=True) make of that uint8 image."""
+    if x.dtype != torch.float32 or x.dim() < 3 or x.shape[-1] not in (3, 4) or not x.is_contiguous():
+        raise ValueError('export_train_views: x must be contiguous float32 [B,...,4] (BGRA) or [B,...,3] (BGR)')
+    B, C = x.shape[0], x.shape[-1]
+    P = x[0].numel() // C if B else 0
+    n = adv_u8.shape[0] if adv_u8.dim() else 0
+    if adv_u8.dtype != torch.uint8 or not adv_u8.is_contiguous() or adv_u8.numel() != n * P * C:
+        raise ValueError('export_train_views: adv_u8 must be a contiguous uint8 store [n,...,%d] of views of %d pixels' % (C, P))
+    if target.dtype != torch.float32 or not target.is_contiguous() or target.numel() != n * P * 3 or target.shape[0] != n:
+        raise ValueError('export_train_views: target must be a contiguous float32 store [n,...,3] with adv_u8\'s n')
+    if len(slots) != B:
+        raise ValueError('export_train_views: one slot per view of x')
+    if B == 0:
+        return
+    if any(not 0 <= int(s) < n for s in slots):                           # (also the C side's answer; here before the int32 conversion)
+        raise ValueError('export_train_views: a slot is outside 0..%d' % (n - 1))
+    tab = (_lib.ctypes.c_int32 * B)(*[int(s) for s in slots])
+    _chk(_lib.load().nerfail_export_train_views(_lib.dev(x, 'x'), C, B, P, tab, n, _lib.dev(adv_u8, 'adv_u8'), _lib.dev(target, 'target'), _s()))
+
+
+@export_train_views.register_fake
+def _(x, slots, adv_u8, target):
+    return None
+
+
+POISON_OPS = ('export_train_views',)

@@ -45,14 +45,7 @@ class RayBatcher:
     [N,3+,4]; the views `i_train` are uploaded once (float32, as RN:748 / RN:752 convert them per step)."""
 
     def __init__(self, images, poses, i_train, hwf, K, near, far, seed=0, rng=None, device=None):
-        self.dev = _cuda() if device is None else torch.device(device)
-        self.H, self.W = int(hwf[0]), int(hwf[1])
-        self.K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
-        self.near, self.far = float(near), float(far)
-        self.i_train = [int(i) for i in i_train]
-        if not self.i_train:
-            raise ValueError('RayBatcher: i_train is empty')
-        self.slot_of = {v: s for s, v in enumerate(self.i_train)}
+        self._setup(_cuda() if device is None else torch.device(device), poses, i_train, hwf, K, near, far, seed, rng)
         n = len(self.i_train)
         self.images = torch.empty((n, self.H, self.W, 3), dtype=torch.float32, device=self.dev)
         for s, v in enumerate(self.i_train):             # one view at a time: no second host copy of the whole set
@@ -61,12 +54,38 @@ class RayBatcher:
                 raise ValueError('RayBatcher: image %d is %s, expected (%d, %d, 3) - RGBA goes through training_images() first'
                                  % (v, tuple(img.shape), self.H, self.W))
             self.images[s].copy_(img.to(torch.float32))
+
+    def _setup(self, dev, poses, i_train, hwf, K, near, far, seed, rng):
+        """Everything but the image store."""
+        self.dev = dev
+        self.H, self.W = int(hwf[0]), int(hwf[1])
+        self.K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+        self.near, self.far = float(near), float(far)
+        self.i_train = [int(i) for i in i_train]
+        if not self.i_train:
+            raise ValueError('RayBatcher: i_train is empty')
+        self.slot_of = {v: s for s, v in enumerate(self.i_train)}
+        n = len(self.i_train)
         p = _host(poses).to(torch.float32)[self.i_train, :3, :4].reshape(n, 12)
         self.poses = p.contiguous().to(self.dev)
         self.seed = int(seed) & 0xFFFFFFFF
         self.rng = np.random.RandomState(self.seed) if rng is None else rng       # draws the view of a no_batching step (RN:746)
         self.epoch, self.i_batch = 0, 0                  # use_batching: RN:707, advanced as RN:737-742
         self.n_global = 0                                # rays of the last batch over ALL ranks (the loss's denominator)
+
+    @classmethod
+    def from_resident(cls, store, poses, i_train, hwf, K, near, far, seed=0, rng=None):
+        """A batcher over a store that already lives on the device: `store` float32 [n,H,W,3], slot s holding view i_train[s]
+        (retrain.PoisonedTrainSet.images). The tensor is adopted as it is: no copy, no upload."""
+        self = cls.__new__(cls)
+        if not isinstance(store, torch.Tensor) or not store.is_cuda or store.dtype != torch.float32 or not store.is_contiguous():
+            raise ValueError('RayBatcher.from_resident: store must be a contiguous float32 tensor on the device')
+        self._setup(store.device, poses, i_train, hwf, K, near, far, seed, rng)
+        if tuple(store.shape) != (len(self.i_train), self.H, self.W, 3):
+            raise ValueError('RayBatcher.from_resident: store is %s, expected (%d, %d, %d, 3): one slot per view of i_train'
+                             % (tuple(store.shape), len(self.i_train), self.H, self.W))
+        self.images = store
+        return self
 
     def key(self, counter):
         return ops.as_op_key((self.seed << 32) | (int(counter) & 0xFFFFFFFF))
