@@ -921,6 +921,79 @@ int nerfail_poison_revision(void);
 int nerfail_export_train_views(const float* x, int channels, int B, int64_t P, const int32_t* slots_host, int64_t n_slots,
                                unsigned char* adv_u8, float* target, void* stream);
 
+/* ------------------------------------------------------------------ classifier-input resize (resize revision 1) -- */
+
+/* The stage in front of a stock victim classifier (GaussNet.py:121-157, model_test.py:283-290): white background, NHWC -> NCHW and
+ * the antialiased bilinear resize to the classifier's side (299; 224 for vit_b_16), as one kernel with an exact adjoint. Like the
+ * eight sections before it this one only ADDS entry points: NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays 15, the eval,
+ * cls, deepfool, scene, u2d, uap2d and poison revisions stay 1, and the additions are announced by nerfail_resize_revision() = 1.
+ * The arithmetic is fixed down to the order of the float32 operations (tests/resize_ref.py restates it in numpy):
+ *
+ *   axis table, n_in -> n_out, in double: scale = n_in / n_out; support = scale >= 1 ? scale : 1; inv = scale >= 1 ? 1 / scale : 1;
+ *     output i: c = scale * (i + 0.5); start = max(0, (int)(c - support + 0.5)); count = min(n_in, (int)(c + support + 0.5)) - start;
+ *     w[k] = max(0, 1 - |(k + start - c + 0.5) * inv|) for k = 0..count-1, divided by their sum (added in that order), then rounded
+ *     ONCE to float32: aten's _upsample_bilinear2d_aa with align_corners = false.
+ *   inverted table: input j is covered by the outputs ostart[j] .. ostart[j] + ocount[j] - 1 (those whose [start, start + count)
+ *     holds j): one contiguous, non-empty range.
+ *   forward, per channel, every product and every sum rounded to float32 on its own (no fused multiply-add):
+ *     t[y][ox]    = w_x[ox][0] * v[y][xs]  (+ w_x[ox][k] * v[y][xs + k], k = 1..count-1, in that order), xs = start_x[ox];
+ *     out[oy][ox] = w_y[oy][0] * t[ys][ox] (+ w_y[oy][k] * t[ys + k][ox], k = 1..count-1, in that order), ys = start_y[oy].
+ *   adjoint: tmp[y][ox] = sum over oy ascending in the inverted range of y of w_y[oy][y - ys] * g[oy][ox];
+ *            gx[y][x]   = sum over ox ascending in the inverted range of x of w_x[ox][x - xs] * tmp[y][ox];
+ *     the first product starts each sum, as in the forward.
+ * No allocation on the device, no synchronisation, no atomics, no global scratch; the same bits on every run. */
+int nerfail_resize_revision(void);
+
+#define NERFAIL_RESIZE_MAX_TAPS 16
+
+/* Pure host functions. nerfail_resize_aa_kmax: the largest count of the axis n_in -> n_out (the row length of w), or 0 when n_in or
+ * n_out < 1. nerfail_resize_aa_table fills caller-owned HOST arrays: start[n_out], count[n_out], w[n_out][kmax] (a row's floats
+ * from count on are +0), ostart[n_in], ocount[n_in]. NERFAIL_EINVAL, with nothing promised about the arrays: n_in or n_out < 1,
+ * a NULL array, kmax below the axis' largest count, any count or ocount above NERFAIL_RESIZE_MAX_TAPS (a scale above ~7.5, or
+ * below ~1/7.5), or an inverted range that would not be contiguous and non-empty. */
+int nerfail_resize_aa_kmax(int n_in, int n_out);
+int nerfail_resize_aa_table(int n_in, int n_out, int32_t* start, int32_t* count, float* w, int kmax, int32_t* ostart,
+                            int32_t* ocount);
+
+/* One axis' tables on the DEVICE, exactly what nerfail_resize_aa_table wrote (the struct itself lives on the host). */
+typedef struct nerfail_resize_axis {
+    const int32_t* start;    /* [n_out] */
+    const int32_t* count;    /* [n_out] */
+    const float* w;          /* [n_out][kmax] */
+    const int32_t* ostart;   /* [n_in] */
+    const int32_t* ocount;   /* [n_in] */
+    int32_t n_in, n_out, kmax, reserved;
+} nerfail_resize_axis;
+
+/* The tiles the two kernels take for H x W -> oh x ow: fwd_tile = {output rows, output columns} of a forward workgroup, bwd_tile =
+ * {source rows, source columns} of an adjoint workgroup. The largest of a fixed ladder (forward 16 x 32 down to 2 x 8, adjoint
+ * 16 x 64 down to 1 x 8) whose source (gradient) window, intermediate and staged weights fit 80 KiB of LDS, so two workgroups share
+ * a CU's 160 KiB. NERFAIL_EINVAL when an axis' table is refused or a pointer is NULL. */
+int nerfail_resize_tiles(int H, int W, int oh, int ow, int32_t* fwd_tile, int32_t* bwd_tile);
+
+/* Source value v: layout 0 = src float32 [B,H,W,4] (x_rgba; 16-byte aligned), v = a > 0 ? c : 255 for the first three channels c of
+ * a pixel with fourth channel a (a = 0, -0, negative, NaN: 255, as torch.where(a > 0, c, 255)); layout 1 = src float32 [B,3,H,W],
+ * taken as it is. out: float32 [B,3,oh,ow], every element written. One workgroup owns an output tile of one view, all three
+ * channels: the source window goes to LDS once (layout 0: one 16-byte load per pixel, the background rule applied on the way in),
+ * the horizontal pass runs LDS -> LDS, the vertical pass LDS -> registers, the store is coalesced along ox; weights are read from
+ * the tables. Whatever the tables hold, no global access leaves src [B,H,W,*] or out [B,3,oh,ow]; the VALUES are the definition's
+ * only for tables written by nerfail_resize_aa_table for H -> oh (ty) and W -> ow (tx).
+ * Refused with NERFAIL_EINVAL before a launch: a NULL pointer (src, out, ty, tx or a table pointer), layout other than 0 or 1,
+ * B outside 1..65535, H, W, oh or ow < 1, ty / tx not of H -> oh / W -> ow (n_in, n_out), kmax outside 1..16 or below the axis'
+ * largest count, an axis nerfail_resize_aa_table refuses, src not aligned (16 bytes for layout 0, else 4), out not 4-byte aligned. */
+int nerfail_cls_input_resize_fwd(const float* src, int layout, int B, int H, int W, int oh, int ow, const nerfail_resize_axis* ty,
+                                 const nerfail_resize_axis* tx, float* out, void* stream);
+
+/* The adjoint for R right-hand sides of one forward: g float32 [R,B,3,oh,ow] -> gsrc. Layout 0: gsrc [R,B,H,W,4] (16-byte aligned),
+ * the first three channels a > 0 ? gx : +0 with a the fourth channel of src (the forward's input, needed for nothing else), the
+ * fourth channel 0 - what autograd gives through torch.where. Layout 1: gsrc [R,B,3,H,W]; src is not read and may be NULL. Every
+ * element of gsrc is written. One workgroup owns a source tile of one view and loops over r: the g window is staged in LDS, the
+ * vertical pass runs LDS -> LDS, the horizontal pass LDS -> registers, layout 0 stores 16 bytes per pixel. Slice r is, bit for
+ * bit, what the call returns for g[r] alone (R = 1). Refused with NERFAIL_EINVAL before a launch: everything the forward refuses
+ * (g and gsrc in the places of src and out), R outside 1..8, layout 0 with a NULL src. */
+int nerfail_cls_input_resize_bwd(const float* g, int R, const float* src, int layout, int B, int H, int W, int oh, int ow,
+                                 const nerfail_resize_axis* ty, const nerfail_resize_axis* tx, float* gsrc, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

@@ -20,6 +20,8 @@ SCENE_REVISION = 1                       # nerfail_scene_revision: the 8-NN sear
 U2D_REVISION = 1                         # nerfail_u2d_revision: the IGSM-2D baseline's forward, step and statistics (attack.igsm_2d)
 UAP2D_REVISION = 1                       # nerfail_uap2d_revision: the UAP-2D baseline's DeepFool step and projection (attack.uap_2d)
 POISON_REVISION = 1                      # nerfail_poison_revision: the export -> training-target hand-off (retrain.PoisonedTrainSet)
+RESIZE_REVISION = 1                      # nerfail_resize_revision: the classifier-input resize and its adjoint (_resize.classifier_input)
+RESIZE_MAX_TAPS = 16                     # NERFAIL_RESIZE_MAX_TAPS
 UAP2D_NORM_TERMS = 24                   # NERFAIL_UAP2D_NORM_TERMS: float32 terms per lane of nerfail_uap2d_step's norms
 DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
 DEEPFOOL_RECORD_WORDS = 4 + 2 * DEEPFOOL_MAX_COMPETITORS    # struct nerfail_deepfool_record as 32-bit words
@@ -201,6 +203,12 @@ SIGNATURES = {
     'nerfail_uap2d_accumulate': (c_i, [c_p, c_p, c_f, c_i64, c_p]),
     'nerfail_poison_revision': (c_i, []),
     'nerfail_export_train_views': (c_i, [c_p, c_i, c_i, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    'nerfail_resize_revision': (c_i, []),
+    'nerfail_resize_aa_kmax': (c_i, [c_i, c_i]),
+    'nerfail_resize_aa_table': (c_i, [c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p]),
+    'nerfail_resize_tiles': (c_i, [c_i, c_i, c_i, c_i, c_p, c_p]),
+    'nerfail_cls_input_resize_fwd': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    'nerfail_cls_input_resize_bwd': (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -225,6 +233,12 @@ class ViewIndexStruct(ctypes.Structure):
 class ViewFwdStruct(ctypes.Structure):
     """struct nerfail_view_fwd (include/nerfail_hip.h)"""
     _fields_ = [('weight_and_index', c_p), ('ori_img', c_p)]
+
+
+class ResizeAxisStruct(ctypes.Structure):
+    """struct nerfail_resize_axis (include/nerfail_hip.h)"""
+    _fields_ = [('start', c_p), ('count', c_p), ('w', c_p), ('ostart', c_p), ('ocount', c_p),
+                ('n_in', ctypes.c_int32), ('n_out', ctypes.c_int32), ('kmax', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
 class AdamTensor(ctypes.Structure):
@@ -274,6 +288,9 @@ def load():
     if lib.nerfail_poison_revision() != POISON_REVISION:
         raise RuntimeError('nerfail_amd: poisoned-retrain revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_poison_revision(), POISON_REVISION))
+    if lib.nerfail_resize_revision() != RESIZE_REVISION:
+        raise RuntimeError('nerfail_amd: classifier-input resize revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_resize_revision(), RESIZE_REVISION))
     _lib = lib
     return lib
 

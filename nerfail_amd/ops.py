@@ -1063,3 +1063,65 @@ def _(x, slots, adv_u8, target):
 
 
 POISON_OPS = ('export_train_views',)
+
+
+# ----------------------------------------------------------------------------------------------- classifier-input resize (GN:121-157; resize revision 1)
+def _resize_axes(H, W, oh, ow, device):
+    from ._resize import axis_tables
+    return axis_tables(H, oh, device), axis_tables(W, ow, device)
+
+
+@custom_op(NS + '::cls_input_resize', mutates_args=(), device_types='cuda')
+def cls_input_resize(src: Tensor, layout: int, oh: int, ow: int) -> Tensor:
+    """The classifier input [B,3,oh,ow] of src: layout 0 = [B,H,W,4] (white where alpha > 0 is false), layout 1 = [B,3,H,W]."""
+    if layout not in (0, 1) or src.dim() != 4 or src.dtype != torch.float32 or src.shape[3 if layout == 0 else 1] != (4 if layout == 0 else 3):
+        raise ValueError('cls_input_resize: src must be float32 [B,H,W,4] (layout 0) or [B,3,H,W] (layout 1)')
+    B = src.shape[0]
+    H, W = (src.shape[1], src.shape[2]) if layout == 0 else (src.shape[2], src.shape[3])
+    ty, tx = _resize_axes(H, W, oh, ow, src.device)
+    out = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=src.device)
+    _chk(_lib.load().nerfail_cls_input_resize_fwd(_lib.dev(src, 'src'), layout, B, H, W, oh, ow, ty.ref, tx.ref, _lib.dev(out), _s()))
+    return out
+
+
+@cls_input_resize.register_fake
+def _(src, layout, oh, ow):
+    return src.new_empty((src.shape[0], 3, oh, ow))
+
+
+@custom_op(NS + '::cls_input_resize_bwd', mutates_args=(), device_types='cuda')
+def cls_input_resize_bwd(g: Tensor, src: Optional[Tensor], layout: int, H: int, W: int) -> Tensor:
+    """The adjoint of cls_input_resize for g [R,B,3,oh,ow], 1 <= R <= 8: [R,B,H,W,4] (layout 0; src = the forward's input, read for
+    its alpha) or [R,B,3,H,W] (layout 1; src unused). Slice r is bitwise the R = 1 result for g[r]."""
+    if layout not in (0, 1) or g.dim() != 5 or g.dtype != torch.float32 or g.shape[2] != 3:
+        raise ValueError('cls_input_resize_bwd: g must be float32 [R,B,3,oh,ow]')
+    R, B, _, oh, ow = g.shape
+    if layout == 0 and (src is None or tuple(src.shape) != (B, H, W, 4) or src.dtype != torch.float32):
+        raise ValueError('cls_input_resize_bwd: layout 0 needs the forward\'s float32 src [B,H,W,4]')
+    ty, tx = _resize_axes(H, W, oh, ow, g.device)
+    out = torch.empty((R, B, H, W, 4) if layout == 0 else (R, B, 3, H, W), dtype=torch.float32, device=g.device)
+    _chk(_lib.load().nerfail_cls_input_resize_bwd(_lib.dev(g, 'g'), R, _lib.dev(src, 'src') if layout == 0 else None, layout, B, H, W, oh, ow,
+                                                  ty.ref, tx.ref, _lib.dev(out), _s()))
+    return out
+
+
+@cls_input_resize_bwd.register_fake
+def _(g, src, layout, H, W):
+    return g.new_empty((g.shape[0], g.shape[1], H, W, 4) if layout == 0 else (g.shape[0], g.shape[1], 3, H, W))
+
+
+def _resize_setup(ctx, inputs, output):
+    src, layout, oh, ow = inputs
+    ctx.layout = layout
+    ctx.hw = (src.shape[1], src.shape[2]) if layout == 0 else (src.shape[2], src.shape[3])
+    ctx.save_for_backward(*((src,) if layout == 0 else ()))
+
+
+def _resize_backward(ctx, g):
+    src = ctx.saved_tensors[0] if ctx.layout == 0 else None
+    return cls_input_resize_bwd(g.contiguous()[None], src, ctx.layout, ctx.hw[0], ctx.hw[1])[0], None, None, None
+
+
+cls_input_resize.register_autograd(_resize_backward, setup_context=_resize_setup)
+
+RESIZE_OPS = ('cls_input_resize', 'cls_input_resize_bwd')
