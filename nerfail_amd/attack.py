@@ -229,24 +229,88 @@ class AttackResult:
         self.best, self.last, self.stats, self.best_epoch, self.best_acc = best, last, stats, best_epoch, best_acc
 
 
-def _read_stats(record, minmax):
-    """THE host read of an epoch: its record and the running epsilon_3d [min, max], one device-to-host copy."""
-    v = torch.cat([record, minmax]).cpu().tolist()
+def _attack_result(best, last, records, epochs):
+    """The AttackResult of nerfail_s and igsm_2d: best_epoch / best_acc are the last ATTACK epoch's record (records[-1] is the
+    export epoch's)."""
+    d = records[-2] if epochs > 1 else None
+    return AttackResult(best, last, records, d['best_epoch'] if d else -1, d['best_acc'] if d else None)
+
+
+def _read_stats(record, minmax=None):
+    """THE host read of an epoch: its record and, where the loop has one (nerfail_s), the running epsilon_3d [min, max], in one
+    device-to-host copy."""
+    v = (record if minmax is None else torch.cat([record, minmax])).cpu().tolist()
     d = dict(zip(STAT_FIELDS, v))
     for k in ('views', 'taken', 'best_epoch', 'epoch', 'test_correct', 'attack_correct'):
         d[k] = int(d[k])
-    d['epsilon_3d_min'], d['epsilon_3d_max'] = v[-2], v[-1]
+    if minmax is not None:
+        d['epsilon_3d_min'], d['epsilon_3d_max'] = v[-2], v[-1]
     return d
+
+
+def _log_loss_acc(log, d):
+    """The two lines every epoch (AS:415-416, IG:402-403) and every pass (AN:481-482, UA:345-346) print."""
+    log('{} Loss: {:.4f} Acc: {:.4f}'.format('test', d['test_loss'], d['test_acc']))
+    log('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', d['attack_loss'], d['attack_acc']))
+
+
+def _log_epsilon(log, d):
+    """print_epsilon (AS:419, AN:487)."""
+    log('epsilon_3d_min:  %s' % d['epsilon_3d_min'])
+    log('epsilon_3d_max:  %s' % d['epsilon_3d_max'])
+
+
+def _log_epoch(log, epoch, epochs, d, beta):
+    """The reference's log block of an epoch (AS:415-418 = IG:402-405, where beta is the constant 0.) and print_epsilon's two
+    lines when the record carries them. log=None prints nothing."""
+    if log is None:
+        return
+    log('Attack ...... [%d/%d]' % (epoch, epochs))
+    _log_loss_acc(log, d)
+    b1 = 1. - beta                                                                                                # (AS:340 has no abs)
+    log('{} Beta Loss: {:.4f} Beta Img Loss: {:.4f}'.format('attack', b1 * d['attack_loss'], beta * d['img_loss']))
+    log('{} Img Loss: {:.4f} Total Loss: {:.4f}'.format('attack', d['img_loss'], (1. - abs(beta)) * d['attack_loss'] + beta * d['img_loss']))
+    if 'epsilon_3d_min' in d:
+        _log_epsilon(log, d)
+
+
+def _check_epochs(epochs):
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    return epochs
+
+
+def _check_one_rank(what):
+    """nerfail and uap_2d update their table view by view: `what` names the loop and its table in the refusal."""
+    world = sharding.world_and_rank(None)[0]
+    if world > 1:
+        raise ValueError('%s view by view: there is nothing to shard over %d ranks' % (what, world))
+
+
+def _check_export_views(caller, items):
+    """An export epoch without views would never end the loop (nothing sets tensor_not_changed). `items`: the views of the export
+    epoch where they are known - a callable is checked when its pass begins."""
+    if items is not None and not callable(items) and len(items) == 0:
+        raise ValueError('%s: the export epoch needs at least one view (export_views is empty)' % caller)
 
 
 def _ori_pointer_table(views):
     return (_lib.c_p * views.B)(*[o.data_ptr() for o in views.ori])
 
 
-class _EpochStats:
-    """The device side of one run's bookkeeping: a stats row and a record per epoch, the best record, the flag word."""
+def _logit_stats(lib, cla, ori_cla, label, row):
+    """AS:319-344's four logit sums and two correct counts of one batch into the stats row `row`, no host read."""
+    c, oc = _lib.f32c(cla), _lib.f32c(ori_cla)
+    _lib.check(lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], int(label), _lib.dev(row), _lib.stream()))
 
-    def __init__(self, epochs, targeted, label, dev):
+
+class _EpochStats:
+    """The device side of one run's bookkeeping: a stats row and a record per epoch, the best record, the flag word. `strict`:
+    the rule an epoch is closed with - False AS:422-431 (<= / >=, a tie goes to the later epoch; the stats row all-reduced in
+    front of it), True IG:407-416 (< / >, a tie keeps the earlier epoch; one rank)."""
+
+    def __init__(self, epochs, targeted, label, dev, strict=False):
         n = _lib.ATTACK_ROW_FLOATS
         self.rows = torch.zeros((epochs, n), dtype=torch.float32, device=dev)
         self.records = torch.zeros((epochs, n), dtype=torch.float32, device=dev)
@@ -256,17 +320,19 @@ class _EpochStats:
         self.flag = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.lib = _lib.load()
         self.scratch = torch.empty((self.lib.nerfail_img_sqerr_scratch_bytes() // 8,), dtype=torch.float64, device=dev)
-        self.targeted, self.label = int(bool(targeted)), int(label)
+        self.targeted, self.label, self.strict = int(bool(targeted)), int(label), bool(strict)
 
     def batch(self, epoch, cla, ori_cla, x_rgba, views):
         """AS:319-344 for one batch (this rank's views of it): five sums into the epoch's row, no host read."""
-        row = _lib.dev(self.rows[epoch])
-        c, oc = _lib.f32c(cla), _lib.f32c(ori_cla)
-        _lib.check(self.lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], self.label, row, _lib.stream()))
+        _logit_stats(self.lib, cla, ori_cla, self.label, self.rows[epoch])
         _lib.check(self.lib.nerfail_img_sqerr(_lib.dev(x_rgba.detach()), _ori_pointer_table(views), views.B, views.P, int(views.ori_u8),
-                                              _lib.c_p(self.scratch.data_ptr()), row, _lib.stream()))
+                                              _lib.c_p(self.scratch.data_ptr()), _lib.dev(self.rows[epoch]), _lib.stream()))
 
-    def close(self, epoch, group):
+    def close(self, epoch, group=None):
+        """The epoch's sums become its record (means, the rule's decision, the best record) and the flag word, on the device."""
+        if self.strict:
+            ops.u2d_epoch_close(self.rows[epoch], self.best, epoch, bool(self.targeted), self.records[epoch], self.flag)
+            return
         sharding.all_reduce_sum_(self.rows[epoch], group)            # the ONE extra collective of an epoch (when sharded): 16 floats
         _lib.check(self.lib.nerfail_attack_epoch_close(_lib.dev(self.rows[epoch]), _lib.dev(self.best), epoch, self.targeted,
                                                        _lib.dev(self.records[epoch]), _lib.dev(self.flag), _lib.stream()))
@@ -276,16 +342,34 @@ class _EpochStats:
 
 
 class _ExportBuffers:
-    """Device uint8 [2,B,H,W,4] (adversarial image, mask image) and its pinned host twin, kept per batch shape."""
+    """The export epoch's way to the host: a device uint8 buffer with one 16-byte aligned slot per image and its pinned host twin,
+    kept per tuple of image sizes for the run."""
 
     def __init__(self):
         self.bufs = {}
+        self.lib = _lib.load()
 
-    def get(self, shape, dev):
-        if shape not in self.bufs:
-            self.bufs[shape] = (torch.empty((2,) + shape, dtype=torch.uint8, device=dev),
-                                torch.empty((2,) + shape, dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
-        return self.bufs[shape]
+    def to_host(self, *images):
+        """float32 device tensors -> one host uint8 array per tensor, shaped like it, converted as cv2.imwrite converts a float
+        image (nerfail_export_u8): one launch per image, ONE copy, one event wait. The arrays are copies: they alias neither the
+        pinned buffer nor each other. An image whose pointer is not 16-byte aligned (a row range of the best table) is cloned
+        first: the kernel reads 128 bits at a time."""
+        sizes = tuple(t.numel() for t in images)
+        starts = [0]
+        for n in sizes:
+            starts.append(starts[-1] + -(-n // 16) * 16)
+        if sizes not in self.bufs:                                         # (free again: every call waits for its own copy below)
+            self.bufs[sizes] = (torch.empty((starts[-1],), dtype=torch.uint8, device=images[0].device),
+                                torch.empty((starts[-1],), dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
+        d_u8, h_u8, ev = self.bufs[sizes]
+        for t, n, at in zip(images, sizes, starts):
+            src = t if t.data_ptr() % 16 == 0 else t.clone()
+            _lib.check(self.lib.nerfail_export_u8(_lib.dev(src), n, _lib.dev(d_u8[at:at + n]), _lib.stream()))
+        h_u8.copy_(d_u8, non_blocking=True)
+        ev.record()
+        ev.synchronize()
+        arr = h_u8.numpy()
+        return [arr[at:at + n].reshape(tuple(t.shape)).copy() for t, n, at in zip(images, sizes, starts)]
 
 
 def _export_batch(net, best, batch, index, stats, epoch, group, bufs, on_export, export_sink=None):
@@ -299,17 +383,8 @@ def _export_batch(net, best, batch, index, stats, epoch, group, bufs, on_export,
     stats.batch(epoch, cla, ori_cla, x_rgba, views)
     if export_sink is not None:
         export_sink.put(parts[2], x_rgba)
-    if on_export is None:
-        return
-    d_u8, h_u8, ev = bufs.get(tuple(x_rgba.shape), x_rgba.device)         # (free again: every call waits for its own copy below)
-    n = x_rgba.numel()
-    _lib.check(stats.lib.nerfail_export_u8(_lib.dev(x_rgba), n, _lib.dev(d_u8[0]), _lib.stream()))
-    _lib.check(stats.lib.nerfail_export_u8(_lib.dev(x), n, _lib.dev(d_u8[1]), _lib.stream()))
-    h_u8.copy_(d_u8, non_blocking=True)
-    ev.record()
-    ev.synchronize()
-    arr = h_u8.numpy()
-    on_export(index, parts[2], arr[0].copy(), arr[1].copy())
+    if on_export is not None:
+        on_export(index, parts[2], *bufs.to_host(x_rgba, x))
 
 
 def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=False, beta=0., export_batches=None,
@@ -360,9 +435,7 @@ def _nerfail_s(export_sink, net, spatial, batches, label, epochs, a=2., epsilon=
     """The body of nerfail_s (its defaults repeated for nerfail_s_into's pass-through)."""
     if not (getattr(net, 'deterministic', True) and getattr(net, 'rgb_grad_only', True)):
         raise ValueError('nerfail_s runs the deterministic rgb-gradient step path (net.deterministic and net.rgb_grad_only)')
-    epochs = int(epochs)
-    if epochs < 1:
-        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    epochs = _check_epochs(epochs)
     if not -1. <= float(beta) <= 1.:
         raise ValueError('beta must be in [-1, 1] (AS:332-336)')
     dev = _cuda()
@@ -378,18 +451,8 @@ def _nerfail_s(export_sink, net, spatial, batches, label, epochs, a=2., epsilon=
     records = []
 
     def finish(epoch):
-        d = _read_stats(stats.records[epoch], net._mm())
-        records.append(d)
-        if log is not None and rank == 0:
-            log('Attack ...... [%d/%d]' % (epoch, epochs))
-            log('{} Loss: {:.4f} Acc: {:.4f}'.format('test', d['test_loss'], d['test_acc']))                       # AS:415-418
-            log('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', d['attack_loss'], d['attack_acc']))
-            b1 = 1. - beta                                                                                        # (AS:340 has no abs)
-            log('{} Beta Loss: {:.4f} Beta Img Loss: {:.4f}'.format('attack', b1 * d['attack_loss'], beta * d['img_loss']))
-            log('{} Img Loss: {:.4f} Total Loss: {:.4f}'.format('attack', d['img_loss'],
-                                                                  (1. - abs(beta)) * d['attack_loss'] + beta * d['img_loss']))
-            log('epsilon_3d_min:  %s' % d['epsilon_3d_min'])
-            log('epsilon_3d_max:  %s' % d['epsilon_3d_max'])
+        records.append(_read_stats(stats.records[epoch], net._mm()))
+        _log_epoch(log if rank == 0 else None, epoch, epochs, records[-1], beta)
         net.epsilon_3d_zero()                                         # AS:420
 
     for epoch in range(epochs - 1):
@@ -404,9 +467,7 @@ def _nerfail_s(export_sink, net, spatial, batches, label, epochs, a=2., epsilon=
         _export_batch(net, best, batch, i, stats, epoch, group, bufs, on_export, export_sink)
     stats.close(epoch, group)                                         # (its decision moves no tensor: the epoch ran on `best` itself)
     finish(epoch)
-    last_attack = records[-2] if epochs > 1 else None
-    return AttackResult(best, s, records, last_attack['best_epoch'] if last_attack else -1,
-                        last_attack['best_acc'] if last_attack else None)
+    return _attack_result(best, s, records, epochs)
 
 
 # ---------------------------------------------------------------------------------------------- the product loop (AN:269-512)
@@ -432,15 +493,47 @@ class _PassStats:
         self.row = torch.zeros((_lib.ATTACK_ROW_FLOATS,), dtype=torch.float32, device=dev)
 
     def batch(self, epoch, cla, ori_cla, x_rgba=None, views=None):
-        c, oc = _lib.f32c(cla), _lib.f32c(ori_cla)
-        _lib.check(self.lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], self.label, _lib.dev(self.row),
-                                                       _lib.stream()))
+        _logit_stats(self.lib, cla, ori_cla, self.label, self.row)
 
-    def read(self, minmax):
-        """THE host read of a pass: the four sums as AN:476-480 divides them, and epsilon_3d's [min, max]."""
-        v = torch.cat([self.row, minmax]).cpu().tolist()
-        return dict(test_sum=v[0] + v[1], attack_sum=v[2] + v[3], test_correct=int(v[4]), attack_correct=int(v[5]), seen=int(v[6]),
-                    epsilon_3d_min=v[-2], epsilon_3d_max=v[-1])
+    def read(self, n_views, minmax=None):
+        """THE host read of a pass, one device-to-host copy: its means as AN:476-480 / UA:340-344 divide the four sums and the
+        two correct counts by `n_views` = len(now_dataloader.dataset) (NaN for a pass without views) and, where the loop has one
+        (nerfail), epsilon_3d's [min, max]."""
+        v = (self.row if minmax is None else torch.cat([self.row, minmax])).cpu().tolist()
+        d = dict(views=n_views, test_correct=int(v[4]), attack_correct=int(v[5]))
+        for k, total in (('test_loss', v[0] + v[1]), ('test_acc', d['test_correct']), ('attack_loss', v[2] + v[3]),
+                         ('attack_acc', d['attack_correct'])):
+            d[k] = total / n_views if n_views else float('nan')
+        if minmax is not None:
+            d['epsilon_3d_min'], d['epsilon_3d_max'] = v[-2], v[-1]
+        return d
+
+
+class _Visits:
+    """What a pass of nerfail / uap_2d counts view by view; fields() is its part of the pass's record. `key`: what names the
+    visit in `visits` (nerfail: the position in the pass, uap_2d: the view index)."""
+
+    def __init__(self):
+        self.visits, self.skipped, self.attacked, self.completed, self.iters = [], 0, 0, 0, 0
+
+    def skip(self, key):
+        self.skipped += 1
+        self.visits.append((key, True, 0, []))
+
+    def ran(self, key, iter_k, classes):
+        """A DeepFool call of iter_k iterations; `classes`: the class chosen in each, None with the mirror."""
+        self.attacked += 1
+        self.iters += iter_k
+        self.visits.append((key, False, iter_k, classes))
+
+    def fields(self):
+        return dict(skipped=self.skipped, attacked=self.attacked, completed=int(self.completed), deepfool_iters=self.iters,
+                    visits=self.visits)
+
+
+def _deepfool_kw(num_classes, df_max_iter, label, targeted, overshoot, m1, m2):
+    """The keyword arguments a pass hands to deepfool[_2d][_native] (AN:396-402, UA:306-312)."""
+    return dict(num_classes=num_classes, max_iter=df_max_iter, target_label=label if targeted else None, overshoot=overshoot, m1=m1, m2=m2)
 
 
 def _pass_done(index, table):
@@ -485,14 +578,9 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
     class of every iteration or None with the mirror)."""
     import time
     from . import deepfool as DF
-    epochs = int(epochs)
-    if epochs < 1:
-        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
-    exp = export_views if export_views is not None else views
-    if not callable(exp) and len(exp) == 0:                               # (nothing would set tensor_not_changed: the loop could not end)
-        raise ValueError('nerfail: the export epoch needs at least one view (export_views is empty)')
-    if sharding.world_and_rank(None)[0] > 1:
-        raise ValueError('nerfail updates the table view by view: there is nothing to shard over %d ranks' % sharding.world_and_rank(None)[0])
+    epochs = _check_epochs(epochs)
+    _check_export_views('nerfail', export_views if export_views is not None else views)
+    _check_one_rank('nerfail updates the table')
     dev = _cuda()
     say = log if log is not None else (lambda *_: None)
     label_i = int(label)
@@ -514,10 +602,9 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
         export = epoch == epochs - 1
         src = (export_views if export_views is not None else views) if export else views
         items = list(src(n_pass) if callable(src) else src)
-        if export and not items:                                          # (nothing would set tensor_not_changed: the loop could not end)
-            raise ValueError('nerfail: the export epoch needs at least one view (export_views is empty)')
-        stats = _PassStats(label_i, dev)
-        visits, skipped, attacked, completed, iters, raises = [], 0, 0, 0, 0, 0
+        if export:
+            _check_export_views('nerfail', items)
+        stats, seen, raises = _PassStats(label_i, dev), _Visits(), 0
         pass_epoch, pass_m1 = epoch, m1
         for i, item in enumerate(items):
             wi, ori = item[0], item[1]
@@ -539,11 +626,9 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
             stats.batch(epoch, cla, ori_cla)
             net.close_update_epsilon_3d()
             if not _same_class(cla, ori_cla):
-                skipped += 1
-                visits.append((i, True, 0, []))
+                seen.skip(i)
                 continue
-            kw = dict(num_classes=num_classes, max_iter=df_max_iter, target_label=label_i if targeted else None, overshoot=overshoot,
-                      m1=m1, m2=m2)
+            kw = _deepfool_kw(num_classes, df_max_iter, label_i, targeted, overshoot, m1, m2)
             if native is None or native:
                 dr, iter_k, _, _, _, classes = DF.deepfool_native((table, wi, ori), None, net, view_ids=vids, **kw)
             else:
@@ -551,15 +636,13 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
                     wi, ori = net._last_views.wi_batch(), net._last_ori
                 dr, iter_k, _, _, _ = DF.deepfool((table, wi, ori), None, net, **kw)
                 classes = None
-            attacked += 1
-            iters += iter_k
-            visits.append((i, False, iter_k, classes))
+            seen.ran(i, iter_k, classes)
             if iter_k < df_max_iter or accumulate_incomplete:             # AN:405-409
                 say('iter_k < df_max_iter')
                 table += dr
                 not_changed = False
                 attack_all += 1
-                completed += iter_k < df_max_iter
+                seen.completed += iter_k < df_max_iter
             elif m2 < m2_max_limit:                                       # AN:410-418
                 no_attack += 1
                 attack_all += 1
@@ -600,16 +683,11 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
                 epoch += 1
         else:
             epoch += 1
-        d = stats.read(net._mm())                                         # THE host read of the pass
-        n_views = len(items)                                              # len(now_dataloader.dataset), AN:476-480
-        nan = float('nan')
-        test_loss, test_acc = (d['test_sum'] / n_views, d['test_correct'] / n_views) if n_views else (nan, nan)
-        attack_loss, attack_acc = (d['attack_sum'] / n_views, d['attack_correct'] / n_views) if n_views else (nan, nan)
-        say('{} Loss: {:.4f} Acc: {:.4f}'.format('test', test_loss, test_acc))
-        say('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', attack_loss, attack_acc))
+        d = stats.read(len(items), net._mm())                             # THE host read of the pass; AN:476-480
+        attack_acc = d['attack_acc']
+        _log_loss_acc(say, d)
         need_to_log['m1-' + str(m1) + ' epoch-' + str(epoch)] = 'time: {} Acc: {:.4f}'.format(time.time() - since, attack_acc)
-        say('epsilon_3d_min:  %s' % d['epsilon_3d_min'])                   # print_epsilon, AN:487
-        say('epsilon_3d_max:  %s' % d['epsilon_3d_max'])
+        _log_epsilon(say, d)                                              # AN:487
         net.epsilon_3d_zero()
         if targeted:                                                      # AN:490-503
             take = (attack_acc >= best_acc and m1 == m1_best) or (m1 > m1_best and attack_acc > 0)
@@ -618,11 +696,8 @@ def nerfail(net, spatial, views, label, epochs, m1=8, m2=100, targeted=False, df
         if take:
             best_acc, m1_best, m2_best = attack_acc, m1, m2
             best = table.clone().detach()
-        records.append(dict(m1=m1, m2=m2, m1_pass=pass_m1, epoch=pass_epoch, next_epoch=epoch, test_loss=test_loss, test_acc=test_acc,
-                            attack_loss=attack_loss, attack_acc=attack_acc, views=n_views, skipped=skipped, attacked=attacked,
-                            completed=int(completed), deepfool_iters=iters, m2_raises=raises, taken=int(bool(take)),
-                            epsilon_3d_min=d['epsilon_3d_min'], epsilon_3d_max=d['epsilon_3d_max'], visits=visits,
-                            test_correct=d['test_correct'], attack_correct=d['attack_correct']))
+        records.append(dict(d, m1=m1, m2=m2, m1_pass=pass_m1, epoch=pass_epoch, next_epoch=epoch, m2_raises=raises, taken=int(bool(take)),
+                            **seen.fields()))
         _pass_done(n_pass, table)
         n_pass += 1
     return NerfailResult(best, table, m1_best, m2_best, best_acc, records, need_to_log)
@@ -638,6 +713,54 @@ def _frozen(model):
     if not isinstance(model, torch.nn.Module):
         return False
     return not any(m.training for m in model.modules()) and not any(p.requires_grad for p in model.parameters())
+
+
+class _Store2D:
+    """What igsm_2d and uap_2d (`caller`) set up alike in front of their loops: the resident uint8 store, the native gate, the
+    classifier in eval() mode with frozen parameters (IG:266-272 / UA:244-250) and the clean images' logits, which then never
+    change: they are computed at a view range's first use and kept for the run (else computed at every use, as the reference)."""
+
+    def __init__(self, caller, model, model_name, images, native, dev):
+        from .GaussNet import u2d_resize
+        from .MyModel import MyCNN
+        if isinstance(images, (list, tuple)):
+            images = torch.stack([torch.as_tensor(v) for v in images])
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] not in (3, 4):
+            raise ValueError('images must be a uint8 store [N,H,W,4] (BGRA) or [N,H,W,3]')
+        self.images = images.to(dev).contiguous()
+        self.N, self.H, self.W = self.images.shape[:3]
+        if self.N < 1:
+            raise ValueError('images holds no view')
+        self.can_native = isinstance(model, MyCNN) and model_name == "my_model"
+        if native and not self.can_native:
+            raise ValueError('%s: native=True needs this package\'s MyCNN as `model` and model_name == "my_model"' % caller)
+        if isinstance(model, torch.nn.Module):
+            model.train(False)
+            for p in model.parameters():
+                p.requires_grad = False
+        self.model, self.model_name, self.resize, self.frozen = model, model_name, u2d_resize, _frozen(model)
+        self.zero_plane = torch.zeros((self.H, self.W, 3), dtype=torch.float32, device=dev)
+        self.idx_all = torch.arange(self.N, dtype=torch.int64, device=dev)
+        self.clean = {}
+
+    def classify(self, cls_in):
+        return self.model(self.resize(cls_in, self.model_name))
+
+    def clean_logits(self, lo, hi):
+        """The classifier's logits of the clean views lo..hi-1, float32 [hi - lo, C]."""
+        if (lo, hi) in self.clean:
+            return self.clean[lo, hi]
+        with torch.no_grad():
+            _, clean_in, _ = ops.u2d_fwd(self.images, self.idx_all[lo:hi], self.zero_plane, False, True, False)   # o + 0, clipped: o itself
+            oc = _lib.f32c(self.classify(clean_in))
+        if self.frozen:
+            self.clean[lo, hi] = oc
+        return oc
+
+    def ori(self, v):
+        """The clean view v on its white background, float32 [1,H,W,3]."""
+        with torch.no_grad():
+            return ops.u2d_fwd(self.images, self.idx_all[v:v + 1], self.zero_plane, True, False, False)[0]
 
 
 def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targeted=False, batch_size=4, on_export=None, log=print,
@@ -679,76 +802,33 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
 
     Host reads: one per epoch (the record, for the reference's four log lines, IG:402-405; log=None keeps the read and drops
     the lines), plus one wait per export batch. Returns an AttackResult: `best` and `last` are [N,H,W,3]."""
-    from .GaussNet import u2d_resize
-    from .MyModel import MyCNN
-    epochs = int(epochs)
-    if epochs < 1:
-        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
+    epochs = _check_epochs(epochs)
     batch_size = int(batch_size)
     if not 1 <= batch_size <= 65535:
         raise ValueError('batch_size must be in 1..65535')
     dev = _cuda()
-    if isinstance(images, (list, tuple)):
-        images = torch.stack([torch.as_tensor(v) for v in images])
-    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] not in (3, 4):
-        raise ValueError('images must be a uint8 store [N,H,W,4] (BGRA) or [N,H,W,3]')
-    images = images.to(dev).contiguous()
-    N, H, W = images.shape[:3]
-    if N < 1:
-        raise ValueError('images holds no view')
-    can_native = isinstance(model, MyCNN) and model_name == "my_model"
-    if native and not can_native:
-        raise ValueError('igsm_2d: native=True needs this package\'s MyCNN as `model` and model_name == "my_model"')
-    use_native = can_native and (native is None or bool(native))
-    if isinstance(model, torch.nn.Module):                                # IG:266-272
-        model.train(False)
-        for p in model.parameters():
-            p.requires_grad = False
+    store = _Store2D('igsm_2d', model, model_name, images, native, dev)                # IG:266-272
+    images, idx_all, N, H, W = store.images, store.idx_all, store.N, store.H, store.W
+    use_native = store.can_native and (native is None or bool(native))
     a, epsilon, targeted = float(a), float(epsilon), bool(targeted)
     label_i = int(label)
     lab32 = torch.full((batch_size,), label_i, dtype=torch.int32, device=dev)
     table = torch.zeros((N, H, W, 3), dtype=torch.float32, device=dev)     # IG:250; its init is the zero table: r_init = NULL
     best = torch.zeros_like(table)
-    zero_plane = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
     batches = [(lo, min(lo + batch_size, N)) for lo in range(0, N, batch_size)]
-    idx_all = torch.arange(N, dtype=torch.int64, device=dev)
-    stats = _EpochStats(epochs, targeted, label_i, dev)
+    stats = _EpochStats(epochs, targeted, label_i, dev, strict=True)       # IG:407-416
     ce_row = torch.zeros((_lib.ATTACK_ROW_FLOATS,), dtype=torch.float32, device=dev)   # ops.cls_ce's own sums: not read
     bufs = _ExportBuffers()
     records = []
-    lib = stats.lib
-
-    def classify(cls_in):
-        return model(u2d_resize(cls_in, model_name))
-
-    def clean_logits(lo, hi):
-        with torch.no_grad():
-            _, clean_in, _ = ops.u2d_fwd(images, idx_all[lo:hi], zero_plane, False, True, False)   # o + 0, clipped: o itself
-            return _lib.f32c(classify(clean_in))
-    ori_cla_all = torch.cat([clean_logits(lo, hi) for lo, hi in batches]) if _frozen(model) else None
 
     def batch_stats(epoch, lo, hi, cla, x_rgb):
         """IG:306-331 for one batch: five sums into the epoch's row, no host read."""
-        oc = ori_cla_all[lo:hi] if ori_cla_all is not None else clean_logits(lo, hi)
-        c = _lib.f32c(cla)
-        row = _lib.dev(stats.rows[epoch])
-        _lib.check(lib.nerfail_attack_logit_stats(_lib.dev(c), _lib.dev(oc), c.shape[0], c.shape[1], label_i, row, _lib.stream()))
+        _logit_stats(stats.lib, cla, store.clean_logits(lo, hi), label_i, stats.rows[epoch])
         ops.u2d_sqerr(x_rgb, images, idx_all[lo:hi], stats.scratch, stats.rows[epoch])
 
     def finish(epoch):
-        ops.u2d_epoch_close(stats.rows[epoch], stats.best, epoch, targeted, stats.records[epoch], stats.flag)
-        if epoch < epochs - 1:
-            stats.keep_if_taken(table, best)
-        d = dict(zip(STAT_FIELDS, stats.records[epoch].cpu().tolist()))    # THE host read of the epoch
-        for k in ('views', 'taken', 'best_epoch', 'epoch', 'test_correct', 'attack_correct'):
-            d[k] = int(d[k])
-        records.append(d)
-        if log is not None:
-            log('Attack ...... [%d/%d]' % (epoch, epochs))
-            log('{} Loss: {:.4f} Acc: {:.4f}'.format('test', d['test_loss'], d['test_acc']))                       # IG:402-405
-            log('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', d['attack_loss'], d['attack_acc']))
-            log('{} Beta Loss: {:.4f} Beta Img Loss: {:.4f}'.format('attack', d['attack_loss'], 0. * d['img_loss']))
-            log('{} Img Loss: {:.4f} Total Loss: {:.4f}'.format('attack', d['img_loss'], d['attack_loss']))
+        records.append(_read_stats(stats.records[epoch]))                 # THE host read of the epoch
+        _log_epoch(log, epoch, epochs, records[-1], 0.)                   # IG:402-405; beta is the constant 0, IG:69
 
     for epoch in range(epochs - 1):
         for bi, (lo, hi) in enumerate(batches):
@@ -763,40 +843,28 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
                     d_in = ops.cnn_bwd_data(model.packed(), ws, pool, d_logits, H, W)
             else:
                 cls_in.requires_grad_()
-                cla = classify(cls_in)
+                cla = store.classify(cls_in)
                 batch_stats(epoch, lo, hi, cla.detach(), x_rgb)
                 d_logits = ops.cls_ce(_lib.f32c(cla), lab32[:B], ce_row, True)              # CrossEntropyLoss()'s gradient, as above
                 d_in = _lib.f32c(torch.autograd.grad(cla, cls_in, grad_outputs=d_logits.to(cla.dtype))[0])
             ops.u2d_step(table, ib, d_in, mask, None, a, epsilon, targeted)
             _igsm2d_batch_done(epoch, bi, table)
+        stats.close(epoch)
+        stats.keep_if_taken(table, best)
         finish(epoch)
     epoch = epochs - 1
     for bi, (lo, hi) in enumerate(batches):
         with torch.no_grad():
             x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[lo:hi], best, True, True, False)
-            cla = classify(cls_in)
+            cla = store.classify(cls_in)
             batch_stats(epoch, lo, hi, cla, x_rgb)
         if export_sink is not None:
             export_sink.put(list(range(lo, hi)), x_rgb)
-        if on_export is None:
-            continue
-        pert = best[lo:hi]
-        if pert.data_ptr() % 16:
-            pert = pert.clone()
-        n = x_rgb.numel()
-        slot = -(-n // 16) * 16                                           # each image starts 16-byte aligned, whatever B, H and W
-        d_u8, h_u8, ev = bufs.get((slot,), dev)
-        _lib.check(lib.nerfail_export_u8(_lib.dev(x_rgb), n, _lib.dev(d_u8[0]), _lib.stream()))
-        _lib.check(lib.nerfail_export_u8(_lib.dev(pert), n, _lib.dev(d_u8[1]), _lib.stream()))
-        h_u8.copy_(d_u8, non_blocking=True)
-        ev.record()
-        ev.synchronize()
-        arr = h_u8.numpy()[:, :n].reshape((2,) + tuple(x_rgb.shape))
-        on_export(bi, list(range(lo, hi)), arr[0].copy(), arr[1].copy())
-    finish(epoch)                                                         # (its decision moves no tensor: the epoch ran on `best` itself)
-    last_attack = records[-2] if epochs > 1 else None
-    return AttackResult(best, table, records, last_attack['best_epoch'] if last_attack else -1,
-                        last_attack['best_acc'] if last_attack else None)
+        if on_export is not None:
+            on_export(bi, list(range(lo, hi)), *bufs.to_host(x_rgb, best[lo:hi]))
+    stats.close(epoch)                                                    # (its decision moves no tensor: the epoch ran on `best` itself)
+    finish(epoch)
+    return _attack_result(best, table, records, epochs)
 
 
 # ---------------------------------------------------------------------------------------------- the product loop (UA:241-358)
@@ -854,58 +922,22 @@ def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, 
     test_correct, attack_correct, skipped, attacked, completed, deepfool_iters, taken and `visits`: per visit (view index,
     skipped, iter_k, the chosen class of every iteration or None with the mirror)."""
     from . import deepfool as DF
-    from .GaussNet import u2d_resize, universal_2D_net
-    from .MyModel import MyCNN
-    epochs = int(epochs)
-    if epochs < 1:
-        raise ValueError('epochs must be at least 1 (the last epoch is the export epoch)')
-    if sharding.world_and_rank(None)[0] > 1:
-        raise ValueError('uap_2d updates one table view by view: there is nothing to shard over %d ranks' % sharding.world_and_rank(None)[0])
+    from .GaussNet import universal_2D_net
+    epochs = _check_epochs(epochs)
+    _check_one_rank('uap_2d updates one table')
     dev = _cuda()
-    if isinstance(images, (list, tuple)):
-        images = torch.stack([torch.as_tensor(v) for v in images])
-    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] not in (3, 4):
-        raise ValueError('images must be a uint8 store [N,H,W,4] (BGRA) or [N,H,W,3]')
-    images = images.to(dev).contiguous()
-    N, H, W = images.shape[:3]
-    if N < 1:
-        raise ValueError('images holds no view')
-    if export_views is not None and not callable(export_views) and len(export_views) == 0:
-        raise ValueError('uap_2d: the export epoch needs at least one view (export_views is empty)')
-    can_native = isinstance(model, MyCNN) and model_name == "my_model"
-    if native and not can_native:
-        raise ValueError('uap_2d: native=True needs this package\'s MyCNN as `model` and model_name == "my_model"')
+    store = _Store2D('uap_2d', model, model_name, images, native, dev)                 # UA:244-250
+    images, idx_all, N, H, W = store.images, store.idx_all, store.N, store.H, store.W
+    _check_export_views('uap_2d', export_views)
     use_native = native is None or bool(native)
-    if isinstance(model, torch.nn.Module):                                # UA:244-250
-        model.train(False)
-        for p in model.parameters():
-            p.requires_grad = False
-    frozen = _frozen(model)
     net = universal_2D_net(dev, 0.02, model, model_name)
     epsilon, targeted, df_max_iter = float(epsilon), bool(targeted), int(df_max_iter)
     label_i = int(label)
     say = log if log is not None else (lambda *_: None)
-    lib = _lib.load()
     table = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)       # UA:219
     best = table.clone()
     best_acc = 0 if targeted else 10000                                   # UA:234-237
-    zero_plane = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
-    idx_all = torch.arange(N, dtype=torch.int64, device=dev)
     bufs = _ExportBuffers()
-    clean = {}
-
-    def classify(cls_in):
-        return model(u2d_resize(cls_in, model_name))
-
-    def clean_logits(v):
-        if v in clean:
-            return clean[v]
-        with torch.no_grad():
-            _, clean_in, _ = ops.u2d_fwd(images, idx_all[v:v + 1], zero_plane, False, True, False)   # o + 0, clipped: o itself
-            oc = _lib.f32c(classify(clean_in))
-        if frozen:
-            clean[v] = oc
-        return oc
 
     def views_of(src, n_pass):
         if src is None:
@@ -915,22 +947,6 @@ def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, 
             raise ValueError('uap_2d: a view index is outside the store (0..%d)' % (N - 1))
         return vs
 
-    def export_view(i, v, x_rgb):
-        n = x_rgb.numel()
-        slot = -(-n // 16) * 16                                           # each image starts 16-byte aligned
-        d_u8, h_u8, ev = bufs.get((3 * slot // 2,), dev)                  # [2, 3 slot / 2]: three slots
-        with torch.no_grad():
-            ori, _, _ = ops.u2d_fwd(images, idx_all[v:v + 1], zero_plane, True, False, False)
-        d = d_u8.view(-1)
-        for k, src in enumerate((x_rgb, table, ori)):
-            _lib.check(lib.nerfail_export_u8(_lib.dev(src), n, _lib.dev(d[k * slot:k * slot + n]), _lib.stream()))
-        h_u8.copy_(d_u8, non_blocking=True)
-        ev.record()
-        ev.synchronize()
-        arr = h_u8.numpy().reshape(-1)
-        on_export(i, [v], arr[:n].reshape(1, H, W, 3).copy(), arr[slot:slot + n].reshape(H, W, 3).copy(),
-                  arr[2 * slot:2 * slot + n].reshape(1, H, W, 3).copy())
-
     records = []
     epoch, n_pass = 0, 0
     while epoch < epochs:
@@ -938,10 +954,9 @@ def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, 
         not_changed = True
         export = epoch == epochs - 1
         items = views_of(export_views if export else attack_views, n_pass)
-        if export and not items:                                          # (nothing would set tensor_not_changed: the loop could not end)
-            raise ValueError('uap_2d: the export epoch needs at least one view (export_views is empty)')
-        stats = _PassStats(label_i, dev)
-        visits, skipped, attacked, completed, iters = [], 0, 0, 0, 0
+        if export:
+            _check_export_views('uap_2d', items)
+        stats, seen = _PassStats(label_i, dev), _Visits()
         pass_epoch = epoch
         for i, v in enumerate(items):
             if export and i == 0:
@@ -949,58 +964,43 @@ def uap_2d(model, model_name, images, label, epochs, epsilon=32., m1=8, m2=100, 
             with torch.no_grad():
                 want_x = export and (on_export is not None or export_sink is not None)
                 x_rgb, cls_in, _ = ops.u2d_fwd(images, idx_all[v:v + 1], table, want_x, True, False)
-                cla = _lib.f32c(classify(cls_in))
-            ori_cla = clean_logits(v)
+                cla = _lib.f32c(store.classify(cls_in))
+            ori_cla = store.clean_logits(v, v + 1)
             stats.batch(epoch, cla, ori_cla)                              # UA:275-289
             if export:
                 if export_sink is not None:
                     export_sink.put([v], x_rgb)
                 if on_export is not None:
-                    export_view(i, v, x_rgb)
+                    on_export(i, [v], *bufs.to_host(x_rgb, table, store.ori(v)))
                 not_changed = False                                       # UA:333
                 continue
             if not _same_class(cla, ori_cla):                             # UA:297-304
-                skipped += 1
-                visits.append((v, True, 0, []))
+                seen.skip(v)
                 continue
-            kw = dict(num_classes=num_classes, max_iter=df_max_iter, target_label=label_i if targeted else None, overshoot=overshoot,
-                      m1=m1, m2=m2)
+            kw = _deepfool_kw(num_classes, df_max_iter, label_i, targeted, overshoot, m1, m2)
             if use_native:
                 _, iter_k, _, _, r_final, classes = DF.deepfool_2d_native((table, None), epsilon, net, images=images, view=v,
                                                                           clean_logits=ori_cla, **kw)
             else:
-                with torch.no_grad():
-                    ori, _, _ = ops.u2d_fwd(images, idx_all[v:v + 1], zero_plane, True, False, False)
-                _, iter_k, _, _, r_final = DF.deepfool_2d((table, ori), epsilon, net, **kw)
+                _, iter_k, _, _, r_final = DF.deepfool_2d((table, store.ori(v)), epsilon, net, **kw)
                 classes = None
-            attacked += 1
-            iters += iter_k
-            visits.append((v, False, iter_k, classes))
+            seen.ran(v, iter_k, classes)
             if iter_k < df_max_iter:                                      # UA:315-319
                 say('iter_k < df_max_iter')
                 ops.uap2d_accumulate(table, _lib.f32c(r_final), epsilon)
                 not_changed = False
-                completed += 1
+                seen.completed += 1
         if not_changed:                                                   # UA:335-338
             epoch = epochs - 1
         else:
             epoch += 1
-        row = stats.row.cpu().tolist()                                    # THE host read of the pass
-        n_views = len(items)                                              # len(now_dataloader.dataset), UA:340-344
-        test_correct, attack_correct = int(row[4]), int(row[5])
-        nan = float('nan')
-        test_loss, test_acc = ((row[0] + row[1]) / n_views, test_correct / n_views) if n_views else (nan, nan)
-        attack_loss, attack_acc = ((row[2] + row[3]) / n_views, attack_correct / n_views) if n_views else (nan, nan)
-        say('{} Loss: {:.4f} Acc: {:.4f}'.format('test', test_loss, test_acc))
-        say('{} Loss: {:.4f} Acc: {:.4f}'.format('attack', attack_loss, attack_acc))
-        take = attack_acc > best_acc if targeted else attack_acc < best_acc   # UA:349-358: strict
+        d = stats.read(len(items))                                        # THE host read of the pass; UA:340-344
+        _log_loss_acc(say, d)
+        take = d['attack_acc'] > best_acc if targeted else d['attack_acc'] < best_acc   # UA:349-358: strict
         if take:
-            best_acc = attack_acc
+            best_acc = d['attack_acc']
             best = table.clone().detach()
-        records.append(dict(epoch=pass_epoch, next_epoch=epoch, views=n_views, test_loss=test_loss, test_acc=test_acc,
-                            attack_loss=attack_loss, attack_acc=attack_acc, test_correct=test_correct, attack_correct=attack_correct,
-                            skipped=skipped, attacked=attacked, completed=completed, deepfool_iters=iters, taken=int(bool(take)),
-                            visits=visits))
+        records.append(dict(d, epoch=pass_epoch, next_epoch=epoch, taken=int(bool(take)), **seen.fields()))
         _uap2d_pass_done(n_pass, table)
         n_pass += 1
     return Uap2dResult(best, table, best_acc, records)

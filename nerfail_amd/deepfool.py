@@ -28,6 +28,40 @@ def _grad(out_scalar, wrt):
     return torch.autograd.grad(out_scalar, wrt, retain_graph=True, create_graph=False)[0]
 
 
+def _bump_and_test(cla, o, target_label, m1):
+    """deepfool.py:53-66: +m1 on the clean class (targeted: on every class but the target), out of place, the first maximum and
+    the break test. Returns (bumped logits, their argmax, done). Stock torch, any device."""
+    bump = torch.zeros_like(cla)
+    if target_label is None:
+        bump[:, o] = m1
+    else:
+        bump[:, :int(target_label)] = m1
+        bump[:, int(target_label) + 1:] = m1
+    cla = cla + bump
+    cla_max_index = torch.max(cla, 1)[1]
+    done = int(cla_max_index) != o if target_label is None else int(cla_max_index) == int(target_label)
+    return cla, cla_max_index, done
+
+
+def _competitors(o, num_classes, target_label):
+    """deepfool.py:68-72: the classes an iteration steps towards."""
+    return [k for k in range(num_classes) if k != o] if target_label is None else [int(target_label)]
+
+
+def _choose(cla, o, ks, m2, nrm, target_label):
+    """deepfool.py:79-96 once the norms `nrm` of grad_k - grad_o are known: (index into ks of the class chosen, the step's scale).
+    Untargeted the first minimum of |f'| / (norm + 1e-4) - the reference's strict `<` scan; a NaN is never chosen, and when
+    nothing can be chosen the scale is 0. Stock torch, any device."""
+    f_prime = (cla[0, ks] - (cla[0, o] + m2)).detach()                                  # deepfool.py:79
+    if target_label is not None:
+        return torch.zeros((), dtype=torch.int64, device=nrm.device), torch.abs(f_prime[0]) / ((nrm[0] ** 2) + 0.0001)   # :92-96
+    value_r = torch.abs(f_prime) / (nrm + 0.0001)                                       # deepfool.py:81
+    value_r = torch.where(torch.isnan(value_r), torch.full_like(value_r, float('inf')), value_r)
+    best = torch.argmin(value_r)
+    scale = torch.abs(f_prime[best]) / ((nrm[best] ** 2) + 0.0001)                      # deepfool.py:86
+    return best, torch.where(torch.isinf(value_r[best]), torch.zeros_like(scale), scale)
+
+
 def deepfool(net_input, e, net, num_classes=8, max_iter=20, target_label: int = None, overshoot: float = 0.02,
              m1: float = 1, m2: float = 30, universal_2d=False):
     if universal_2d:
@@ -52,27 +86,14 @@ def deepfool(net_input, e, net, num_classes=8, max_iter=20, target_label: int = 
         x_out, x_rgba, cla, _, ori_cla = net(spatial_rgb, weight_and_index, ori_img)     # deepfool.py:51
         ori_cla_max_index = torch.max(ori_cla, 1)[1]
         o = int(ori_cla_max_index)
-        bump = torch.zeros_like(cla)                                                    # deepfool.py:53-57 (+m1), out of place
-        if target_label is None:
-            bump[:, o] = m1
-        else:
-            bump[:, :int(target_label)] = m1
-            bump[:, int(target_label) + 1:] = m1
-        cla = cla + bump
-        cla_max_index = torch.max(cla, 1)[1]
-        if (target_label is None) and int(cla_max_index) != o:
-            break
-        if (target_label is not None) and int(cla_max_index) == int(target_label):
+        cla, cla_max_index, done = _bump_and_test(cla, o, target_label, m1)
+        if done:
             break
 
-        if target_label is None:
-            ks = [k for k in range(num_classes) if k != o]
-        else:
-            ks = [int(target_label)]
+        ks = _competitors(o, num_classes, target_label)
         # the multi-RHS pass takes 2..8 logits ([o] + ks): with o >= num_classes all num_classes competitors remain (9 at
         # num_classes = 8), with a single class none does - those cases iterate class by class like the reference
         multi = hasattr(net, 'logit_gradients') and getattr(net, 'deterministic', False) and 2 <= len(ks) + 1 <= 8
-        f_prime = (cla[0, ks] - (cla[0, o] + m2)).detach()                              # deepfool.py:79
         if multi:
             # all class gradients in one pass over the inverted index (K11 multi-RHS), then the step arithmetic in two
             # streaming kernels (K14): ||G_k - G_o||^2 for every k, device-side choice, rot / clamp / alpha restore
@@ -89,15 +110,7 @@ def deepfool(net_input, e, net, num_classes=8, max_iter=20, target_label: int = 
             grads_k = torch.stack([_grad(cla[:, k].sum(), spatial_rgb) for k in ks])
             grad_prime = grads_k - grad_o.unsqueeze(0)                                  # deepfool.py:78 for every k
             nrm = torch.linalg.vector_norm(grad_prime.reshape(len(ks), -1), dim=1)
-        if target_label is None:
-            value_r = torch.abs(f_prime) / (nrm + 0.0001)                               # deepfool.py:81
-            value_r = torch.where(torch.isnan(value_r), torch.full_like(value_r, float('inf')), value_r)
-            best = torch.argmin(value_r)                                                # first minimum = strict `<` scan
-            scale = torch.abs(f_prime[best]) / ((nrm[best] ** 2) + 0.0001)              # deepfool.py:86
-            scale = torch.where(torch.isinf(value_r[best]), torch.zeros_like(scale), scale)   # nothing chosen: dr = 0
-        else:
-            best = torch.zeros((), dtype=torch.int64, device=nrm.device)
-            scale = torch.abs(f_prime[0]) / ((nrm[0] ** 2) + 0.0001)                    # deepfool.py:92-96
+        best, scale = _choose(cla, o, ks, m2, nrm, target_label)
         if multi:
             rot = _lib.f32c(rot)
             new_s = torch.empty_like(spatial_rgb_0)
@@ -116,6 +129,46 @@ def deepfool(net_input, e, net, num_classes=8, max_iter=20, target_label: int = 
     spatial_rgb = spatial_rgb.detach()
     rot = (spatial_rgb - spatial_rgb_0).detach()
     return rot, loop_i, ori_cla_max_index, cla_max_index, spatial_rgb
+
+
+def _target_word(target_label, C):
+    """The gate's target word: -1 untargeted, else the class; None when it names none of the C classes (the call falls through)."""
+    target = -1 if target_label is None else int(target_label)
+    return target if -1 <= target < C else None
+
+
+class _NativeCall:
+    """What deepfool_native and deepfool_2d_native allocate once per call and do alike: the gradient rows [o] + competitors,
+    record / trace / rot / out, the gate with the iteration's one host read, the six-value result. `r_0`: the table the call
+    started from (a device copy of its own); `o`: the clean argmax; `target`: _target_word's."""
+
+    def __init__(self, r_0, C, o, target, max_iter):
+        self.lib = _lib.load()
+        self.r_0, self.C, self.o, self.target = r_0, C, o, target
+        self.rows = [o] + _competitors(o, C, None if target < 0 else target)
+        self.record = torch.zeros((_lib.DEEPFOOL_RECORD_WORDS,), dtype=torch.int32, device=r_0.device)
+        self.trace = torch.full((max(int(max_iter), 1),), -1, dtype=torch.int32, device=r_0.device)
+        self.rot = torch.zeros_like(r_0)
+        self.out = torch.empty_like(r_0)
+        self.loop_i, self.arg = 0, None
+
+    def gate(self, cla, m1, m2):
+        """nerfail_deepfool_gate on this iteration's logits, then the iteration's one host read: done?"""
+        cla_c = _lib.f32c(cla)
+        _lib.check(self.lib.nerfail_deepfool_gate(_lib.dev(cla_c), self.C, self.o, self.target, float(m1), float(m2), _lib.dev(self.record),
+                                                  _lib.stream()))
+        done, self.arg = self.record[:2].tolist()
+        return done
+
+    def trace_slot(self):
+        return self.trace[self.loop_i:self.loop_i + 1]
+
+    def result(self, ori_cla_max_index, cla):
+        """`cla`: the logits whose argmax is reported when no gate ran (max_iter < 1)."""
+        cla_max_index = torch.max(cla, 1)[1] if self.arg is None else torch.full((1,), self.arg, dtype=torch.int64, device=self.r_0.device)
+        r = self.out if self.loop_i > 0 else self.r_0.clone()
+        classes = self.trace[:self.loop_i].tolist() if self.loop_i > 0 else []
+        return (r - self.r_0).detach(), self.loop_i, ori_cla_max_index, cla_max_index, r.detach(), classes
 
 
 def _native_applies(net, num_classes, universal_2d):
@@ -162,40 +215,26 @@ def deepfool_native(net_input, e, net, num_classes=8, max_iter=20, target_label:
     s = spatial_rgb_0.clone().requires_grad_(True)
     x_out, x_rgba, cla, _, ori_cla = fwd(s)                                             # deepfool.py:33
     C = int(cla.shape[1])
-    target = -1 if target_label is None else int(target_label)
-    if cla.shape[0] != 1 or C != int(num_classes) or not -1 <= target < C:
+    target = _target_word(target_label, C)
+    if cla.shape[0] != 1 or C != int(num_classes) or target is None:
         return mirror()
     ori_cla_max_index = torch.max(ori_cla, 1)[1]
-    o = int(ori_cla_max_index)                                                          # THE read of the call
-    arg = None
-    lib = _lib.load()
-    ks = [k for k in range(C) if k != o] if target < 0 else [target]
-    n_rhs, n = len(ks) + 1, spatial_rgb_0.numel() // 4
-    nb = lib.nerfail_deepfool_step_scratch_bytes(n_rhs, n)
+    call = _NativeCall(spatial_rgb_0, C, int(ori_cla_max_index), target, max_iter)     # THE read of the call
+    n_rhs, n = len(call.rows), spatial_rgb_0.numel() // 4
+    nb = call.lib.nerfail_deepfool_step_scratch_bytes(n_rhs, n)
     scratch = torch.empty((nb // 8,), dtype=torch.float64, device=dev)
-    record = torch.zeros((_lib.DEEPFOOL_RECORD_WORDS,), dtype=torch.int32, device=dev)
-    trace = torch.full((max(int(max_iter), 1),), -1, dtype=torch.int32, device=dev)
-    rot = torch.zeros_like(spatial_rgb_0)
-    out = torch.empty_like(spatial_rgb_0)
-    loop_i = 0
-    while loop_i < max_iter:
-        if loop_i > 0:
-            s = out.detach().requires_grad_(True)
+    while call.loop_i < max_iter:
+        if call.loop_i > 0:
+            s = call.out.detach().requires_grad_(True)
             x_out, x_rgba, cla, _, ori_cla = fwd(s)                                     # deepfool.py:51
-        cla_c = _lib.f32c(cla)
-        _lib.check(lib.nerfail_deepfool_gate(_lib.dev(cla_c), C, o, target, float(m1), float(m2), _lib.dev(record), _lib.stream()))
-        done, arg = record[:2].tolist()                                                 # the iteration's one host read
-        if done:
+        if call.gate(cla, m1, m2):
             break
-        G = net.logit_gradients(s, None, x_out, x_rgba, cla, [o] + ks)
-        _lib.check(lib.nerfail_deepfool_step(_lib.dev(G), n_rhs, n, _lib.dev(record), _lib.c_p(scratch.data_ptr()), nb, float(overshoot),
-                                             _lib.dev(spatial_rgb_0), _lib.dev(rot), _lib.dev(out), _lib.dev(trace[loop_i:loop_i + 1]),
-                                             _lib.stream()))
-        loop_i += 1
-    cla_max_index = torch.max(cla, 1)[1] if arg is None else torch.full((1,), arg, dtype=torch.int64, device=dev)
-    spatial_rgb = out if loop_i > 0 else spatial_rgb_0.clone()
-    classes = trace[:loop_i].tolist() if loop_i > 0 else []
-    return (spatial_rgb - spatial_rgb_0).detach(), loop_i, ori_cla_max_index, cla_max_index, spatial_rgb.detach(), classes
+        G = net.logit_gradients(s, None, x_out, x_rgba, cla, call.rows)
+        _lib.check(call.lib.nerfail_deepfool_step(_lib.dev(G), n_rhs, n, _lib.dev(call.record), _lib.c_p(scratch.data_ptr()), nb,
+                                                  float(overshoot), _lib.dev(spatial_rgb_0), _lib.dev(call.rot), _lib.dev(call.out),
+                                                  _lib.dev(call.trace_slot()), _lib.stream()))
+        call.loop_i += 1
+    return call.result(ori_cla_max_index, cla)
 
 
 # ---------------------------------------------------------------------------------------------- the 2-D baseline's DeepFool (universal_2d)
@@ -222,32 +261,14 @@ def deepfool_2d(net_input, e, net, num_classes=8, max_iter=20, target_label: int
         _, _, cla, _, ori_cla = net(r, ori_img)                                         # deepfool.py:49
         ori_cla_max_index = torch.max(ori_cla, 1)[1]
         o = int(ori_cla_max_index)
-        bump = torch.zeros_like(cla)                                                    # deepfool.py:53-57 (+m1), out of place
-        if target_label is None:
-            bump[:, o] = m1
-        else:
-            bump[:, :int(target_label)] = m1
-            bump[:, int(target_label) + 1:] = m1
-        cla = cla + bump
-        cla_max_index = torch.max(cla, 1)[1]
-        if (target_label is None) and int(cla_max_index) != o:
+        cla, cla_max_index, done = _bump_and_test(cla, o, target_label, m1)
+        if done:
             break
-        if (target_label is not None) and int(cla_max_index) == int(target_label):
-            break
-        ks = [k for k in range(num_classes) if k != o] if target_label is None else [int(target_label)]
-        f_prime = (cla[0, ks] - (cla[0, o] + m2)).detach()                              # deepfool.py:79
+        ks = _competitors(o, num_classes, target_label)
         grad_o = _grad(cla[:, o].sum(), r)
         grad_prime = torch.stack([_grad(cla[:, k].sum(), r) for k in ks]) - grad_o.unsqueeze(0)   # deepfool.py:80 for every k
         nrm = torch.linalg.vector_norm(grad_prime.reshape(len(ks), -1), dim=1)
-        if target_label is None:
-            value_r = torch.abs(f_prime) / (nrm + 0.0001)                               # deepfool.py:82
-            value_r = torch.where(torch.isnan(value_r), torch.full_like(value_r, float('inf')), value_r)
-            best = torch.argmin(value_r)                                                # first minimum = strict `<` scan
-            scale = torch.abs(f_prime[best]) / ((nrm[best] ** 2) + 0.0001)              # deepfool.py:85
-            scale = torch.where(torch.isinf(value_r[best]), torch.zeros_like(scale), scale)   # nothing chosen: dr = 0
-        else:
-            best = torch.zeros((), dtype=torch.int64, device=nrm.device)
-            scale = torch.abs(f_prime[0]) / ((nrm[0] ** 2) + 0.0001)                    # deepfool.py:92-96
+        best, scale = _choose(cla, o, ks, m2, nrm, target_label)
         rot = (rot + scale * grad_prime[best]).detach()
         r = torch.clamp((r_0 + (overshoot * rot)).detach(), -255, 255)                  # deepfool.py:100-101, all three channels
         loop_i += 1
@@ -314,8 +335,8 @@ def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_lab
     else:
         store = images
     C = int(num_classes)
-    target = -1 if target_label is None else int(target_label)
-    if not -1 <= target < C:
+    target = _target_word(target_label, C)
+    if target is None:
         return mirror()
     model, name = net.model, net.model_name
     cnn = isinstance(model, MyCNN) and name == "my_model"
@@ -330,21 +351,13 @@ def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_lab
     if clean_logits.dim() != 2 or clean_logits.shape[0] != 1 or clean_logits.shape[1] != C:
         return mirror()
     ori_cla_max_index = torch.max(clean_logits, 1)[1]
-    o = int(ori_cla_max_index)                                                          # THE read of the call
-    ks = [k for k in range(C) if k != o] if target < 0 else [target]
-    rows = [o] + ks
-    n_rhs = len(rows)
-    lib = _lib.load()
-    scratch, _ = ops.uap2d_step_scratch(n_rhs, P, dev)
-    record = torch.zeros((_lib.DEEPFOOL_RECORD_WORDS,), dtype=torch.int32, device=dev)
-    trace = torch.full((max(int(max_iter), 1),), -1, dtype=torch.int32, device=dev)
-    rot = torch.zeros_like(r_0)
-    out = torch.empty_like(r_0)
-    onehot = torch.zeros((n_rhs, 1, C), dtype=torch.float32, device=dev)
-    onehot[torch.arange(n_rhs, device=dev), 0, torch.tensor(rows, device=dev)] = 1.
-    cur, arg, cla = r_0, None, None
-    loop_i = 0
-    while loop_i < max_iter:
+    call = _NativeCall(r_0, C, int(ori_cla_max_index), target, max_iter)               # THE read of the call
+    rows = call.rows
+    scratch, _ = ops.uap2d_step_scratch(len(rows), P, dev)
+    onehot = torch.zeros((len(rows), 1, C), dtype=torch.float32, device=dev)
+    onehot[torch.arange(len(rows), device=dev), 0, torch.tensor(rows, device=dev)] = 1.
+    cur, cla = r_0, None
+    while call.loop_i < max_iter:
         with torch.no_grad():
             _, cls_in, mask = ops.u2d_fwd(store, idx, cur, False, True, True)           # deepfool.py:49 up to the classifier
         if cnn:
@@ -355,26 +368,18 @@ def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_lab
             cla = model(u2d_resize(cls_in, name))
             if cla.dim() != 2 or cla.shape[0] != 1 or cla.shape[1] != C:
                 return mirror()
-        cla_c = _lib.f32c(cla)
-        _lib.check(lib.nerfail_deepfool_gate(_lib.dev(cla_c), C, o, target, float(m1), float(m2), _lib.dev(record), _lib.stream()))
-        done, arg = record[:2].tolist()                                                 # the iteration's one host read
-        if done:
+        if call.gate(cla, m1, m2):
             break
         if cnn:
             with torch.no_grad():
                 G = ops.cnn_bwd_data_multi(model.packed(), ws, pool, onehot, hw[0], hw[1])
         else:
             G = _lib.f32c(torch.stack([torch.autograd.grad(cla[0, k], cls_in, retain_graph=True)[0] for k in rows]))
-        ops.uap2d_step(G, mask.view(-1), record, scratch, overshoot, r_0, rot, out, trace[loop_i:loop_i + 1])
-        cur = out
-        loop_i += 1
-    if arg is None:                                                                     # max_iter < 1: deepfool.py:31's forward alone
+        ops.uap2d_step(G, mask.view(-1), call.record, scratch, overshoot, r_0, call.rot, call.out, call.trace_slot())
+        cur = call.out
+        call.loop_i += 1
+    if call.arg is None:                                                                # max_iter < 1: deepfool.py:31's forward alone
         with torch.no_grad():
             _, cls_in, _ = ops.u2d_fwd(store, idx, cur, False, True, False)
             cla = model(u2d_resize(cls_in, name))
-        cla_max_index = torch.max(cla, 1)[1]
-    else:
-        cla_max_index = torch.full((1,), arg, dtype=torch.int64, device=dev)
-    r = out if loop_i > 0 else r_0.clone()
-    classes = trace[:loop_i].tolist() if loop_i > 0 else []
-    return (r - r_0).detach(), loop_i, ori_cla_max_index, cla_max_index, r.detach(), classes
+    return call.result(ori_cla_max_index, cla)
