@@ -994,6 +994,45 @@ int nerfail_cls_input_resize_fwd(const float* src, int layout, int B, int H, int
 int nerfail_cls_input_resize_bwd(const float* g, int R, const float* src, int layout, int B, int H, int W, int oh, int ow,
                                  const nerfail_resize_axis* ty, const nerfail_resize_axis* tx, float* gsrc, void* stream);
 
+/* ------------------------------------------------------------------ foreground-only scene maps (fg revision 1) -- */
+
+/* Scene maps over the pixels the attacks read. gauss_net writes 0 to x_rgba and takes no gradient wherever the view's registered
+ * BGRA image has alpha <= 0, so a view's map matters only on its FOREGROUND, the pixels with alpha > 0: these entry points list
+ * them, make rays for the list and search for the list. Like the nine sections before it this one only ADDS entry points:
+ * NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays 15, every other revision stays 1, and the additions are announced by
+ * nerfail_fg_revision() = 1. nerfail_ray_gen and nerfail_knn8_grid_weights[_view] are unchanged. No allocation on the device, no
+ * synchronisation, no float atomics; the same bits on every run.
+ *
+ * nerfail_fg_pixel_list: bgra = one uint8 BGRA view of n_pixels pixels (4-byte aligned; 1 <= n_pixels < 2^31). Writes
+ * list[0..n) = the indices row * W + col of the pixels with A > 0, strictly ascending, and *count = n, both on the device (list
+ * holds n_pixels int32; elements from n on are not written). An ordered stream compaction in three launches - ballot and popcount
+ * per wave into one count per workgroup, an exclusive scan of the counts, the write - whose order does not depend on scheduling.
+ * workspace: nerfail_fg_pixel_list_workspace_bytes(n_pixels) bytes (0 for a count outside the range), 4-byte aligned; contents
+ * unspecified on return.
+ *
+ * nerfail_ray_gen_list: rays[n,11]; row j is bit for bit the row nerfail_ray_gen writes for pixel pix[j] of the H x W view (one
+ * device function behind both). n = 0 is valid and launches nothing. H * W < 2^31.
+ *
+ * nerfail_knn8_grid_weights_list: nerfail_knn8_grid_weights over the n compact queries (64 consecutive queries per wave), with
+ * query j's weights and indices written to row pix[j] of the two planes of weight_and_index[2, n_pixels, 8] (16-byte aligned). The
+ * same call first zeroes ALL of weight_and_index on the same stream (+0: weight 0, index 0), so every row not named by pix is zero
+ * bits. A listed row is bit for bit the row nerfail_knn8_grid_weights[_view] writes for that query. sum_d2 (device double, may be
+ * NULL): the fixed-order double fold over the 8 n listed distances only. n = 0 is valid: the map is all zero, *sum_d2 = 0, no search
+ * is launched (queries, pix and workspace may then be NULL). workspace: nerfail_knn8_grid_weights_workspace_bytes(n) bytes, 8-byte
+ * aligned, needed when sum_d2 is given. The VALUES of pix are the caller's contract (distinct, in [0, n_pixels) - a list made by
+ * nerfail_fg_pixel_list); a value outside [0, n_pixels) stores nothing. Refused with NERFAIL_EINVAL before any launch: n_pixels
+ * outside [1, 2^31), n outside [0, n_pixels], n_points outside [8, 2^24), c not > 0, a NULL or misaligned pointer, a workspace or
+ * grid workspace that is too small, a point count that contradicts the grid built in grid_workspace. */
+int nerfail_fg_revision(void);
+size_t nerfail_fg_pixel_list_workspace_bytes(int64_t n_pixels);
+int nerfail_fg_pixel_list(const uint8_t* bgra, int64_t n_pixels, int32_t* list, int32_t* count, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int nerfail_ray_gen_list(int H, int W, const float* K4_host, const float* c2w_host, float near_, float far_, const int32_t* pix,
+                         int64_t n, float* rays, void* stream);
+int nerfail_knn8_grid_weights_list(const float* queries, int64_t n, const int32_t* pix, int64_t n_pixels, int64_t n_points, float c,
+                                   float* weight_and_index, double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ victim classifier (MyCNN) -- */
 
 /* The MyCNN classifier of model/MyModel.py:5-52 (ABI 9): seven stages of 3x3 valid conv + bias + ReLU + 2x2 floor max-pool

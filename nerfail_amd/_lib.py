@@ -21,6 +21,7 @@ U2D_REVISION = 1                         # nerfail_u2d_revision: the IGSM-2D bas
 UAP2D_REVISION = 1                       # nerfail_uap2d_revision: the UAP-2D baseline's DeepFool step and projection (attack.uap_2d)
 POISON_REVISION = 1                      # nerfail_poison_revision: the export -> training-target hand-off (retrain.PoisonedTrainSet)
 RESIZE_REVISION = 1                      # nerfail_resize_revision: the classifier-input resize and its adjoint (_resize.classifier_input)
+FG_REVISION = 1                          # nerfail_fg_revision: pixel list, list rays and list search of foreground-only scene maps (scene)
 RESIZE_MAX_TAPS = 16                     # NERFAIL_RESIZE_MAX_TAPS
 UAP2D_NORM_TERMS = 24                   # NERFAIL_UAP2D_NORM_TERMS: float32 terms per lane of nerfail_uap2d_step's norms
 DEEPFOOL_MAX_COMPETITORS = 8             # NERFAIL_DEEPFOOL_MAX_COMPETITORS
@@ -209,6 +210,11 @@ SIGNATURES = {
     'nerfail_resize_tiles': (c_i, [c_i, c_i, c_i, c_i, c_p, c_p]),
     'nerfail_cls_input_resize_fwd': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     'nerfail_cls_input_resize_bwd': (c_i, [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    'nerfail_fg_revision': (c_i, []),
+    'nerfail_fg_pixel_list_workspace_bytes': (ctypes.c_size_t, [c_i64]),
+    'nerfail_fg_pixel_list': (c_i, [c_p, c_i64, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    'nerfail_ray_gen_list': (c_i, [c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_i64, c_p, c_p]),
+    'nerfail_knn8_grid_weights_list': (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_f, c_p, c_p, c_p, ctypes.c_size_t, c_p, ctypes.c_size_t, c_p]),
     'nerfail_cnn_packed_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_pack': (c_i, [c_p, c_i, c_p, c_p]),
     'nerfail_cnn_workspace_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
@@ -291,6 +297,9 @@ def load():
     if lib.nerfail_resize_revision() != RESIZE_REVISION:
         raise RuntimeError('nerfail_amd: classifier-input resize revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_resize_revision(), RESIZE_REVISION))
+    if lib.nerfail_fg_revision() != FG_REVISION:
+        raise RuntimeError('nerfail_amd: foreground scene-maps revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_fg_revision(), FG_REVISION))
     _lib = lib
     return lib
 

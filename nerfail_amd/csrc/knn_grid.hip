@@ -19,6 +19,7 @@
 // where the brute-force scan computes 1.92 M.
 #include "common.h"
 #include "gauss_weight.h"
+#include "knn_grid_list.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -224,11 +225,14 @@ constexpr int kMinGroup = 8;
 // the kernel once a query's eight keys are final: `dist` receives K9's weights (gauss_weights8 of the distances, gauss_weight.h)
 // instead of the distances, `idx_f` the indices as float as before - the two planes of the attack's [2,P,8] map - and, when
 // `d2_part` is set, slot blockIdx.x of it the wave's sum of d * d over its valid queries (double; see the epilogue).
-template <bool WEIGHTS>
+// LIST (knn_grid_list.h, behind nerfail_knn8_grid_weights_list): the queries are a compact list in the flat form and query j's row
+// goes to row pix[j] of `dist` / `idx_f` (n_rows rows each; a value outside [0, n_rows) stores nothing). Only the store differs.
+template <bool WEIGHTS, bool LIST = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void knn8_grid_kernel(const float* __restrict__ queries, long nq, int view_h, int view_w, const Grid* __restrict__ gp,
                                                         const float4* __restrict__ sorted, const int* __restrict__ cell_start,
                                                         const int* __restrict__ coarse_cnt, const int* __restrict__ super_cnt, float* __restrict__ dist, float* __restrict__ idx_f,
-                                                        int* __restrict__ idx_i, unsigned long long* __restrict__ stats, float gauss_c, double* __restrict__ d2_part) {
+                                                        int* __restrict__ idx_i, unsigned long long* __restrict__ stats, float gauss_c, double* __restrict__ d2_part,
+                                                        const int32_t* __restrict__ pix, long n_rows) {
     // One wave per workgroup. view_w > 0: the queries are the [view_h, view_w] pixels of a view and a wave takes an 8 x 8 pixel
     // TILE (0.014 scene units across on a lego view, a third of a cell: the 64 searches share nearly all their candidates);
     // view_w == 0: 64 consecutive queries. Lanes past the end repeat a valid query of the wave (no early return: the search
@@ -627,6 +631,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void kn
 #pragma unroll
         for (int k = 0; k < 8; ++k) d[k] = w[k];
     }
+    if constexpr (LIST) {
+        qi = (long)pix[qi];
+        if ((unsigned long)qi >= (unsigned long)n_rows) return;
+    }
     float4* __restrict__ od = reinterpret_cast<float4*>(dist + 8 * qi);
     od[0] = make_float4(d[0], d[1], d[2], d[3]);
     od[1] = make_float4(d[4], d[5], d[6], d[7]);
@@ -808,7 +816,7 @@ static int grid_search(const float* queries, int64_t n_queries, int view_h, int 
     NF_REQUIRE(waves < (1L << 31), "too many queries for one launch");
     knn8_grid_kernel<false><<<dim3((unsigned)waves), dim3(64), 0, as_stream(stream)>>>(
         queries, n_queries, view_h, view_w, w.gp, w.sorted, w.cell_start, w.coarse_cnt, w.super_cnt, dist, idx_f32, idx_i32,
-        g_knn_stats, 0.f, nullptr);
+        g_knn_stats, 0.f, nullptr, nullptr, 0);
     NF_LAUNCHED("knn8_grid_kernel");
     return NERFAIL_OK;
 }
@@ -875,7 +883,7 @@ static int grid_weights(const float* queries, int64_t n_queries, int view_h, int
     double* part = sum_d2 != nullptr ? (double*)workspace : nullptr;
     knn8_grid_kernel<true><<<dim3((unsigned)waves), dim3(64), 0, as_stream(stream)>>>(
         queries, n_queries, view_h, view_w, w.gp, w.sorted, w.cell_start, w.coarse_cnt, w.super_cnt, weight_and_index,
-        weight_and_index + 8 * n_queries, nullptr, g_knn_stats, c, part);
+        weight_and_index + 8 * n_queries, nullptr, g_knn_stats, c, part, nullptr, 0);
     NF_LAUNCHED("knn8_grid_kernel<weights>");
     if (sum_d2 != nullptr) {
         knn8_d2_fold_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(part, waves, sum_d2);
@@ -898,3 +906,39 @@ extern "C" int nerfail_knn8_grid_weights_view(const float* queries, int height, 
     return grid_weights(queries, (int64_t)height * width, height, width, n_points, c, weight_and_index, sum_d2, grid_workspace,
                         grid_workspace_bytes, workspace, workspace_bytes, stream);
 }
+
+// ------------------------------------------------------------------------------------------ fg revision 1 (knn_grid_list.h)
+// The search half of nerfail_knn8_grid_weights_list (fg_scene.hip): the same kernel over a compact query list, rows scattered.
+namespace nerfail {
+
+int knn8_grid_list_check(int64_t n, int64_t n_points, const void* grid_workspace, size_t grid_workspace_bytes) {
+    NF_REQUIRE(grid_workspace != nullptr && grid_workspace_bytes >= nerfail_knn8_grid_workspace_bytes(n_points),
+               "grid workspace too small (nerfail_knn8_grid_workspace_bytes)");
+    const int64_t built = built_for(grid_workspace);
+    NF_REQUIRE(built < 0 || built == n_points, "n_points does not match the grid built in this workspace (nerfail_knn8_grid_build)");
+    NF_REQUIRE((n + 63) / 64 < ((int64_t)1 << 31), "too many queries for one launch");
+    return NERFAIL_OK;
+}
+
+int knn8_grid_weights_list_launch(const float* queries, int64_t n, const int32_t* pix, int64_t n_rows, int64_t n_points, float c,
+                                  float* weight_and_index, double* sum_d2, const void* grid_workspace, size_t grid_workspace_bytes,
+                                  void* workspace, hipStream_t s) {
+    const int rc = knn8_grid_list_check(n, n_points, grid_workspace, grid_workspace_bytes);
+    if (rc != NERFAIL_OK) return rc;
+    const long waves = (long)((n + 63) / 64);
+    double* part = sum_d2 != nullptr ? (double*)workspace : nullptr;
+    if (waves > 0) {
+        const GridWs w = carve(const_cast<void*>(grid_workspace), n_points);
+        knn8_grid_kernel<true, true><<<dim3((unsigned)waves), dim3(64), 0, s>>>(
+            queries, n, 0, 0, w.gp, w.sorted, w.cell_start, w.coarse_cnt, w.super_cnt, weight_and_index, weight_and_index + 8 * n_rows,
+            nullptr, g_knn_stats, c, part, pix, n_rows);
+        NF_LAUNCHED("knn8_grid_kernel<weights, list>");
+    }
+    if (sum_d2 != nullptr) {                                  // (no partials: the fold writes 0)
+        knn8_d2_fold_kernel<<<dim3(1), dim3(64), 0, s>>>(part, waves, sum_d2);
+        NF_LAUNCHED("knn8_d2_fold_kernel");
+    }
+    return NERFAIL_OK;
+}
+
+}  // namespace nerfail

@@ -5,35 +5,9 @@
 // K1b: the training batch (RN:690-742, RN:744-773) - the index shuffle and rays + target colours of one batch from resident data.
 #include "common.h"
 #include "index_shuffle.h"
+#include "ray_pixel.h"
 
 namespace nerfail {
-
-struct Cam {
-    float fx, fy, cx, cy;
-    float c2w[12];
-};
-
-// dirs = ((i-cx)/fx, -(j-cy)/fy, -1); rays_d[a] = (dirs0*R[a][0] + dirs1*R[a][1]) + dirs2*R[a][2]
-// (torch.sum over 3 products, no FMA), rays_o = c2w[:,3].
-__device__ __forceinline__ void pixel_ray(const Cam& c, int col, int row, float* o, float* d) {
-    const float d0 = __fdiv_rn(__fsub_rn((float)col, c.cx), c.fx);
-    const float d1 = -__fdiv_rn(__fsub_rn((float)row, c.cy), c.fy);
-    const float d2 = -1.0f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float p0 = __fmul_rn(d0, c.c2w[4 * a + 0]);
-        const float p1 = __fmul_rn(d1, c.c2w[4 * a + 1]);
-        const float p2 = __fmul_rn(d2, c.c2w[4 * a + 2]);
-        d[a] = __fadd_rn(__fadd_rn(p0, p1), p2);
-        o[a] = c.c2w[4 * a + 3];
-    }
-}
-
-__device__ __forceinline__ void viewdir_of(const float* d, float* v) {
-    const float n = sqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) v[a] = __fdiv_rn(d[a], n);
-}
 
 __global__ void get_rays_kernel(Cam c, int H, int W, float* __restrict__ rays_o, float* __restrict__ rays_d) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -45,15 +19,6 @@ __global__ void get_rays_kernel(Cam c, int H, int W, float* __restrict__ rays_o,
         rays_o[3 * p + a] = o[a];
         rays_d[3 * p + a] = d[a];
     }
-}
-
-__device__ __forceinline__ void store_ray(float* __restrict__ r, const float* o, const float* d, float near_, float far_) {
-    float v[3];
-    viewdir_of(d, v);
-    r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
-    r[3] = d[0]; r[4] = d[1]; r[5] = d[2];
-    r[6] = near_; r[7] = far_;
-    r[8] = v[0]; r[9] = v[1]; r[10] = v[2];
 }
 
 __global__ void pack_rays_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, long n,
@@ -148,13 +113,6 @@ __global__ void sample_coarse_kernel(const float* __restrict__ rays, long n_rays
 #pragma unroll
         for (int a = 0; a < 3; ++a) pts[3 * g + a] = mul_add_rn(ray[3 + a], z, ray[a]);
     }
-}
-
-static inline bool fill_cam(Cam& c, const float* K4, const float* c2w) {
-    if (K4 == nullptr || c2w == nullptr) return false;
-    c.fx = K4[0]; c.fy = K4[1]; c.cx = K4[2]; c.cy = K4[3];
-    for (int i = 0; i < 12; ++i) c.c2w[i] = c2w[i];
-    return true;
 }
 
 }  // namespace nerfail

@@ -32,6 +32,12 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     return _rn._render(H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, True, kwargs)
 
 
+def render_pixels(H, W, K, pix, chunk=1024 * 32, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False, **kwargs):
+    """render() for the pixels `pix` (device int32 [n], row * W + col) of the view c2w only -> [rgb_map, disp_map, acc_map, pts_max,
+    extras], each [n, ...], compact, in list order: row j is bit for bit row pix[j] of the full render (run_nerf._render_pixels)."""
+    return _rn._render_pixels(H, W, K, pix, chunk, c2w, ndc, near, far, use_viewdirs, True, kwargs)
+
+
 def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0):
     """NC:138-178: per view render + (optional) PNG and the pts_max .npy the 8-NN build consumes."""
     H, W, focal = hwf

@@ -48,6 +48,29 @@ def _(K, c2w, anchor, H, W, near, far, pix_begin, pix_count):
     return anchor.new_empty((pix_count, _lib.RAY_FLOATS), dtype=torch.float32)
 
 
+@custom_op(NS + '::ray_gen_list', mutates_args=(), device_types='cuda')
+def ray_gen_list(K: Tensor, c2w: Tensor, pix: Tensor, H: int, W: int, near: float, far: float) -> Tensor:
+    """Packed rays [n, 11] of the pixels `pix` (device int32 [n], values row * W + col) of an H x W view: row j is bit for bit
+    ray_gen's row for pixel pix[j] (nerfail_ray_gen_list, fg revision 1). K and c2w as in ray_gen. Not differentiable: data."""
+    k = K.detach().to('cpu', torch.float64)
+    c = c2w.detach().to('cpu', torch.float32)[:3, :4].reshape(-1).tolist()
+    if pix.dtype != torch.int32 or pix.dim() != 1:
+        raise TypeError('ray_gen_list: pix must be int32 [n] (got %s %s)' % (pix.dtype, tuple(pix.shape)))
+    n = pix.shape[0]
+    rays = torch.empty((n, _lib.RAY_FLOATS), dtype=torch.float32, device=pix.device)
+    _chk(_lib.load().nerfail_ray_gen_list(H, W, _lib.host_floats([k[0, 0], k[1, 1], k[0, 2], k[1, 2]]), _lib.host_floats(c), near, far,
+                                          _lib.dev(pix, 'pix'), n, _lib.dev(rays), _s()))
+    return rays
+
+
+@ray_gen_list.register_fake
+def _(K, c2w, pix, H, W, near, far):
+    return pix.new_empty((pix.shape[0], _lib.RAY_FLOATS), dtype=torch.float32)
+
+
+FG_OPS = ('ray_gen_list',)
+
+
 # ----------------------------------------------------------------------------------------------- K1b training batch (RN:690-773)
 def _u64(key):
     """The dispatcher's int is a signed 64-bit value: keys are taken modulo 2^64 (pass the two's complement of one >= 2^63)."""
@@ -250,6 +273,36 @@ def knn8_weights_into(queries, n_points, c, grid_ws, grid_bytes, out, sum_d2):
     else:
         _chk(lib.nerfail_knn8_grid_weights(_lib.dev(queries, 'queries'), Q, n_points, c, _lib.dev(out), d2, _lib.dev(grid_ws), grid_bytes,
                                            _lib.c_p(ws.data_ptr()), nb, _s()))
+
+
+def fg_pixel_list(image):
+    """nerfail_fg_pixel_list: uint8 BGRA [H,W,4] on the device -> (list int32 [H*W], count int32 [1]), both on the device;
+    list[:count] are the pixels with alpha > 0, ascending. No host read."""
+    lib = _lib.load()
+    P = image.numel() // 4
+    if image.dtype != torch.uint8 or image.shape[-1] != 4 or P == 0:
+        raise TypeError('fg_pixel_list: image must be uint8 BGRA [H,W,4] (got %s %s)' % (image.dtype, tuple(image.shape)))
+    nb = lib.nerfail_fg_pixel_list_workspace_bytes(P)
+    ws = torch.empty((max(nb, 4) // 4,), dtype=torch.int32, device=image.device)
+    lst = torch.empty((P,), dtype=torch.int32, device=image.device)
+    count = torch.empty((1,), dtype=torch.int32, device=image.device)
+    _chk(lib.nerfail_fg_pixel_list(_lib.dev(image, 'image'), P, _lib.dev(lst), _lib.dev(count), _lib.dev(ws), nb, _s()))
+    return lst, count
+
+
+def knn8_weights_list_into(queries, pix, n_points, c, grid_ws, grid_bytes, out, sum_d2):
+    """nerfail_knn8_grid_weights_list over a BUILT grid: `out` [2,...,8] (P = out.numel() // 16 rows per plane) is zeroed, row
+    pix[j] of both planes receives query j's weights and indices, the device double `sum_d2` the fold over the listed distances."""
+    lib = _lib.load()
+    n = pix.shape[0]
+    if queries.numel() != 3 * n or pix.dtype != torch.int32:
+        raise TypeError('knn8_weights_list_into: queries [n,3] and pix int32 [n] must agree')
+    nb = lib.nerfail_knn8_grid_weights_workspace_bytes(n)
+    ws = torch.empty((max(nb, 8) // 8,), dtype=torch.float64, device=out.device)
+    d2 = _lib.c_p(sum_d2.data_ptr()) if sum_d2 is not None else None
+    _chk(lib.nerfail_knn8_grid_weights_list(_lib.dev(queries, 'queries') if n else None, n, _lib.dev(pix, 'pix') if n else None,
+                                            out.numel() // 16, n_points, c, _lib.dev(out), d2, _lib.dev(grid_ws), grid_bytes,
+                                            _lib.c_p(ws.data_ptr()), nb, _s()))
 
 
 @custom_op(NS + '::knn8_weights', mutates_args=(), device_types='cuda')

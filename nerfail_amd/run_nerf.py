@@ -110,6 +110,35 @@ def ray_gen(H, W, K, c2w, near, far, pix_begin=0, pix_count=None):
     return rays
 
 
+def ray_gen_list(H, W, K, c2w, near, far, pix):
+    """Packed rays [n, 11] of the listed pixels (device int32 [n], row * W + col): row j is ray_gen's row for pixel pix[j]."""
+    from . import ops  # noqa: F401  (registers torch.ops.nerfail_mi.ray_gen_list)
+    pix = torch.as_tensor(pix, dtype=torch.int32, device=_cuda()).contiguous()
+    return torch.ops.nerfail_mi.ray_gen_list(torch.as_tensor(np.asarray(K) if not isinstance(K, torch.Tensor) else K), torch.as_tensor(c2w), pix, int(H), int(W), float(near), float(far))
+
+
+def _render_pixels(H, W, K, pix, chunk, c2w, ndc, near, far, use_viewdirs, want_pts_max, kwargs):
+    """_render over a pixel list: every value [n, ...], compact, in list order. Only the ray source differs - batchify_rays and
+    render_rays are the ones of the full render, and no kernel of theirs looks at a ray's position in its launch, so row j is
+    bit for bit row pix[j] of the full render."""
+    if ndc:
+        raise NotImplementedError('ndc=True is LLFF-only (RN:112-114); the blender configs pass ndc=False')
+    if not use_viewdirs:
+        raise NotImplementedError('HIP path implements use_viewdirs=True (all configs/*.txt)')
+    rays_flat = ray_gen_list(H, W, K, c2w, near, far, pix)
+    k_extract = ['rgb_map', 'disp_map', 'acc_map'] + (['pts_max'] if want_pts_max else [])
+    if rays_flat.shape[0] == 0:                          # an all-background view: nothing to render
+        z = rays_flat.new_empty((0, 3))
+        return [z, z[:, 0], z[:, 0]] + ([z] if want_pts_max else []) + [{}]
+    all_ret = batchify_rays(rays_flat, chunk, want_pts_max=want_pts_max, **kwargs)
+    return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
+
+
+def render_pixels(H, W, K, pix, chunk=1024 * 32, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False, **kwargs):
+    """render() for the pixels `pix` (device int32 [n]) of the view c2w only -> [rgb_map, disp_map, acc_map, extras], each [n, ...]."""
+    return _render_pixels(H, W, K, pix, chunk, c2w, ndc, near, far, use_viewdirs, False, kwargs)
+
+
 def _render(H, W, K, chunk, rays, c2w, ndc, near, far, use_viewdirs, c2w_staticcam, want_pts_max, kwargs):
     if ndc:
         raise NotImplementedError('ndc=True is LLFF-only (RN:112-114); the blender configs pass ndc=False')

@@ -8,6 +8,9 @@ contract. `build_scene_maps` is the same stage as a product: render (ends on the
 the Gaussian weights as its epilogue, one launch) -> `GaussNet.register_view` (the map, the image and the inverted index stay
 resident under a view id) - the ids it returns are what attack.nerfail_s / attack.nerfail / nerfail_s_step take as `view_ids=`.
 Nothing is written unless `save_dir` asks for it, and every map is bit for bit the file pipeline's.
+`foreground_only=True` (opt-in) renders and searches only the pixels the attacks read - alpha > 0 in the view's image:
+`foreground_pixels` -> nerf_to_coord.render_pixels -> `view_map_pixels`; the maps are then the file pipeline's on those pixels and zero
+elsewhere.
 """
 import itertools
 import os
@@ -97,13 +100,61 @@ def view_map(pts_max, point_set, c=0.02, method='auto'):
     return wi, torch.square(d).sum(dtype=torch.float64)
 
 
+def foreground_pixels(image):
+    """The foreground of a view as gauss_net sees it: the pixels of its registered uint8 BGRA image [H,W,4] with alpha > 0, as a
+    device int32 [n] tensor of indices row * W + col, strictly ascending (nerfail_fg_pixel_list: an ordered stream compaction
+    on the device). One 4-byte host read: n, the length of what is returned."""
+    dev = _cuda()
+    img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 4:
+        raise ValueError('image must be uint8 BGRA [H,W,4] (MyDataset.py:200), got %s %s' % (img.dtype, tuple(img.shape)))
+    lst, count = ops.fg_pixel_list(img.to(dev).contiguous())
+    return lst[:int(count)]                                   # THE host read
+
+
+def view_map_pixels(pts, pix, hw, point_set, c=0.02, method='auto'):
+    """One view over a pixel list: pts [n,3] (the rendered points of the pixels `pix`, device int32 [n]) against the point set ->
+    (weight_and_index [2,H,W,8], sum_d2). Row pix[j] of both planes is bit for bit view_map's row for that point; every other
+    row is zero bits (weight 0, index 0). sum_d2 (0-dim float64) sums the 8 n listed distances' float32 squares only.
+    method 'auto': from GRID_FROM points up nerfail_knn8_grid_weights_list (the map zeroed and the rows scattered by one call),
+    below that the brute-force scan over the compact queries, K9, and index_copy_ into zeros; 'grid' / 'brute' force either."""
+    dev = _cuda()
+    if not float(c) > 0:
+        raise _lib.NerfailError('view_map_pixels: c must be positive')
+    H, W = int(hw[0]), int(hw[1])
+    q = _lib.f32c(torch.as_tensor(pts), dev).reshape(-1, 3)
+    pix = torch.as_tensor(pix, dtype=torch.int32, device=dev).contiguous()
+    n = int(pix.shape[0])
+    if pix.dim() != 1 or q.shape[0] != n or n > H * W:
+        raise ValueError('pts must be [n,3] and pix [n] with n <= H * W, got %s and %s' % (tuple(q.shape), tuple(pix.shape)))
+    if method == 'auto':
+        method = 'grid' if point_set.Ns >= GRID_FROM else 'brute'
+    if method == 'grid':
+        ws, nbytes = point_set.grid()
+        wi = torch.empty((2, H, W, 8), dtype=torch.float32, device=dev)
+        sum_d2 = torch.empty((), dtype=torch.float64, device=dev)
+        ops.knn8_weights_list_into(q, pix, point_set.Ns, float(c), ws, nbytes, wi, sum_d2)
+        return wi, sum_d2
+    if method != 'brute':
+        raise ValueError('method must be auto, grid or brute')
+    wi = torch.zeros((2, H * W, 8), dtype=torch.float32, device=dev)
+    if n == 0:
+        return wi.reshape(2, H, W, 8), torch.zeros((), dtype=torch.float64, device=dev)
+    d, i = knn8(q, point_set.points, method='brute')
+    rows = torch.ops.nerfail_mi.gauss_weight(torch.stack([d, i], 0).reshape(1, 2, n, 1, 8), float(c))[0].reshape(2, n, 8)
+    wi.index_copy_(1, pix.long(), rows)
+    return wi.reshape(2, H, W, 8), torch.square(d).sum(dtype=torch.float64)
+
+
 class SceneMaps:
     """What build_scene_maps returns. `point_set` / `Ns`: the scene's point set and the rows of its perturbation table;
     `view_ids`: {split: [id, ...]} in pose order - hand them to the attack loops as `view_ids=`; `v`: the "v" of DW:92-100, the
-    mean over the views of each view's mean squared distance; `c`; `hw`: the views' (H, W)."""
+    mean over the views of each view's mean squared distance; `c`; `hw`: the views' (H, W); `rendered`: {split: [n, ...]}, the
+    pixels rendered and searched per view (H W each, or the foreground counts of a foreground_only call)."""
 
-    def __init__(self, point_set, view_ids, v, c, hw, scene_key):
+    def __init__(self, point_set, view_ids, v, c, hw, scene_key, rendered=None):
         self.point_set, self.Ns, self.view_ids, self.v, self.c, self.hw, self.scene_key = point_set, point_set.Ns, view_ids, v, c, hw, scene_key
+        self.rendered = rendered if rendered is not None else {s: [hw[0] * hw[1]] * len(ids) for s, ids in view_ids.items()}
 
     def batches(self, splits, batch_size):
         """[(None, None, ids), ...]: the views of `splits` (a name or several) in order, `batch_size` per batch, as
@@ -113,7 +164,7 @@ class SceneMaps:
 
 
 def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024 * 32, images=None, view_ids=None,
-                     point_set=None, keep_maps=True, save_dir=None, on_view=None):
+                     point_set=None, keep_maps=True, save_dir=None, on_view=None, foreground_only=False):
     """NC + CI + DW for a whole scene without the disk: every view of `poses` rendered, searched, weighted and registered.
 
     `poses`: {split: [N,4,4]} or one array (then the split is 'test'). `mask_list`: the views of the 'test' split whose points
@@ -124,10 +175,25 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
     keep_maps=False: only the inverted index and the image of a view stay resident (the attack's forward needs the map, so
     True is the default). `save_dir`: ALSO write `index_and_weight/<split>/<i>.pth` (CPU float32 [2,H,W,8]) and its
     `<i>.idx.pth` sidecar under it - what the file pipeline leaves behind, which GaussNet.load_view_maps accepts as it is; no
-    `.npy`, no `index_and_dist`. `on_view(split, i, view_id, weight_and_index)` sees every map. Returns SceneMaps."""
-    dev = _cuda()
+    `.npy`, no `index_and_dist`. `on_view(split, i, view_id, weight_and_index)` sees every map. Returns SceneMaps.
+
+    foreground_only=True (opt-in; for attacks that take the returned ids as `view_ids=`): a view is rendered and searched only on
+    its foreground, the pixels whose images[split][i] has alpha > 0 - gauss_net's own rule: it writes 0 to x_rgba and takes no
+    gradient anywhere else, and an all-zero map row adds nothing to the inverted index. Every view then needs an image
+    (ValueError otherwise, before any device call). Per view: foreground_pixels -> nerf_to_coord.render_pixels -> view_map_pixels
+    -> register_view. The map equals the full call's at every foreground pixel, bit for bit, and is all-zero bits (weight 0,
+    index 0) elsewhere; the point set, Ns and the perturbation table are those of the full call: the mask_list views are still
+    rendered in full, once, and their cached points gathered at the list. `rendered` holds the foreground counts; a view
+    without foreground gets a zero map. `v` becomes the mean, over the views with n > 0, of sum_d2 / (8 n): the mean squared
+    distance of FOREGROUND pixels - not DW's `v`, which also averages the background pixels' far larger distances."""
     if not isinstance(poses, dict):
         poses, images, view_ids = {'test': poses}, (None if images is None else {'test': images}), (None if view_ids is None else {'test': view_ids})
+    if foreground_only:                                       # (host-side only: nothing has touched the device yet)
+        for split in poses:
+            have = images.get(split) if images is not None else None
+            if have is None or len(have) < len(poses[split]) or any(have[i] is None for i in range(len(poses[split]))):
+                raise ValueError("foreground_only=True: every view needs its image (images['%s'] is missing or short)" % split)
+    dev = _cuda()
     order = [s for s in SPLITS if s in poses] + [s for s in poses if s not in SPLITS]
     H, W = int(hwf[0]), int(hwf[1])
     scene_key = 'scene%d' % next(_scene_counter)
@@ -144,18 +210,34 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
     Ns = point_set.Ns
     v_sum = torch.zeros((), dtype=torch.float64, device=dev)
     n_views = 0
-    out_ids = {}
+    out_ids, rendered = {}, {}
     for split in order:
         ids = []
+        rendered[split] = []
         if save_dir is not None:
             os.makedirs(os.path.join(save_dir, 'index_and_weight', split), exist_ok=True)
         for i, c2w in enumerate(poses[split]):
             pts = pts_cache.pop(i, None) if split == 'test' else None
-            if pts is None:
-                pts = _render_pts(render_kwargs, c2w, hwf, K, chunk)
-            wi, sum_d2 = view_map(pts, point_set, c)
-            v_sum += sum_d2 / float(8 * H * W)                # this view's mean squared distance (DW:92), on the device
-            n_views += 1
+            if foreground_only:
+                pix = foreground_pixels(images[split][i])
+                n = int(pix.shape[0])
+                if pts is not None:                           # a base view: rendered in full above, gathered here
+                    fg = pts.reshape(-1, 3).index_select(0, pix.long())
+                else:
+                    with torch.no_grad():                     # as the reference renders (NC:640)
+                        fg = _NC.render_pixels(H, W, K, pix, chunk=chunk, c2w=torch.as_tensor(c2w)[:3, :4], **render_kwargs)[3]
+                wi, sum_d2 = view_map_pixels(fg, pix, (H, W), point_set, c)
+                if n > 0:
+                    v_sum += sum_d2 / float(8 * n)            # mean squared distance of this view's foreground
+                    n_views += 1
+                rendered[split].append(n)
+            else:
+                if pts is None:
+                    pts = _render_pts(render_kwargs, c2w, hwf, K, chunk)
+                wi, sum_d2 = view_map(pts, point_set, c)
+                v_sum += sum_d2 / float(8 * H * W)            # this view's mean squared distance (DW:92), on the device
+                n_views += 1
+                rendered[split].append(H * W)
             vid = view_ids[split][i] if view_ids is not None and split in view_ids else (scene_key, split, i)
             img = images[split][i] if images is not None and images.get(split) is not None else None
             if keep_maps:
@@ -175,7 +257,7 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
             ids.append(vid)
         out_ids[split] = ids
     v = float(v_sum) / max(n_views, 1)                        # THE host read of the call
-    return SceneMaps(point_set, out_ids, v, float(c), (H, W), scene_key)
+    return SceneMaps(point_set, out_ids, v, float(c), (H, W), scene_key, rendered)
 
 
 def perturbation_table(base_images, zero_init=True, rand_init=False, generator=None):

@@ -3,6 +3,7 @@
 file pipeline (nerf_to_coord.render_path -> create_index_and_dist -> dist_to_weight -> GaussNet.load_view_maps).
 
     python tools/scene_maps_bench.py [--out FILE] [--skip-pipeline]
+    python tools/scene_maps_bench.py --foreground [--out FILE]
 
 (a) `kernel`: one 800x800 view of rendered-view geometry (synth.sphere_view_points) against the 1.92 M points of three such
     views, grid built once. Arm `chain`: create_index_and_dist.index_and_dist (the search, then the torch.stack copy) followed
@@ -13,6 +14,13 @@ file pipeline (nerf_to_coord.render_path -> create_index_and_dist -> dist_to_wei
     (host clock around a device synchronisation) of build_scene_maps, render included, against the file pipeline for the same
     views in a fresh temporary directory on the local disk, each arm run twice in alternation (both runs reported); the render
     alone (the same 8 views, nothing else) is timed separately, and the bytes each arm leaves on disk are counted.
+(c) `--foreground` (run INSTEAD of (a) and (b)): build_scene_maps(foreground_only=True) against the full call over the same 8
+    views of 800x800, the same D8 W256 pair and synth.disc_alpha_image as the views' images (radius 300 of 800: n / P = 0.44);
+    `point_set=` is prebuilt from views MASK, so all 8 views take the new path. Wall time of each call, the arms ALTERNATED,
+    ROUNDS times each; the render alone likewise (nerf_to_coord.render of every pixel against render_pixels of the lists) -
+    `render_ratio` is to be read beside `n_over_P`; and the three new kernels alone on one view, event-timed, median of 20
+    after 5 warm-up (pixel list; ray_gen_list; the list search with its zeroing and fold, next to view_map on the whole view).
+    Writes profiles/r28_fg_scene_maps_bench.json.
 Writes one JSON object (default profiles/r23_scene_maps_bench.json) and prints it."""
 import json
 import os
@@ -171,15 +179,110 @@ def pipeline_arms(dev):
     return res
 
 
+ROUNDS = 3
+
+
+def foreground_arms(dev):
+    from nerfail_amd import GaussNet as G, nerf_to_coord as NC, run_nerf as RN
+    from nerfail_amd.scene import PointSet, build_scene_maps, foreground_pixels, view_map, view_map_pixels
+    from nerfail_amd import ops
+    kw = render_kwargs(dev)
+    focal, K = synth.lego_intrinsics(SIDE, SIDE)
+    hwf = [SIDE, SIDE, focal]
+    poses = torch.from_numpy(np.stack([synth.pose_spherical(-180. + 45. * i, -30., 4.) for i in range(VIEWS)]).astype(np.float32))
+    images = synth.disc_alpha_image(VIEWS, SIDE, SIDE, seed=1).astype(np.uint8)
+    chunk = 1024 * 32
+    P = SIDE * SIDE
+    ps = PointSet.from_render(kw, poses[MASK], hwf, K, chunk)              # (also the warm-up: weight images packed, kernels loaded)
+    dimg = [torch.from_numpy(images[i]).to(dev) for i in range(VIEWS)]
+    lists = [foreground_pixels(im) for im in dimg]
+    n = [int(l.shape[0]) for l in lists]
+
+    def clear():
+        for c in (G._VIEW_CACHE, G._VIEW_MAPS, G._VIEW_ORI):
+            c.clear()
+
+    def full_call():
+        return build_scene_maps(kw, poses, hwf, K, None, c=C, chunk=chunk, images=images, point_set=ps)
+
+    def fg_call():
+        return build_scene_maps(kw, poses, hwf, K, None, c=C, chunk=chunk, images=images, point_set=ps, foreground_only=True)
+
+    def render_full():
+        with torch.no_grad():
+            for c2w in poses:
+                NC.render(SIDE, SIDE, K, chunk=chunk, c2w=c2w[:3, :4], **kw)
+
+    def render_lists():
+        with torch.no_grad():
+            for c2w, pix in zip(poses, lists):
+                NC.render_pixels(SIDE, SIDE, K, pix, chunk=chunk, c2w=c2w[:3, :4], **kw)
+    res = {'shape': '%d views %dx%d, D8 W256 NeRF, 64 + 128 samples, point set prebuilt from views %s (%d points), disc images' % (VIEWS, SIDE, SIDE, MASK, ps.Ns),
+           'n_per_view': n, 'n_over_P': sum(n) / float(VIEWS * P), 'rounds': ROUNDS,
+           'full_call_s': [], 'foreground_call_s': [], 'render_full_s': [], 'render_lists_s': []}
+    fg_call()
+    clear()                                                                # warm-up of the new path
+    for _ in range(ROUNDS):
+        t, a = wall(full_call)
+        res['full_call_s'].append(t)
+        clear()
+        t, b = wall(fg_call)
+        res['foreground_call_s'].append(t)
+        clear()
+        res['render_full_s'].append(wall(render_full)[0])
+        res['render_lists_s'].append(wall(render_lists)[0])
+        assert b.rendered['test'] == n and a.Ns == b.Ns
+    med = lambda v: float(np.median(v))                                    # noqa: E731
+    res['call_ratio'] = med(res['foreground_call_s']) / med(res['full_call_s'])
+    res['render_ratio'] = med(res['render_lists_s']) / med(res['render_full_s'])
+    res['full_arm_spread_s'] = {'call': max(res['full_call_s']) - min(res['full_call_s']), 'render': max(res['render_full_s']) - min(res['render_full_s'])}
+    res['v'] = {'full': a.v, 'foreground': b.v}
+    # ---- the three new kernels alone, on view 0
+    with torch.no_grad():
+        pts = NC.render(SIDE, SIDE, K, chunk=chunk, c2w=poses[0][:3, :4], **kw)[3].reshape(SIDE, SIDE, 3)
+    pix = lists[0]
+    fg = pts.reshape(-1, 3).index_select(0, pix.long())
+    c2w = poses[0][:3, :4]
+    arms = {'pixel_list': lambda: ops.fg_pixel_list(dimg[0]), 'ray_gen_list': lambda: RN.ray_gen_list(SIDE, SIDE, K, c2w, 2., 6., pix),
+            'ray_gen_whole_view': lambda: RN.ray_gen(SIDE, SIDE, K, c2w, 2., 6.),
+            'list_search_zero_and_fold': lambda: view_map_pixels(fg, pix, (SIDE, SIDE), ps, C), 'view_map_whole_view': lambda: view_map(pts, ps, C)}
+    want = view_map(pts, ps, C)[0].reshape(2, P, 8)
+    got = view_map_pixels(fg, pix, (SIDE, SIDE), ps, C)[0].reshape(2, P, 8)
+    assert torch.equal(got[:, pix.long()], want[:, pix.long()]) and int((got != 0).any(-1).any(0).sum()) <= n[0]
+    times = {k: [] for k in arms}
+    for it in range(WARMUP + RUNS):
+        for k, fn in arms.items():                                         # alternated
+            ms = event_ms(fn)
+            if it >= WARMUP:
+                times[k].append(ms)
+    res['kernels_view0'] = {k: summary(v) for k, v in times.items()}
+    res['kernels_view0']['n'] = n[0]
+    new_ms = sum(res['kernels_view0'][k]['ms_median'] for k in ('pixel_list', 'ray_gen_list', 'list_search_zero_and_fold'))
+    res['new_kernels_ms_per_view'] = new_ms
+    # what of the render's time is not proportional to n / P, beside the full arm's spread and the new kernels
+    res['render_excess_s'] = med(res['render_lists_s']) - res['n_over_P'] * med(res['render_full_s'])
+    res['call_excess_s'] = med(res['foreground_call_s']) - res['n_over_P'] * med(res['full_call_s'])
+    res['note'] = ('wall clock around a device synchronisation, arms alternated; *_excess_s = the foreground arm minus n_over_P x the full arm, '
+                   'to be read beside full_arm_spread_s and VIEWS x new_kernels_ms_per_view; the call also holds the per-view host reads '
+                   '(the list length, the two counts of the inverted-index build) and register_view, which do not shrink with n')
+    return res
+
+
 def main():
     dev = torch.device('cuda:0')
     res = {'device': torch.cuda.get_device_name(0), 'warmup': WARMUP, 'runs': RUNS, 'command': 'python tools/scene_maps_bench.py',
            'commit': subprocess.run(['git', 'rev-parse', 'HEAD'], cwd=ROOT, capture_output=True, text=True).stdout.strip()
            or os.environ.get('NERFAIL_COMMIT', 'unknown')}
-    res['kernel'] = kernel_arms(dev)
-    if '--skip-pipeline' not in sys.argv:
-        res['pipeline'] = pipeline_arms(dev)
-    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', 'r23_scene_maps_bench.json')
+    if '--foreground' in sys.argv:
+        res['command'] += ' --foreground'
+        res['foreground'] = foreground_arms(dev)
+        default_out = 'r28_fg_scene_maps_bench.json'
+    else:
+        res['kernel'] = kernel_arms(dev)
+        if '--skip-pipeline' not in sys.argv:
+            res['pipeline'] = pipeline_arms(dev)
+        default_out = 'r23_scene_maps_bench.json'
+    out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(ROOT, 'profiles', default_out)
     text = json.dumps(res, indent=1)
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
