@@ -76,7 +76,7 @@ def _share(batch, group=None):
     wi, ori = batch[0], batch[1]
     vids = batch[2] if len(batch) > 2 and batch[2] is not None else getattr(wi, 'view_ids', None)
     B = len(vids if vids is not None else wi)
-    lo, hi = sharding.shard_range(B, rank, world)
+    lo, hi = sharding.batch_share(B, rank, world)    # THE ownership rule (sharding.owned_positions: the same call per batch)
     if hi <= lo:                            # more ranks than views: this rank only takes part in the sum
         parts = None
     elif (lo, hi) == (0, B):
@@ -414,7 +414,9 @@ def nerfail_s(net, spatial, batches, label, epochs, a=2., epsilon=32., targeted=
 
     More than one rank (torch.distributed; `group`): every batch's views are sharded as nerfail_s_step shards them, each rank
     accumulates the statistics of the views it owns, ONE extra all-reduce per epoch sums the stats row before the close, so
-    every rank takes the same decisions and ends with the same `best`. on_export is called on every rank for its own views.
+    every rank takes the same decisions and ends with the same `best`. on_export is called on every rank for its own views
+    (an export sink likewise receives them: retrain.PoisonedTrainSet.gather() then makes every rank's sink complete). The views
+    a rank owns are those of sharding.owned_positions: scene.build_scene_maps(shard_batch=) registers exactly them per rank.
 
     nerfail_s_into(export_sink, ...) is this call with a device-side sink behind the export epoch.
 

@@ -9,10 +9,15 @@ the folders, test_for_inception reads them back. Here it is one call that stays 
                          the file path would make of it, bit for bit, into two resident stores
     render_splits        nerf_render_only.py:619-656: every split rendered, uint8 in cv2's channel order, resident
     attack_output_dir    transfer_files.get_test_dir_after_nerf_attack: the folder names test_for_inception reads
-    poisoned_retrain     require_complete -> RayBatcher.from_resident -> train.train (with the README's restart advice) ->
+    poisoned_retrain     gather -> require_complete -> RayBatcher.from_resident -> train.train (with the README's restart advice) ->
                          render_splits -> model_test.evaluate_views per split
 
-Not supported (the reference's blender configs use neither): half_res and white_bkgd=False targets; more than one rank."""
+More than one rank (torch.distributed): an export epoch fills each rank's sink with that rank's views, PoisonedTrainSet.gather()
+makes every sink complete, train.train is data-parallel, render_splits(sharded=True) splits the poses and exchanges the uint8
+views; poisoned_retrain does all of it and returns the same result on every rank. Executed with gloo ranks sharing one device
+(tests/test_hip_multirank_pipeline.py): the claim is the one-rank bits, no speed-up was measured on several devices.
+
+Not supported (the reference's blender configs use neither): half_res and white_bkgd=False targets."""
 import os
 
 import numpy as np
@@ -58,6 +63,7 @@ class PoisonedTrainSet:
         self.images = torch.zeros((n, self.H, self.W, 3), dtype=torch.float32, device=self.dev)
         self.adv_u8 = torch.zeros((n, self.H, self.W, self.channels), dtype=torch.uint8, device=self.dev)
         self.filled = set()
+        self.remote = set()                                   # of `filled`: the views another rank's put() wrote (gather)
 
     def put(self, view_ids, x):
         """THE launch: the float export x [B,H,W,C] (a device tensor, C = channels) of the views `view_ids` into their slots."""
@@ -76,6 +82,7 @@ class PoisonedTrainSet:
             x = x.to(torch.float32).contiguous().clone()
         ops.export_train_views(x, [self.slot_of[v] for v in ids], self.adv_u8, self.images)
         self.filled.update(ids)
+        self.remote.difference_update(ids)
 
     def missing(self):
         return [v for v in self.view_ids if v not in self.filled]
@@ -88,9 +95,55 @@ class PoisonedTrainSet:
         world = sharding.world_and_rank(None)[0]
         more = ''
         if world > 1:
-            more = (' - with %d ranks an export sink holds only the views its own rank exported; the hand-off is one-rank: run the '
-                    'export epoch on one rank' % world)
+            more = (' - with %d ranks an export sink holds only the views its own rank exported until gather() has made it the union of '
+                    'the ranks\' sinks: call gather() on every rank after the export epoch (poisoned_retrain does)' % world)
         raise ValueError('PoisonedTrainSet: %d of %d train views were never exported: %s%s' % (len(miss), len(self.view_ids), miss, more))
+
+    def gather(self, group=None):
+        """After an export epoch on several ranks (torch.distributed; `group`, None = the default group), called on every rank:
+        each rank's sink becomes the union of the ranks' sinks. One all-reduce of 2 n int32 says who filled which slot; a slot
+        filled on more than one rank is a ValueError naming it, on every rank; every other filled slot travels from its owner
+        by broadcast (runs of neighbouring slots of one owner in one call): a copy, so `images` and `adv_u8` hold the bits the
+        owner's put() wrote. A slot no rank filled stays missing. One rank: nothing happens. A view received here still belongs
+        to its owner, so a second gather() finds the same owners and changes nothing. Returns self."""
+        world, rank = sharding.world_and_rank(group)
+        if world == 1:
+            return self
+        owner = gather_slots(self.images, self.adv_u8, [v in self.filled and v not in self.remote for v in self.view_ids], group)
+        twice = [self.view_ids[s] for s, o in enumerate(owner) if o == DUPLICATE]
+        if twice:
+            raise ValueError('PoisonedTrainSet.gather: view(s) %s were exported on more than one rank - every view of an export epoch '
+                             'belongs to one rank (attack.nerfail_s_into shards its export batches that way)' % (twice,))
+        self.remote = {self.view_ids[s] for s, o in enumerate(owner) if o is not None and o != rank}
+        self.filled |= self.remote
+        return self
+
+
+DUPLICATE = -1
+
+
+def gather_slots(images, adv_u8, filled, group=None):
+    """The exchange behind PoisonedTrainSet.gather, over plain tensors: `images` and `adv_u8` ([n, ...], contiguous, on one
+    device) and `filled` (n booleans: the slots this rank wrote). Returns the owner of every slot, the same list on every rank:
+    a rank, None (nobody filled it) or DUPLICATE (more than one rank did); with a DUPLICATE nothing has been moved, else every
+    owned slot of both tensors now holds its owner's bytes on every rank."""
+    world, rank = sharding.world_and_rank(group)
+    n = len(filled)
+    mine = torch.tensor([1 if f else 0 for f in filled] + [rank if f else 0 for f in filled], dtype=torch.int32)
+    who = sharding.all_reduce_sum_(mine.to(images.device), group).cpu().tolist()       # [0:n] how many ranks filled it, [n:2n] which
+    owner = [None if who[s] == 0 else (who[n + s] if who[s] == 1 else DUPLICATE) for s in range(n)]
+    if DUPLICATE in owner:
+        return owner
+    s = 0
+    while s < n:
+        e = s + 1
+        while e < n and owner[e] == owner[s]:
+            e += 1
+        if owner[s] is not None:
+            sharding.broadcast_(images[s:e], owner[s], group)
+            sharding.broadcast_(adv_u8[s:e], owner[s], group)
+        s = e
+    return owner
 
 
 # ---------------------------------------------------------------------------------------------- nerf_render_only.py:619-656
@@ -123,11 +176,17 @@ def render_view_u8(render_kwargs, c2w, hwf, K, chunk):
         return (255 * torch.clamp(rgb, 0, 1)).to(torch.uint8).flip(-1).contiguous()
 
 
-def render_splits(render_kwargs_test, poses, i_split, hwf, K, chunk, tags=("test", "train", "val"), savedir=None, start=0):
+def render_splits(render_kwargs_test, poses, i_split, hwf, K, chunk, tags=("test", "train", "val"), savedir=None, start=0, sharded=False,
+                  group=None):
     """nerf_render_only.py:619-656: for every tag the poses of its split (i_split = [train, val, test]) rendered with
     `render_kwargs_test` (near / far included). Returns {tag: uint8 [N,H,W,3]} on the device, converted as run_nerf.to8b converts
     and in cv2's channel order - what model_test.evaluate_render measures and what cv2.imread returns for the PNGs the reference
-    writes. `savedir`: additionally writes savedir/renderonly_<tag>_<start:06d>/<i:03d>.png, the reference's folders."""
+    writes. `savedir`: additionally writes savedir/renderonly_<tag>_<start:06d>/<i:03d>.png, the reference's folders.
+    sharded=True (opt-in; torch.distributed, `group`, the same weights on every rank): of each tag's N poses this rank renders
+    sharding.shard_range(N, rank, world), the uint8 views are exchanged (sharding.all_gather_ranges_), every rank returns the
+    full tensors - the unsharded call's bits - and rank 0 alone writes `savedir`. One rank: the unsharded call."""
+    world, rank = sharding.world_and_rank(group) if sharded else (1, 0)
+    H, W = int(hwf[0]), int(hwf[1])
     out = {}
     for tag in tags:
         if tag not in SPLIT_OF_TAG:
@@ -137,8 +196,15 @@ def render_splits(render_kwargs_test, poses, i_split, hwf, K, chunk, tags=("test
             raise ValueError('render_splits: the %s split holds no view' % tag)
         p = poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else np.asarray(poses)
         split_poses = torch.as_tensor(p[idx], dtype=torch.float32)       # on the host: a pose travels to the ray kernel by value
-        out[tag] = torch.stack([render_view_u8(render_kwargs_test, c2w, hwf, K, chunk) for c2w in split_poses])
-        if savedir is not None:
+        if world > 1:
+            lo, hi = sharding.shard_range(len(idx), rank, world)
+            out[tag] = torch.empty((len(idx), H, W, 3), dtype=torch.uint8, device=_cuda())
+            for i in range(lo, hi):
+                out[tag][i] = render_view_u8(render_kwargs_test, split_poses[i], hwf, K, chunk)
+            sharding.all_gather_ranges_(out[tag], sharding.shard_ranges(len(idx), world), group)
+        else:
+            out[tag] = torch.stack([render_view_u8(render_kwargs_test, c2w, hwf, K, chunk) for c2w in split_poses])
+        if savedir is not None and rank == 0:
             _write_views(os.path.join(savedir, 'renderonly_{}_{:06d}'.format(tag, start)), out[tag])
     return out
 
@@ -211,15 +277,23 @@ def poisoned_retrain(train_set, poses, i_split, hwf, K, args, make_nerf=None, or
     save_dir/<tag>/<i:03d>.png (attack_output_dir(..., step=1) names the folder test_for_inception reads) - and, with `model`,
     `model_name`, `label` and `originals` ({tag: the split's clean views, uint8, cv2 order}), evaluate_views per tag of
     `eval_tags`. near = 2, far = 6 (RN:573-574) unless given; what remains of **eval_kw goes to evaluate_views (batch,
-    num_classes, resize_to). One rank only. Returns a RetrainResult."""
+    num_classes, resize_to).
+
+    More than one rank (torch.distributed, the default group): every rank calls this with its own sink and the same arguments.
+    train_set.gather() first makes every sink the union of what the ranks' export epochs put; train.train is data-parallel
+    (rank 0's parameters, one gradient all-reduce per step, the ranks' parameters compared at every log point); `logged` is the
+    same on every rank, so restart_below restarts all ranks together, and a found checkpoint is refused on every rank;
+    render_splits(sharded=True) splits the poses of each tag and exchanges the views; evaluate_views then runs on every rank
+    over the full renders (not sharded on purpose: 2.4 ms per 8 views, no rule for merging device records, the same bits
+    everywhere). `save_dir` and the log lines are rank 0's. The RetrainResult is identical on every rank.
+    Returns a RetrainResult."""
     from . import run_nerf as RN
     from .train import RayBatcher, train
     resume = bool(eval_kw.pop('resume', False))
     near, far = float(eval_kw.pop('near', 2.)), float(eval_kw.pop('far', 6.))
-    world = sharding.world_and_rank(None)[0]
+    world, rank = sharding.world_and_rank(None)
+    train_set.gather()                                                    # (one rank: nothing happens)
     train_set.require_complete()
-    if world > 1:
-        raise ValueError('poisoned_retrain: the hand-off is one-rank (%d ranks are running)' % world)
     i_train = [int(i) for i in i_split[0]]
     if len(train_set.view_ids) != len(i_train):
         raise ValueError('poisoned_retrain: the set holds %d views, the train split %d - slot s must hold the view of pose i_split[0][s]'
@@ -236,7 +310,7 @@ def poisoned_retrain(train_set, poses, i_split, hwf, K, args, make_nerf=None, or
     evaluate = model is not None and originals is not None
     if evaluate and (model_name is None or label is None):
         raise ValueError('poisoned_retrain: a classifier needs its model_name and the label')
-    say = log if log is not None else (lambda *_: None)
+    say = log if log is not None and rank == 0 else (lambda *_: None)    # rank 0 speaks (train.train silences the others itself)
     attempts = 0
     while True:
         render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer = make_nerf(attempts)
@@ -266,8 +340,8 @@ def poisoned_retrain(train_set, poses, i_split, hwf, K, args, make_nerf=None, or
     tags = list(eval_tags)
     if save_dir is not None:
         tags += [t for t in ('train', 'test', 'val') if t not in tags]
-    renders = render_splits(render_kwargs_test, poses, i_split, hwf, K, int(getattr(args, 'chunk', 1024 * 32)), tags=tags)
-    if save_dir is not None:
+    renders = render_splits(render_kwargs_test, poses, i_split, hwf, K, int(getattr(args, 'chunk', 1024 * 32)), tags=tags, sharded=world > 1)
+    if save_dir is not None and rank == 0:
         for tag in ('train', 'test', 'val'):
             _write_views(os.path.join(save_dir, tag), renders[tag])
     reports = {}

@@ -11,6 +11,9 @@ Nothing is written unless `save_dir` asks for it, and every map is bit for bit t
 `foreground_only=True` (opt-in) renders and searches only the pixels the attacks read - alpha > 0 in the view's image:
 `foreground_pixels` -> nerf_to_coord.render_pixels -> `view_map_pixels`; the maps are then the file pipeline's on those pixels and zero
 elsewhere.
+`shard_batch=B` (opt-in, under torch.distributed) builds the scene once across the ranks: the base views by pixel range, every
+other view on the rank the attack's batches of B hand it to (sharding.batch_owner); the results are the one-rank call's bits.
+Executed with gloo ranks sharing one device; no speed-up was measured on several devices.
 """
 import itertools
 import os
@@ -22,6 +25,7 @@ from . import _lib
 from . import ops
 from . import GaussNet as _G
 from . import nerf_to_coord as _NC
+from . import sharding
 from .create_index_and_dist import _grid_for, knn8
 from .run_nerf_helpers import _cuda
 
@@ -70,6 +74,21 @@ def _render_pts(render_kwargs, c2w, hwf, K, chunk):
     with torch.no_grad():                                  # as the reference renders (NC:640)
         pts_max = _NC.render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)[3]
     return pts_max.reshape(H, W, 3)
+
+
+def _render_pts_sharded(render_kwargs, c2w, hwf, K, chunk, rank, world, group):
+    """_render_pts across the ranks of `group`: this rank renders its pixel range (sharding.render_shard: the slices concatenate
+    bit for bit to the full render), the ranges are exchanged (sharding.all_gather_ranges_), every rank returns the same [H,W,3]."""
+    H, W = int(hwf[0]), int(hwf[1])
+    kw = {k: v for k, v in render_kwargs.items() if k not in ('near', 'far')}
+    with torch.no_grad():
+        (lo, hi), ret = sharding.render_shard(H, W, K, torch.as_tensor(c2w)[:3, :4], render_kwargs.get('near', 0.), render_kwargs.get('far', 1.),
+                                              rank, world, chunk, **kw)
+    pts = torch.empty((H * W, 3), dtype=torch.float32, device=_cuda())
+    if hi > lo:
+        pts[lo:hi] = ret['pts_max']
+    sharding.all_gather_ranges_(pts, sharding.shard_ranges(H * W, world), group)
+    return pts.reshape(H, W, 3)
 
 
 def view_map(pts_max, point_set, c=0.02, method='auto'):
@@ -150,21 +169,34 @@ class SceneMaps:
     """What build_scene_maps returns. `point_set` / `Ns`: the scene's point set and the rows of its perturbation table;
     `view_ids`: {split: [id, ...]} in pose order - hand them to the attack loops as `view_ids=`; `v`: the "v" of DW:92-100, the
     mean over the views of each view's mean squared distance; `c`; `hw`: the views' (H, W); `rendered`: {split: [n, ...]}, the
-    pixels rendered and searched per view (H W each, or the foreground counts of a foreground_only call)."""
+    pixels rendered and searched per view (H W each, or the foreground counts of a foreground_only call).
+    A call with `shard_batch` set is sharded: `shard_batch` and `world` record the batch size and the number of ranks the views
+    were split for, `owned` ({split: [positions]}) names the views THIS rank rendered, searched and registered - under the
+    attack's own rule, sharding.owned_positions per split; `view_ids`, `rendered` and `v` cover all views on every rank.
+    Unsharded: shard_batch None, world 1, every position owned."""
 
-    def __init__(self, point_set, view_ids, v, c, hw, scene_key, rendered=None):
+    def __init__(self, point_set, view_ids, v, c, hw, scene_key, rendered=None, owned=None, shard_batch=None, world=1):
         self.point_set, self.Ns, self.view_ids, self.v, self.c, self.hw, self.scene_key = point_set, point_set.Ns, view_ids, v, c, hw, scene_key
         self.rendered = rendered if rendered is not None else {s: [hw[0] * hw[1]] * len(ids) for s, ids in view_ids.items()}
+        self.owned = owned if owned is not None else {s: list(range(len(ids))) for s, ids in view_ids.items()}
+        self.shard_batch, self.world = shard_batch, world
 
     def batches(self, splits, batch_size):
         """[(None, None, ids), ...]: the views of `splits` (a name or several) in order, `batch_size` per batch, as
-        attack.nerfail_s takes them when the maps and images are resident."""
-        ids = [v for s in ((splits,) if isinstance(splits, str) else splits) for v in self.view_ids[s]]
-        return [(None, None, ids[b:b + batch_size]) for b in range(0, len(ids), batch_size)]
+        attack.nerfail_s takes them when the maps and images are resident. Sharded maps: each split is cut on its own (a batch
+        never holds views of two splits: ownership was decided per split), and `batch_size` must be the `shard_batch` the maps
+        were built for (ValueError otherwise: another cut hands a rank views it never registered)."""
+        splits = (splits,) if isinstance(splits, str) else splits
+        if self.shard_batch is None:
+            ids = [v for s in splits for v in self.view_ids[s]]
+            return [(None, None, ids[b:b + batch_size]) for b in range(0, len(ids), batch_size)]
+        if int(batch_size) != self.shard_batch:
+            raise ValueError('SceneMaps.batches: these maps were built for batches of shard_batch = %d views, not %r' % (self.shard_batch, batch_size))
+        return [(None, None, self.view_ids[s][b:b + batch_size]) for s in splits for b in range(0, len(self.view_ids[s]), batch_size)]
 
 
 def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024 * 32, images=None, view_ids=None,
-                     point_set=None, keep_maps=True, save_dir=None, on_view=None, foreground_only=False):
+                     point_set=None, keep_maps=True, save_dir=None, on_view=None, foreground_only=False, shard_batch=None, group=None):
     """NC + CI + DW for a whole scene without the disk: every view of `poses` rendered, searched, weighted and registered.
 
     `poses`: {split: [N,4,4]} or one array (then the split is 'test'). `mask_list`: the views of the 'test' split whose points
@@ -185,7 +217,17 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
     index 0) elsewhere; the point set, Ns and the perturbation table are those of the full call: the mask_list views are still
     rendered in full, once, and their cached points gathered at the list. `rendered` holds the foreground counts; a view
     without foreground gets a zero map. `v` becomes the mean, over the views with n > 0, of sum_d2 / (8 n): the mean squared
-    distance of FOREGROUND pixels - not DW's `v`, which also averages the background pixels' far larger distances."""
+    distance of FOREGROUND pixels - not DW's `v`, which also averages the background pixels' far larger distances.
+
+    shard_batch=B (opt-in, an int >= 1) under a torch.distributed process group (`group`; None = the default group) of more than
+    one rank: the scene is built once across the group, for an attack that takes `maps.batches(split, B)`. Each mask_list view
+    is rendered by pixel range over the ranks and the ranges exchanged - point set, Ns and grid are the one-rank call's bits on
+    every rank. Of each split, position i is rendered, searched, registered, saved and shown to on_view only on
+    sharding.batch_owner(i, len(split), B, world): the rank attack._share hands it to. view_ids, rendered and v cover all
+    views on every rank: each rank writes its views' terms and counts in double into one vector (zeros elsewhere), ONE all-reduce
+    sums it - exactly: every slot has one non-zero contribution - and the terms are added in the one-rank call's order, so v is
+    the one-rank v; that vector is the call's only host read besides the per-view counts. With one rank (or no group) the
+    call owns everything and is today's call. shard_batch=None: every rank builds everything, as before."""
     if not isinstance(poses, dict):
         poses, images, view_ids = {'test': poses}, (None if images is None else {'test': images}), (None if view_ids is None else {'test': view_ids})
     if foreground_only:                                       # (host-side only: nothing has touched the device yet)
@@ -193,6 +235,13 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
             have = images.get(split) if images is not None else None
             if have is None or len(have) < len(poses[split]) or any(have[i] is None for i in range(len(poses[split]))):
                 raise ValueError("foreground_only=True: every view needs its image (images['%s'] is missing or short)" % split)
+    world, rank = 1, 0
+    if shard_batch is not None:
+        if isinstance(shard_batch, bool) or int(shard_batch) != shard_batch or int(shard_batch) < 1:
+            raise ValueError('shard_batch must be an int >= 1 (the batch size of the attack), got %r' % (shard_batch,))
+        shard_batch = int(shard_batch)
+        world, rank = sharding.world_and_rank(group)
+    sharded = world > 1
     dev = _cuda()
     order = [s for s in SPLITS if s in poses] + [s for s in poses if s not in SPLITS]
     H, W = int(hwf[0]), int(hwf[1])
@@ -205,19 +254,29 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
         if not mask_list or min(mask_list) < 0 or max(mask_list) >= len(poses['test']):
             raise ValueError('mask_list must name views of the test split (0..%d)' % (len(poses['test']) - 1))
         for i in sorted(set(mask_list)):                      # rendered once: as base views now, as views of their split below
-            pts_cache[i] = _render_pts(render_kwargs, poses['test'][i], hwf, K, chunk)
+            pts_cache[i] = (_render_pts_sharded(render_kwargs, poses['test'][i], hwf, K, chunk, rank, world, group) if sharded
+                            else _render_pts(render_kwargs, poses['test'][i], hwf, K, chunk))
         point_set = PointSet.from_views([pts_cache[i] for i in mask_list])
     Ns = point_set.Ns
     v_sum = torch.zeros((), dtype=torch.float64, device=dev)
     n_views = 0
-    out_ids, rendered = {}, {}
+    out_ids, rendered, owned = {}, {}, {}
+    first = dict(zip(order, itertools.accumulate([0] + [len(poses[s]) for s in order])))       # a split's first slot in `terms`
+    total = sum(len(poses[s]) for s in order)
+    terms = torch.zeros((2 * total,), dtype=torch.float64, device=dev) if sharded else None   # per view: its term of v, its count
     for split in order:
         ids = []
         rendered[split] = []
+        owned[split] = sharding.owned_positions(len(poses[split]), shard_batch, rank, world) if sharded else list(range(len(poses[split])))
+        mine = set(owned[split])
         if save_dir is not None:
             os.makedirs(os.path.join(save_dir, 'index_and_weight', split), exist_ok=True)
         for i, c2w in enumerate(poses[split]):
             pts = pts_cache.pop(i, None) if split == 'test' else None
+            vid = view_ids[split][i] if view_ids is not None and split in view_ids else (scene_key, split, i)
+            ids.append(vid)
+            if i not in mine:                                 # another rank's view: only its id is known here
+                continue
             if foreground_only:
                 pix = foreground_pixels(images[split][i])
                 n = int(pix.shape[0])
@@ -227,18 +286,21 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
                     with torch.no_grad():                     # as the reference renders (NC:640)
                         fg = _NC.render_pixels(H, W, K, pix, chunk=chunk, c2w=torch.as_tensor(c2w)[:3, :4], **render_kwargs)[3]
                 wi, sum_d2 = view_map_pixels(fg, pix, (H, W), point_set, c)
-                if n > 0:
-                    v_sum += sum_d2 / float(8 * n)            # mean squared distance of this view's foreground
-                    n_views += 1
-                rendered[split].append(n)
+                term = sum_d2 / float(8 * n) if n > 0 else None   # mean squared distance of this view's foreground
             else:
                 if pts is None:
                     pts = _render_pts(render_kwargs, c2w, hwf, K, chunk)
                 wi, sum_d2 = view_map(pts, point_set, c)
-                v_sum += sum_d2 / float(8 * H * W)            # this view's mean squared distance (DW:92), on the device
-                n_views += 1
-                rendered[split].append(H * W)
-            vid = view_ids[split][i] if view_ids is not None and split in view_ids else (scene_key, split, i)
+                n, term = H * W, sum_d2 / float(8 * H * W)    # this view's mean squared distance (DW:92), on the device
+            if sharded:
+                if term is not None:
+                    terms[first[split] + i] = term
+                terms[total + first[split] + i] = float(n)
+            else:
+                if term is not None:
+                    v_sum += term
+                    n_views += 1
+                rendered[split].append(n)
             img = images[split][i] if images is not None and images.get(split) is not None else None
             if keep_maps:
                 _G.register_view(vid, Ns, wi, img)
@@ -254,10 +316,21 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
                 vi.save(os.path.join(save_dir, 'index_and_weight', split, '%d.idx.pth' % i))
             if on_view is not None:
                 on_view(split, i, vid, wi)
-            ids.append(vid)
         out_ids[split] = ids
-    v = float(v_sum) / max(n_views, 1)                        # THE host read of the call
-    return SceneMaps(point_set, out_ids, v, float(c), (H, W), scene_key, rendered)
+    if sharded:
+        sharding.all_reduce_sum_(terms, group)                # exact: one rank wrote each slot, the others add zeros
+        t = terms.cpu().tolist()                              # THE host read of the call
+        v_sum = 0.
+        for split in order:
+            for k in range(first[split], first[split] + len(poses[split])):
+                rendered[split].append(int(t[total + k]))
+                if rendered[split][-1] > 0:                   # the one-rank call's order, view by view, in double
+                    v_sum += t[k]
+                    n_views += 1
+        v = v_sum / max(n_views, 1)
+    else:
+        v = float(v_sum) / max(n_views, 1)                    # THE host read of the call
+    return SceneMaps(point_set, out_ids, v, float(c), (H, W), scene_key, rendered, owned, shard_batch, world)
 
 
 def perturbation_table(base_images, zero_init=True, rand_init=False, generator=None):

@@ -4,6 +4,9 @@ Rays are independent units: a view's pixel range is cut into contiguous per-rank
 with NO data-path collective (each rank writes / keeps its own slice). The attack step has one real
 exchange: the sum of the per-shard perturbation gradients (attack.nerfail_s_step). Training splits the rays of each
 step and sums one flat buffer of parameter gradients per step (train.train, _train.GradArena).
+Which rank owns which view of a list attacked in batches is ONE rule, batch_share: attack._share cuts a batch with it,
+scene.build_scene_maps(shard_batch=) builds a view on batch_owner's rank only. Results that every rank needs whole (a base view's
+points, exported train views, rendered splits) travel by all_gather_ranges_: a copy from the owner, never a sum.
 The range arithmetic is pure host logic: importable and testable without a GPU.
 """
 import torch
@@ -21,6 +24,44 @@ def shard_range(n, rank, world):
 
 def shard_ranges(n, world):
     return [shard_range(n, r, world) for r in range(world)]
+
+
+def batch_bounds(position, n, batch_size):
+    """[b0, b1): the batch that holds `position` when a list of n ids is cut into batches of `batch_size`, the last one short."""
+    n, batch_size, position = int(n), int(batch_size), int(position)
+    if batch_size < 1 or not (0 <= position < n):
+        raise ValueError('bad position/n/batch_size: %r/%r/%r' % (position, n, batch_size))
+    b0 = position - position % batch_size
+    return b0, min(b0 + batch_size, n)
+
+
+def batch_share(B, rank, world):
+    """THE ownership rule of a batch of B views: rank `rank` owns shard_range(B, rank, world) of it. attack._share cuts every
+    batch with this call; batch_owner / owned_positions apply it to a whole list of ids cut into batches."""
+    return shard_range(B, rank, world)
+
+
+def owned_positions(n, batch_size, rank, world):
+    """The positions of a list of n ids that `rank` owns when the list is attacked in batches of `batch_size` (the last one
+    short) over `world` ranks: per batch [b0, b1), b0 + batch_share(b1 - b0, rank, world). Ascending."""
+    n, batch_size = int(n), int(batch_size)
+    if batch_size < 1 or n < 0:
+        raise ValueError('bad n/batch_size: %r/%r' % (n, batch_size))
+    out = []
+    for b0 in range(0, n, batch_size):
+        lo, hi = batch_share(min(batch_size, n - b0), rank, world)
+        out.extend(range(b0 + lo, b0 + hi))
+    return out
+
+
+def batch_owner(position, n, batch_size, world):
+    """The rank that owns `position` of a list of n ids under owned_positions' rule."""
+    b0, b1 = batch_bounds(position, n, batch_size)
+    for r in range(int(world)):
+        lo, hi = batch_share(b1 - b0, r, world)
+        if lo <= position - b0 < hi:
+            return r
+    raise ValueError('bad world: %r' % (world,))
 
 
 def world_and_rank(group=None):
@@ -110,6 +151,20 @@ def broadcast_(t, src=0, group=None):
             t.copy_(h.reshape(t.shape))
         return t
     dist.broadcast(t, src=gsrc, group=group)
+    return t
+
+
+def all_gather_ranges_(t, ranges, group=None):
+    """In place: `t` (contiguous) is cut along its first dimension into one range per rank, ranges[r] = [lo, hi) - rank r has
+    filled t[lo:hi]; afterwards every rank holds every range, each bit for bit its owner's. One broadcast_ per non-empty range
+    (so on broadcast_'s two paths: on the device, or - HIP tensor under pure gloo - through the pinned host buffer)."""
+    if not _collective(group):
+        return t
+    if not t.is_contiguous() or len(ranges) != dist.get_world_size(group):
+        raise ValueError('all_gather_ranges_: a contiguous tensor and one range per rank')
+    for src, (lo, hi) in enumerate(ranges):
+        if hi > lo:
+            broadcast_(t[lo:hi], src, group)
     return t
 
 

@@ -4,6 +4,7 @@ file pipeline (nerf_to_coord.render_path -> create_index_and_dist -> dist_to_wei
 
     python tools/scene_maps_bench.py [--out FILE] [--skip-pipeline]
     python tools/scene_maps_bench.py --foreground [--out FILE]
+    python tools/scene_maps_bench.py --sharded [--out FILE]
 
 (a) `kernel`: one 800x800 view of rendered-view geometry (synth.sphere_view_points) against the 1.92 M points of three such
     views, grid built once. Arm `chain`: create_index_and_dist.index_and_dist (the search, then the torch.stack copy) followed
@@ -21,6 +22,10 @@ file pipeline (nerf_to_coord.render_path -> create_index_and_dist -> dist_to_wei
     `render_ratio` is to be read beside `n_over_P`; and the three new kernels alone on one view, event-timed, median of 20
     after 5 warm-up (pixel list; ray_gen_list; the list search with its zeroing and fold, next to view_map on the whole view).
     Writes profiles/r28_fg_scene_maps_bench.json.
+(d) `--sharded` (run INSTEAD of (a) and (b)): a one-GPU sanity number, not a scaling claim - build_scene_maps(shard_batch=8) in
+    this one-rank process against the call without the keyword, over shape (b)'s 8 views and point set. One rank owns every
+    view, so both arms issue the same launches; wall time of each call, the arms ALTERNATED, ROUNDS times each.
+    Writes profiles/r29_sharded_scene_maps_bench.json.
 Writes one JSON object (default profiles/r23_scene_maps_bench.json) and prints it."""
 import json
 import os
@@ -268,6 +273,45 @@ def foreground_arms(dev):
     return res
 
 
+def sharded_arms(dev):
+    from nerfail_amd import GaussNet as G
+    from nerfail_amd.scene import build_scene_maps
+    kw = render_kwargs(dev)
+    focal, K = synth.lego_intrinsics(SIDE, SIDE)
+    hwf = [SIDE, SIDE, focal]
+    poses = torch.from_numpy(np.stack([synth.pose_spherical(-180. + 45. * i, -30., 4.) for i in range(VIEWS)]).astype(np.float32))
+    chunk = 1024 * 32
+
+    def clear():
+        for c in (G._VIEW_CACHE, G._VIEW_MAPS, G._VIEW_ORI):
+            c.clear()
+
+    def plain_call():
+        return build_scene_maps(kw, poses, hwf, K, MASK, c=C, chunk=chunk)
+
+    def keyword_call():
+        return build_scene_maps(kw, poses, hwf, K, MASK, c=C, chunk=chunk, shard_batch=VIEWS)
+    res = {'shape': '%d views %dx%d, D8 W256 NeRF, 64 + 128 samples, point set = views %s; one rank, no process group' % (VIEWS, SIDE, SIDE, MASK),
+           'rounds': ROUNDS, 'plain_call_s': [], 'shard_batch_call_s': []}
+    plain_call()
+    clear()                                                                # warm-up: weight images packed, kernels loaded
+    for _ in range(ROUNDS):
+        t, a = wall(plain_call)
+        res['plain_call_s'].append(t)
+        clear()
+        t, b = wall(keyword_call)
+        res['shard_batch_call_s'].append(t)
+        clear()
+        assert a.v == b.v and a.rendered == b.rendered and b.owned == {'test': list(range(VIEWS))} and b.world == 1
+    med = lambda v: float(np.median(v))                                    # noqa: E731
+    res['plain_arm_spread_s'] = max(res['plain_call_s']) - min(res['plain_call_s'])
+    res['median_difference_s'] = med(res['shard_batch_call_s']) - med(res['plain_call_s'])
+    res['inside_the_plain_arm_spread'] = bool(abs(res['median_difference_s']) <= res['plain_arm_spread_s'])
+    res['note'] = ('wall clock around a device synchronisation, arms alternated; one rank owns every view, so the keyword changes no '
+                   'launch - nothing here measures several devices')
+    return res
+
+
 def main():
     dev = torch.device('cuda:0')
     res = {'device': torch.cuda.get_device_name(0), 'warmup': WARMUP, 'runs': RUNS, 'command': 'python tools/scene_maps_bench.py',
@@ -277,6 +321,10 @@ def main():
         res['command'] += ' --foreground'
         res['foreground'] = foreground_arms(dev)
         default_out = 'r28_fg_scene_maps_bench.json'
+    elif '--sharded' in sys.argv:
+        res['command'] += ' --sharded'
+        res['sharded'] = sharded_arms(dev)
+        default_out = 'r29_sharded_scene_maps_bench.json'
     else:
         res['kernel'] = kernel_arms(dev)
         if '--skip-pipeline' not in sys.argv:
