@@ -5,7 +5,7 @@ baselines' `universal_2D_dataset` / `universal_2D_dataset_rand_select` (MD:235-2
 
 What differs is WHERE the tensors come from. The reference reads the PNG and `torch.load`s the 41 MB map from disk for
 every item of every iteration (MD:199-204) and the DataLoader stacks eight of them into a fresh batch tensor. A view's map
-and image never change, so here an item is loaded ONCE and then lives on the device under its view id (GaussNet.
+and image never change, so here an item is loaded ONCE and then lives on the device under its view id (views.
 register_view; 288 GB of HBM hold a whole scene); later __getitem__ calls return those resident tensors, and
 `collate_views` hands the batch to gauss_net.forward / nerfail_s_step as a list of per-view tensors plus their ids instead of
 stacking 328 MB per iteration. With the default collate function the batch is a stacked DEVICE tensor, as in the reference.
@@ -17,7 +17,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from . import GaussNet as _G
+from . import views as _views
 from .run_nerf_helpers import _cuda
 
 
@@ -82,16 +82,15 @@ class gauss_dataset(Dataset):
 
     def __getitem__(self, index):
         dev = _cuda()
-        key = _G._view_key(self.view_id(index), self.Ns) if self.Ns is not None else None
-        wi = _G._VIEW_MAPS.get(key) if key is not None else None
-        ori = _G._VIEW_ORI.get(key) if key is not None else None
+        wi, ori = _views.resident(self.view_id(index), self.Ns) if self.Ns is not None else (None, None)
+        missing = wi is None or ori is None
         if ori is None:
             ori = torch.tensor(_imread_unchanged(self.all_img_name_list[index])).to(dev)
         if wi is None:
             wi = torch.load(self.all_index_and_dist_name_list[index], map_location=dev)
-        if key is not None and (key not in _G._VIEW_MAPS or key not in _G._VIEW_ORI):
-            _G.register_view(self.view_id(index), self.Ns, weight_and_index=wi, ori_img=ori)
-            wi, ori = _G._VIEW_MAPS[key], _G._VIEW_ORI[key]
+        if self.Ns is not None and missing:
+            _views.register_view(self.view_id(index), self.Ns, weight_and_index=wi, ori_img=ori)
+            wi, ori = _views.resident(self.view_id(index), self.Ns)
         return index, ori, wi, self.all_img_save_to_name_list[index], self.all_img_mask_save_to_name_list[index]
 
     def collate_views(self, batch):

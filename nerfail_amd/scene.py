@@ -28,6 +28,7 @@ from . import nerf_to_coord as _NC
 from . import sharding
 from .create_index_and_dist import _grid_for, knn8
 from .run_nerf_helpers import _cuda
+from .views import _file_sig
 
 GRID_FROM = 4096          # the 'auto' rule of create_index_and_dist.knn8: grid search from this many points up
 SPLITS = ('test', 'train', 'val')     # CI:110
@@ -312,7 +313,7 @@ def build_scene_maps(render_kwargs, poses, hwf, K, mask_list, c=0.02, chunk=1024
                 mpath = os.path.join(save_dir, 'index_and_weight', split, '%d.pth' % i)
                 torch.save(wi.cpu(), mpath)                    # DW:95-97
                 vi = _G.view_indices([wi], Ns, [vid])[0]
-                vi.src = _G._file_sig(mpath)
+                vi.src = _file_sig(mpath)
                 vi.save(os.path.join(save_dir, 'index_and_weight', split, '%d.idx.pth' % i))
             if on_view is not None:
                 on_view(split, i, vid, wi)

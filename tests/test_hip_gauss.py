@@ -722,6 +722,32 @@ def test_attack_step_reuses_cached_original_logits():
     assert len(calls) == 3 and torch.equal(c, ref) and torch.equal(d, ref)
 
 
+def test_an_image_uploaded_again_under_its_id_misses_the_logit_cache():
+    """views.py rule 8: keep_views_resident writes resident images through the same writer as register_view, which bumps the
+    image epoch of the id. After the resident images are gone (a clear, an eviction) ANOTHER image uploaded under the same id
+    must not find the first one's logits in the net's cache (default cache_ori_cla, frozen classifier)."""
+    from nerfail_amd import GaussNet as G, attack as A
+    s0, wi, ori_u8, victim = _toy_attack(seed=88, B=3)
+    victim.eval()                                                 # AS:281: the automatic cache's precondition
+    label = torch.tensor(1, device=dev())
+    ids = [('again', i) for i in range(3)]
+    G._VIEW_CACHE.clear(); G._VIEW_MAPS.clear(); G._VIEW_ORI.clear()
+    net = G.gauss_net(dev(), 0.02, victim, 'my_model', epsilon=None)
+    net.keep_views_resident = True
+    assert net.cache_ori_cla is None
+    A.nerfail_s_step(net, s0, s0, wi, torch.from_numpy(ori_u8), label, view_ids=ids)             # image set A: uploaded, logits cached
+    _, _, ori_cla_a, _, _ = net.attack_forward(s0, None, None, view_ids=ids)
+    G._VIEW_MAPS.clear(); G._VIEW_ORI.clear()
+    set_b = ori_u8.copy()
+    set_b[0][..., :3] = 255 - set_b[0][..., :3]
+    _, _, ori_cla_b, _, _ = net.attack_forward(s0, wi, torch.from_numpy(set_b), view_ids=ids)    # image set B under the same ids
+    fresh = G.gauss_net(dev(), 0.02, victim, 'my_model', epsilon=None)
+    _, _, ori_cla_ref, _, _ = fresh.attack_forward(s0, None, None, view_ids=ids)
+    assert not torch.equal(ori_cla_ref[0], ori_cla_a[0])                                         # (the two sets do differ)
+    assert torch.equal(ori_cla_b, ori_cla_ref)
+    G._VIEW_CACHE.clear(); G._VIEW_MAPS.clear(); G._VIEW_ORI.clear()
+
+
 def test_original_logits_are_cached_by_default_for_named_views():
     """cache_ori_cla = None (the default) keeps the unperturbed images' logits per set of view ids while the
     classifier is a frozen pure function (every module in eval() mode, no parameter requiring grad: AS:281-287) - the loop of
