@@ -1122,6 +1122,46 @@ int nerfail_cnn_bwd_weights(const float* packed, int num_classes, const float* x
                             const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch,
                             float* d_params, float* d_x /* or NULL */, void* stream);
 
+/* bf16x3: a second, opt-in arithmetic for the victim's conv stages 2..7, forward and backward-data, on
+ * v_mfma_f32_32x32x16_bf16 (csrc/cnn_x3.hip). Only ADDS entry points: NERFAIL_ABI_VERSION stays 14, nerfail_abi_revision() stays
+ * 15, every other revision stays 1, and the additions are announced by nerfail_cnn_x3_revision() = 1. The exact entry points
+ * above, their kernels and their bits are unchanged.
+ * Arithmetic: both operands of every product are split by three round-to-nearest-even conversions to bf16 (8 significant
+ * bits), x = x0 + x1 + x2 with |x1| <= 2^-8 |x|, |x2| <= 2^-16 |x| and each subtraction exact in f32; nothing is left over
+ * while the pieces are normal numbers. Of the nine piece products the six a1b1, a0b2, a2b0, a0b1, a1b0, a0b0 are kept and issued
+ * in that order (smallest first) into ONE f32 accumulator per output element, one step of 16 channels (k16) after another in a
+ * fixed order (the nine taps of a 16-channel slice, the slices ascending). A bf16 x bf16 product is exact in f32; what is
+ * dropped (a1b2 + a2b1 + a2b2) is at most 2^-23 |a||b| per product in the worst case, about 2^-26 |a||b| on average, per
+ * product. The results are f32-accurate, not bitwise those of the exact kernels. No float atomics, every output is written by
+ * one lane, two calls give the same bits.
+ * Special values: bf16 has the f32 exponent range, so nothing is pre-scaled. A NaN is NaN in all three pieces: NaN inputs give
+ * NaN at the positions where the exact kernels give NaN. +-Inf (and a finite |x| >= 2^128 (1 - 2^-9), which rounds to a bf16
+ * Inf) becomes NaN, because Inf - Inf happens in the split.
+ * Scope: stage 1 in both directions, the FC head in both directions and every weight gradient stay on the exact kernels, called
+ * as they are: the x3 forward's stage-1 output and mask codes are bit for bit the exact forward's. Activations and gradients
+ * stay f32 in global memory: workspace, masks, scratch and d_x have exactly the contracts, sizes and size functions of
+ * nerfail_cnn_fwd / nerfail_cnn_bwd_data / nerfail_cnn_bwd_data_multi, so what an x3 forward wrote can be consumed by either
+ * backward family and vice versa. The refusals are the exact entry points' (shapes, NULL pointers, R * B <= 65535); slice r of
+ * nerfail_cnn_bwd_data_multi_x3 is bit for bit nerfail_cnn_bwd_data_x3 of row r.
+ *   packed_x3:  nerfail_cnn_x3_packed_bytes(num_classes) bytes (0 for an unsupported num_classes; the size does not depend on
+ *               it otherwise), 16-byte aligned, made by nerfail_cnn_pack_x3 from `packed` on the device. For stage s = 1..6,
+ *               back to back, the forward image and then the backward image, each the split of the same region of `packed`
+ *               (forward [Cout][tap][Cin], backward [Cin][tap][Cout], written [NC][9][KC] here):
+ *                   [KC / 16 slices][NC rows][9 taps][3 planes][16 channels] bf16,
+ *               plane p = piece p of the split (largest first), channel c of slice cb = K-channel 16 cb + c.
+ *   Every x3 call takes `packed` as well (bias, stage 1, the FC head). */
+int nerfail_cnn_x3_revision(void);
+size_t nerfail_cnn_x3_packed_bytes(int num_classes);
+int nerfail_cnn_pack_x3(const float* packed, int num_classes, void* packed_x3, void* stream);
+int nerfail_cnn_fwd_x3(const float* packed, const void* packed_x3, int num_classes, const float* x, int B, int H, int W,
+                       float* workspace, unsigned char* masks, float* logits, void* stream);
+int nerfail_cnn_bwd_data_x3(const float* packed, const void* packed_x3, int num_classes, const float* workspace,
+                            const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch, float* d_x,
+                            void* stream);
+int nerfail_cnn_bwd_data_multi_x3(const float* packed, const void* packed_x3, int num_classes, const float* workspace,
+                                  const unsigned char* masks, const float* d_logits /* [R,B,num_classes] */, int R, int B, int H,
+                                  int W, float* scratch, float* d_x /* [R,B,3,H,W] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -294,7 +294,8 @@ class gauss_net(_EpsilonRange, nn.Module):
         m = self.model
         if not isinstance(m, nn.Module):
             return None
-        return tuple((t.data_ptr(), t._version) for t in list(m.parameters()) + list(m.buffers()))
+        # (a victim's arithmetic, MyCNN.precision, is part of its state: logits cached under one mode are not the other's)
+        return tuple((t.data_ptr(), t._version) for t in list(m.parameters()) + list(m.buffers())) + (getattr(m, 'precision', None),)
 
     def attack_forward(self, spatial_rgb, weight_and_index_list, ori_img, view_ids=None):
         """The forward of one NeRFail-S step (AS:317) without what that step never uses: no `x` tensor (GN:83), no float copy

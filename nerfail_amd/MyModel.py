@@ -32,9 +32,12 @@ from ._images import ImageCache
 
 
 class MyCNN(nn.Module):
-    def __init__(self, num_classes=24, trainable=False):
+    PRECISIONS = ('f32', 'bf16x3')
+
+    def __init__(self, num_classes=24, trainable=False, precision='f32'):
         super().__init__()
         self.trainable = bool(trainable)
+        self.precision = precision
         chans = (3, 32, 64, 128, 256, 256, 128, 64)
         for i in range(7):
             setattr(self, 'conv%d' % (i + 1), nn.Conv2d(chans[i], chans[i + 1], 3))
@@ -42,8 +45,19 @@ class MyCNN(nn.Module):
         self.fc1 = nn.Linear(1024, 512)
         self.fc2 = nn.Linear(512, num_classes)
         self.num_classes = num_classes
-        self._images = ImageCache(self._params, {'packed': (self._pack, None)})
+        self._images = ImageCache(self._params, {'packed': (self._pack, None), 'x3': (self._pack_x3, 'packed')})
         self._flat = None
+
+    @property
+    def precision(self):
+        """'f32' (the exact kernels) or 'bf16x3' (conv stages 2..7 on bf16 MFMAs, f32-accurate). Assignable."""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        if value not in self.PRECISIONS:
+            raise ValueError('MyCNN: precision must be one of %s (got %r)' % (self.PRECISIONS, value))
+        self._precision = value
 
     def _params(self):
         ps = []
@@ -66,6 +80,34 @@ class MyCNN(nn.Module):
         """The MFMA weight image (nerfail_cnn_pack), cached like NeRF's (_images.ImageCache): rebuilt when any parameter
         moves or is written in place."""
         return self._images.get('packed')
+
+    def _pack_x3(self, packed):
+        return ops.cnn_pack_x3(packed, self.num_classes)
+
+    def packed_x3(self):
+        """The bf16x3 image of stages 2..7 (nerfail_cnn_pack_x3), made from packed() and cached beside it: re-made exactly when
+        packed() is (a parameter write or move), dropped by sgd_step()."""
+        return self._images.get('x3')
+
+    def forward_masks(self, x):
+        """(logits, workspace, masks) of a forward that keeps its pool masks, in this module's precision, without an autograd
+        graph: what the graph-free attack loops hand to backward_data()."""
+        with torch.no_grad():
+            if self._precision == 'bf16x3':
+                return ops.cnn_fwd_x3(self.packed(), self.packed_x3(), x, self.num_classes, True)
+            return ops.cnn_fwd(self.packed(), x, self.num_classes, True)
+
+    def backward_data(self, workspace, masks, d_logits, H, W):
+        """The input gradient from the buffers of forward_masks(), in this module's precision: d_logits [B,num_classes] ->
+        [B,3,H,W] (one backward), d_logits [R,B,num_classes] -> [R,B,3,H,W] (the multi backward, slice r bitwise the single
+        backward of row r)."""
+        multi = d_logits.dim() == 3
+        with torch.no_grad():
+            if self._precision == 'bf16x3':
+                op = ops.cnn_bwd_data_multi_x3 if multi else ops.cnn_bwd_data_x3
+                return op(self.packed(), self.packed_x3(), workspace, masks, d_logits, H, W)
+            op = ops.cnn_bwd_data_multi if multi else ops.cnn_bwd_data
+            return op(self.packed(), workspace, masks, d_logits, H, W)
 
     def _is_flat(self):
         """True while every parameter still is the view of self._flat that flatten_parameters() made it (.to(), a deep copy
@@ -122,12 +164,19 @@ class MyCNN(nn.Module):
         if not x.is_contiguous():
             raise ValueError('MyCNN: the input must be a contiguous NCHW tensor')
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self._precision != 'f32':
+                raise RuntimeError('MyCNN: the training path is exact f32 only - a forward that needs weight gradients cannot run '
+                                   'with precision=%r; set precision=\'f32\', freeze the classifier (requires_grad_(False)) or '
+                                   'run under torch.no_grad()' % (self._precision,))
             if self.trainable:
                 return ops.CnnTrainFn.apply(self, x, *self._params())
             raise RuntimeError('MyCNN: weight gradients are not enabled on this module - construct it with trainable=True, freeze '
                                'the classifier (requires_grad_(False)) or run under torch.no_grad()')
         keep = torch.is_grad_enabled() and x.requires_grad
-        logits, _, _ = ops.cnn_fwd(self.packed(), x, self.num_classes, keep)
+        if self._precision == 'bf16x3':
+            logits, _, _ = ops.cnn_fwd_x3(self.packed(), self.packed_x3(), x, self.num_classes, keep)
+        else:
+            logits, _, _ = ops.cnn_fwd(self.packed(), x, self.num_classes, keep)
         return logits
 
     def input_gradients(self, logits, d_logits):
@@ -141,7 +190,7 @@ class MyCNN(nn.Module):
         if saved is None:
             raise RuntimeError('MyCNN.input_gradients: `logits` is not the output of a mask-keeping forward of a MyCNN (a '
                                'grad-enabled forward of an input that requires grad, its graph not yet freed)')
-        packed, ws, masks, (H, W) = saved
+        packed, ws, masks, (H, W), packed_x3 = saved
         if not self._images.holds('packed', packed):
             raise RuntimeError('MyCNN.input_gradients: `logits` did not come from the last weight image of this module '
                                '(another module\'s forward, or the parameters were written and repacked since)')
@@ -153,4 +202,6 @@ class MyCNN(nn.Module):
                              % (logits.shape[0], logits.shape[1], tuple(getattr(d_logits, 'shape', ()))))
         if d_logits.shape[0] < 1:
             raise ValueError('MyCNN.input_gradients: d_logits holds no right-hand side (R = 0)')
+        if packed_x3 is not None:                    # the family that made `logits`, whatever self.precision is now
+            return ops.cnn_bwd_data_multi_x3(packed, packed_x3, ws, masks, _lib.f32c(d_logits, logits.device), H, W)
         return ops.cnn_bwd_data_multi(packed, ws, masks, _lib.f32c(d_logits, logits.device), H, W)

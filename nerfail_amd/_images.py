@@ -1,4 +1,4 @@
-"""One versioned cache for the device weight images of a module (NeRF: f32, f32_T, x3, x3f, f16, f16_T; MyCNN: packed).
+"""One versioned cache for the device weight images of a module (NeRF: f32, f32_T, x3, x3f, f16, f16_T; MyCNN: packed, x3).
 
 Plain Python: no library, no GPU, not an nn.Module (state_dict(), parameters() and .to() of the owner never see it). The
 owner hands in `params`, a callable returning its parameters in one fixed order, and a table name -> (pack, source):

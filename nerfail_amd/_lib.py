@@ -21,6 +21,7 @@ U2D_REVISION = 1                         # nerfail_u2d_revision: the IGSM-2D bas
 UAP2D_REVISION = 1                       # nerfail_uap2d_revision: the UAP-2D baseline's DeepFool step and projection (attack.uap_2d)
 POISON_REVISION = 1                      # nerfail_poison_revision: the export -> training-target hand-off (retrain.PoisonedTrainSet)
 RESIZE_REVISION = 1                      # nerfail_resize_revision: the classifier-input resize and its adjoint (_resize.classifier_input)
+CNN_X3_REVISION = 1                      # nerfail_cnn_x3_revision: the bf16x3 arithmetic of the MyCNN victim (MyCNN(precision='bf16x3'))
 FG_REVISION = 1                          # nerfail_fg_revision: pixel list, list rays and list search of foreground-only scene maps (scene)
 RESIZE_MAX_TAPS = 16                     # NERFAIL_RESIZE_MAX_TAPS
 UAP2D_NORM_TERMS = 24                   # NERFAIL_UAP2D_NORM_TERMS: float32 terms per lane of nerfail_uap2d_step's norms
@@ -227,6 +228,12 @@ SIGNATURES = {
     'nerfail_cnn_grad_floats': (ctypes.c_size_t, [c_i]),
     'nerfail_cnn_bwd_weights_scratch_bytes': (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     'nerfail_cnn_bwd_weights': (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    'nerfail_cnn_x3_revision': (c_i, []),
+    'nerfail_cnn_x3_packed_bytes': (ctypes.c_size_t, [c_i]),
+    'nerfail_cnn_pack_x3': (c_i, [c_p, c_i, c_p, c_p]),
+    'nerfail_cnn_fwd_x3': (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    'nerfail_cnn_bwd_data_x3': (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'nerfail_cnn_bwd_data_multi_x3': (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
 }
 
 
@@ -300,6 +307,9 @@ def load():
     if lib.nerfail_fg_revision() != FG_REVISION:
         raise RuntimeError('nerfail_amd: foreground scene-maps revision %d, expected %d - rebuild the library'
                            % (lib.nerfail_fg_revision(), FG_REVISION))
+    if lib.nerfail_cnn_x3_revision() != CNN_X3_REVISION:
+        raise RuntimeError('nerfail_amd: bf16x3 victim revision %d, expected %d - rebuild the library'
+                           % (lib.nerfail_cnn_x3_revision(), CNN_X3_REVISION))
     _lib = lib
     return lib
 

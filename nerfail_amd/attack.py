@@ -791,8 +791,9 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
     on_export None no image is copied to the host. None (the default) leaves the loop as it is.
 
     The classifier. `native=None` (automatic) or True (insist): when `model` is this package's MyCNN and model_name is
-    "my_model", a step is ops.cnn_fwd with its pool masks, ops.cls_ce with a constant label vector for d loss / d logits,
-    ops.cnn_bwd_data and the step kernel - no autograd graph and no torch op between the launches. Any other classifier, or
+    "my_model", a step is MyCNN.forward_masks (ops.cnn_fwd with its pool masks; the bf16x3 ops when the victim's precision is
+    'bf16x3'), ops.cls_ce with a constant label vector for d loss / d logits, MyCNN.backward_data (ops.cnn_bwd_data[_x3]) and the
+    step kernel - no autograd graph and no torch op between the launches. Any other classifier, or
     native=False: the classifier input requires grad, then the resize, the model and autograd.grad. Both paths take
     d loss / d logits of nn.CrossEntropyLoss() from ONE definition, ops.cls_ce ((softmax - onehot) / B, evaluated in double and
     rounded once): torch's float32 backward of the same loss differs from it in the last bits, which measured flipped the sign
@@ -839,10 +840,10 @@ def igsm_2d(model, model_name, images, label, epochs, a=2., epsilon=32., targete
                 x_rgb, cls_in, mask = ops.u2d_fwd(images, ib, table, True, True, True)
             if use_native:
                 with torch.no_grad():
-                    cla, ws, pool = ops.cnn_fwd(model.packed(), cls_in, model.num_classes, True)
+                    cla, ws, pool = model.forward_masks(cls_in)
                     batch_stats(epoch, lo, hi, cla, x_rgb)
                     d_logits = ops.cls_ce(cla, lab32[:B], ce_row, True)                      # (softmax - onehot) / B
-                    d_in = ops.cnn_bwd_data(model.packed(), ws, pool, d_logits, H, W)
+                    d_in = model.backward_data(ws, pool, d_logits, H, W)
             else:
                 cls_in.requires_grad_()
                 cla = store.classify(cls_in)

@@ -42,9 +42,6 @@ namespace cnn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-static size_t act_floats(const Dims& d, int s, int B) { return (size_t)B * d.hin[s + 1] * d.win[s + 1] * stage_cout(s); }
-static size_t mask_bytes_of(const Dims& d, int s, int B) { return (size_t)B * d.hin[s + 1] * npc8(d.win[s + 1]) * 2 * stage_cout(s); }
-
 // ---------------------------------------------------------------------------------------------------------------- pack
 // One thread per element of the image; the source index is recomputed from the destination's.
 
@@ -86,19 +83,7 @@ __global__ void pack_fc1_kernel(const float* __restrict__ w, float* __restrict__
 // Workgroup: 4 waves, each 2 m-tiles x NT n-tiles. Forward: 8 x 8 pooled cells (wave w: pooled rows 2w, 2w+1; an m-tile is one
 // pooled row of 8 cells = 2 x 16 conv pixels). Backward: 8 rows x 32 columns of stage-input pixels (an m-tile is 32 pixels of
 // one row).
-struct ConvArgs {
-    const float* in;           // forward: stage input (NHWC, or NCHW for MODE 1)
-    const float* w;            // weight image of this stage and direction
-    const float* bias;         // forward
-    float* out;                // forward: pooled NHWC; backward: d input NHWC
-    unsigned char* mask;       // forward: argmax codes (NULL = inference)
-    const float* gp;           // backward: d pooled output (NHWC)
-    const float* act;          // backward: pooled output (NHWC)
-    const unsigned char* gmask;// backward: argmax codes of the forward
-    int hin, win, hp, wp;      // stage input and pooled output sizes
-    int B;                     // backward: images of the forward (grid z = r * B + b covers the R right-hand sides)
-};
-
+// (ConvArgs: cnn_layout.h)
 template <int MODE>
 struct Geo {
     static constexpr int TH = MODE == 2 ? 10 : 18;
@@ -795,14 +780,9 @@ extern "C" size_t nerfail_cnn_bwd_scratch_bytes(int B, int H, int W) {
     return (act_floats(d, 0, B) + act_floats(d, 1, B)) * sizeof(float);
 }
 
-extern "C" int nerfail_cnn_fwd(const float* packed, int num_classes, const float* x, int B, int H, int W, float* workspace,
-                               unsigned char* masks, float* logits, void* stream) {
-    Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && x != nullptr && workspace != nullptr && logits != nullptr,
-               "packed, x, workspace or logits is NULL");
+// The forward launch chain (arguments already validated). x3 = NULL: the exact kernels; else stages 2..7 on the bf16x3 image.
+static int fwd_launch(const float* packed, const void* x3, int num_classes, const float* x, int B, const Dims& d, float* workspace,
+                      unsigned char* masks, float* logits, void* stream) {
     const PackLayout L = pack_layout(num_classes);
     hipStream_t st = as_stream(stream);
     const float* in = x;
@@ -819,7 +799,7 @@ extern "C" int nerfail_cnn_fwd(const float* packed, int num_classes, const float
         a.win = d.win[s];
         a.hp = d.hin[s + 1];
         a.wp = d.win[s + 1];
-        int rc = conv_fwd_stage(s, a, B, st);
+        int rc = (x3 && s >= 1) ? conv_fwd_stage_x3(s, a, x3, B, st) : conv_fwd_stage(s, a, B, st);
         if (rc) return rc;
         in = act;
         act += act_floats(d, s, B);
@@ -829,6 +809,28 @@ extern "C" int nerfail_cnn_fwd(const float* packed, int num_classes, const float
                                                      act, logits);
     NF_LAUNCHED("cnn_fc_fwd");
     return 0;
+}
+
+#define NF_CNN_FWD_CHECKS                                                                                              \
+    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");                             \
+    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");                                                         \
+    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");        \
+    NF_REQUIRE(packed != nullptr && x != nullptr && workspace != nullptr && logits != nullptr,                         \
+               "packed, x, workspace or logits is NULL")
+
+extern "C" int nerfail_cnn_fwd(const float* packed, int num_classes, const float* x, int B, int H, int W, float* workspace,
+                               unsigned char* masks, float* logits, void* stream) {
+    Dims d;
+    NF_CNN_FWD_CHECKS;
+    return fwd_launch(packed, nullptr, num_classes, x, B, d, workspace, masks, logits, stream);
+}
+
+extern "C" int nerfail_cnn_fwd_x3(const float* packed, const void* packed_x3, int num_classes, const float* x, int B, int H, int W,
+                                  float* workspace, unsigned char* masks, float* logits, void* stream) {
+    Dims d;
+    NF_CNN_FWD_CHECKS;
+    NF_REQUIRE(packed_x3 != nullptr, "packed_x3 is NULL");
+    return fwd_launch(packed, packed_x3, num_classes, x, B, d, workspace, masks, logits, stream);
 }
 
 // True when R right-hand sides of a B-image forward fit the grid's z dimension (R * B <= 65535).
@@ -841,7 +843,7 @@ extern "C" size_t nerfail_cnn_bwd_multi_scratch_bytes(int R, int B, int H, int W
 }
 
 // The backward launch chain for R right-hand sides of one B-image forward (arguments already validated).
-static int bwd_data_launch(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
+static int bwd_data_launch(const float* packed, const void* x3, int num_classes, const float* workspace, const unsigned char* masks,
                            const float* d_logits, int R, int B, int H, int W, const Dims& d, float* scratch, float* d_x,
                            void* stream) {
     const PackLayout L = pack_layout(num_classes);
@@ -872,7 +874,7 @@ static int bwd_data_launch(const float* packed, int num_classes, const float* wo
         a.hp = d.hin[s + 1];
         a.wp = d.win[s + 1];
         a.B = B;
-        int rc = conv_bwd_stage(s, a, Z, st);
+        int rc = x3 ? conv_bwd_stage_x3(s, a, x3, Z, st) : conv_bwd_stage(s, a, Z, st);
         if (rc) return rc;
     }
     const unsigned tiles = (unsigned)(((W + 15) / 16) * ((H + 15) / 16));
@@ -891,7 +893,7 @@ extern "C" int nerfail_cnn_bwd_data(const float* packed, int num_classes, const 
     NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
     NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
                    d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
-    return bwd_data_launch(packed, num_classes, workspace, masks, d_logits, 1, B, H, W, d, scratch, d_x, stream);
+    return bwd_data_launch(packed, nullptr, num_classes, workspace, masks, d_logits, 1, B, H, W, d, scratch, d_x, stream);
 }
 
 extern "C" int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
@@ -903,7 +905,33 @@ extern "C" int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, 
     NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
     NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
                    d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
-    return bwd_data_launch(packed, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
+    return bwd_data_launch(packed, nullptr, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
+}
+
+// The bf16x3 forms: the same refusals, the same buffers and size functions; stages 7..2 run on the bf16x3 image (cnn_x3.hip),
+// the FC head and stage 1 on the exact kernels above.
+extern "C" int nerfail_cnn_bwd_data_x3(const float* packed, const void* packed_x3, int num_classes, const float* workspace,
+                                       const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch,
+                                       float* d_x, void* stream) {
+    Dims d;
+    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
+    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
+    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
+    NF_REQUIRE(packed != nullptr && packed_x3 != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr &&
+                   scratch != nullptr && d_x != nullptr, "packed, packed_x3, workspace, masks, d_logits, scratch or d_x is NULL");
+    return bwd_data_launch(packed, packed_x3, num_classes, workspace, masks, d_logits, 1, B, H, W, d, scratch, d_x, stream);
+}
+
+extern "C" int nerfail_cnn_bwd_data_multi_x3(const float* packed, const void* packed_x3, int num_classes, const float* workspace,
+                                             const unsigned char* masks, const float* d_logits, int R, int B, int H, int W,
+                                             float* scratch, float* d_x, void* stream) {
+    Dims d;
+    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
+    NF_REQUIRE(multi_ok(R, B), "R and B must be >= 1 with R * B <= 65535 (one grid slice per right-hand side and image)");
+    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
+    NF_REQUIRE(packed != nullptr && packed_x3 != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr &&
+                   scratch != nullptr && d_x != nullptr, "packed, packed_x3, workspace, masks, d_logits, scratch or d_x is NULL");
+    return bwd_data_launch(packed, packed_x3, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- weight gradients

@@ -60,6 +60,51 @@ static PackLayout pack_layout(int C) {
     return L;
 }
 
+static inline size_t act_floats(const Dims& d, int s, int B) { return (size_t)B * d.hin[s + 1] * d.win[s + 1] * stage_cout(s); }
+static inline size_t mask_bytes_of(const Dims& d, int s, int B) { return (size_t)B * d.hin[s + 1] * npc8(d.win[s + 1]) * 2 * stage_cout(s); }
+
+// ---- the bf16x3 weight image of nerfail_cnn_pack_x3 (bytes; cnn_x3.hip reads it, tests/cnn_x3_ref.py restates it).
+// Stages 2..7 (s = 1..6), per stage the forward image and then the backward image, each made from the f32 image of the same
+// stage and direction, which is [NC][9 taps][KC] (forward: NC = Cout, KC = Cin; backward: NC = Cin, KC = Cout, taps not flipped):
+//     [KC / 16 slices][NC rows][9 taps][3 planes][16 channels] bf16
+// plane 0, 1, 2 = the three pieces of the split (bf16_split.h), largest first; element (cb, n, t, p, c) is piece p of the f32
+// image's (n, t, 16 cb + c). The 864 bytes (kX3RowSlots 16-byte slots) of one (slice, row) are what a lane's nine k16 steps read
+// with three ds_read_b128 each (lane half h: channels 8h .. 8h + 7 of a plane), and the rows of an n-block are contiguous.
+// The image does not depend on num_classes.
+constexpr int kX3RowSlots = 9 * 3 * 2;
+struct X3Layout {
+    size_t fwd[kStages], bwd[kStages], total;                   // [0] unused: stage 1 stays exact f32
+};
+static inline X3Layout x3_layout() {
+    X3Layout X;
+    size_t o = 0;
+    X.fwd[0] = X.bwd[0] = 0;
+    for (int s = 1; s < kStages; ++s) {
+        const size_t n = (size_t)stage_cout(s) * stage_cin(s) * 9 * 3 * 2;
+        X.fwd[s] = o; o += n;
+        X.bwd[s] = o; o += n;
+    }
+    X.total = o;
+    return X;
+}
+
+// ---- one conv stage launch: the arguments of conv_stage_kernel (cnn.hip) and conv_x3_kernel (cnn_x3.hip)
+struct ConvArgs {
+    const float* in;           // forward: stage input (NHWC, or NCHW for MODE 1)
+    const float* w;            // weight image of this stage and direction (exact kernels)
+    const float* bias;         // forward
+    float* out;                // forward: pooled NHWC; backward: d input NHWC
+    unsigned char* mask;       // forward: argmax codes (NULL = inference)
+    const float* gp;           // backward: d pooled output (NHWC)
+    const float* act;          // backward: pooled output (NHWC)
+    const unsigned char* gmask;// backward: argmax codes of the forward
+    int hin, win, hp, wp;      // stage input and pooled output sizes
+    int B;                     // backward: images of the forward (grid z = r * B + b covers the R right-hand sides)
+};
+// stages 2..7 (s = 1..6) on the bf16x3 image `x3` (cnn_x3.hip); Z: grid slices (B, or R * B)
+int conv_fwd_stage_x3(int s, const ConvArgs& a, const void* x3, int B, hipStream_t st);
+int conv_bwd_stage_x3(int s, const ConvArgs& a, const void* x3, int Z, hipStream_t st);
+
 // ---- d_params of nerfail_cnn_bwd_weights; also the flat parameter and momentum buffers of nerfail_cnn_sgd_step
 struct GradLayout {                                             // d_params (floats): nn.Module layout, state-dict order
     size_t w[kStages + 2], b[kStages + 2], total;               // 7, 8: fc1, fc2

@@ -29,13 +29,11 @@
 //     boundary sits at the group's second-to-last tile-step (both remaining tile-steps' fragments are in registers when
 //     the slot is released).
 #include "mlp_lds.h"
+#include "bf16_split.h"
 
 namespace nerfail {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const u32x4 lds_cu4;
 typedef __attribute__((address_space(3))) const f32x2 lds_cf2;
 
@@ -93,14 +91,7 @@ static inline bool make_x3f_layout(const MlpLayout& L, int W, X3Layout& X) {
 __host__ __device__ inline unsigned x3f_const_floats(const MlpLayout& L) { return L.total - L.b_off[0]; }
 static inline unsigned x3f_composed_floats(const MlpLayout& L) { return (unsigned)(L.NT / 2 * 32) * (L.NT * 32) + kPiece; }
 
-// x = hi + mid + lo (+ |r| <= 2^-27 |x|) by round-to-nearest, two elements at a time (element 0 in the low half).
-__device__ __forceinline__ unsigned cvt_bf2(float x0, float x1) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0, x1}, bf16x2));
-}
-__device__ __forceinline__ void sub_bf2(float& x0, float& x1, unsigned p) {       // x -= the bf16 pair p, exact
-    x0 -= __uint_as_float(p << 16);
-    x1 -= __uint_as_float(p & 0xffff0000u);
-}
+// (cvt_bf2 / sub_bf2, the three-way split: bf16_split.h)
 
 // ---- the bf16x3 image from the f32 image: one thread per (layer step, tile, lane), 8 weights -> 3 x 16 bytes.
 // The f32 image holds layer l as [quad Q][32-row tile][lane32][4]: weight (row i, k-step 4Q + e) of half h at lane32

@@ -293,7 +293,8 @@ def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_lab
     be left out for a one-view store; an index outside the store is a ValueError) (else
     ori_img, which then must hold whole numbers in 0..255, is taken as a one-view store), and `clean_logits` [1,C] of that view
     (else the classifier runs once on the clean image). Class gradients: with this package's MyCNN under model_name "my_model",
-    ops.cnn_fwd with its pool masks and ONE ops.cnn_bwd_data_multi over the one-hot rows [o] + ks; with any other classifier
+    MyCNN.forward_masks (ops.cnn_fwd with its pool masks, or its bf16x3 form when the victim's precision says so) and ONE
+    MyCNN.backward_data (ops.cnn_bwd_data_multi[_x3]) over the one-hot rows [o] + ks; with any other classifier
     one autograd.grad per row with respect to the classifier input, stacked. Record, scratch, rot, the one-hot rows and the
     trace array are allocated once per call.
 
@@ -361,8 +362,7 @@ def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_lab
         with torch.no_grad():
             _, cls_in, mask = ops.u2d_fwd(store, idx, cur, False, True, True)           # deepfool.py:49 up to the classifier
         if cnn:
-            with torch.no_grad():
-                cla, ws, pool = ops.cnn_fwd(model.packed(), cls_in, C, True)
+            cla, ws, pool = model.forward_masks(cls_in)
         else:
             cls_in.requires_grad_()
             cla = model(u2d_resize(cls_in, name))
@@ -371,8 +371,7 @@ def deepfool_2d_native(net_input, e, net, num_classes=8, max_iter=20, target_lab
         if call.gate(cla, m1, m2):
             break
         if cnn:
-            with torch.no_grad():
-                G = ops.cnn_bwd_data_multi(model.packed(), ws, pool, onehot, hw[0], hw[1])
+            G = model.backward_data(ws, pool, onehot, hw[0], hw[1])
         else:
             G = _lib.f32c(torch.stack([torch.autograd.grad(cla[0, k], cls_in, retain_graph=True)[0] for k in rows]))
         ops.uap2d_step(G, mask.view(-1), call.record, scratch, overshoot, r_0, call.rot, call.out, call.trace_slot())

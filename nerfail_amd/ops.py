@@ -591,17 +591,23 @@ cnn_fwd.register_autograd(_cnn_backward, setup_context=_cnn_setup)
 
 
 def cnn_fwd_saved(logits):
-    """(packed, workspace, masks, (H, W)) that the cnn_fwd call which returned `logits` saved for its backward: read off the
-    tensor's autograd node, so nothing is copied and nothing outlives the graph. None when `logits` is not the direct output
-    of a differentiable cnn_fwd, or when its graph was already freed (a backward without retain_graph)."""
+    """(packed, workspace, masks, (H, W), packed_x3) that the cnn_fwd / cnn_fwd_x3 call which returned `logits` saved for its
+    backward: read off the tensor's autograd node, so nothing is copied and nothing outlives the graph. packed_x3 is None for
+    the exact family (cnn_fwd) and the bf16x3 image for cnn_fwd_x3: it says which backward family matches. None when `logits`
+    is not the direct output of a differentiable cnn_fwd[_x3], or when its graph was already freed (a backward without
+    retain_graph)."""
     node = getattr(logits, 'grad_fn', None)
     if node is None or not getattr(node, 'is_cnn_fwd', False):
         return None
     try:
-        packed, ws, masks = node.saved_tensors
+        saved = node.saved_tensors
     except RuntimeError:
         return None
-    return packed, ws, masks, node.hw
+    if getattr(node, 'is_cnn_x3', False):
+        packed, packed_x3, ws, masks = saved
+        return packed, ws, masks, node.hw, packed_x3
+    packed, ws, masks = saved
+    return packed, ws, masks, node.hw, None
 
 
 def cnn_grad_layout(num_classes):
@@ -686,6 +692,122 @@ class CnnTrainFn(torch.autograd.Function):
 
 
 CNN_OPS = ('cnn_fwd', 'cnn_bwd_data', 'cnn_bwd_data_multi', 'cnn_bwd_weights')
+
+
+# ---- the same victim on the bf16 matrix cores (csrc/cnn_x3.hip): stages 2..7 as six bf16 products per f32 product, f32-accurate.
+# Buffers and sizes are cnn_fwd's: a workspace and masks of one family can be handed to the other family's backward.
+def _x3_image_ok(packed_x3, num_classes, what):
+    if packed_x3.dtype != torch.uint8 or packed_x3.numel() != _lib.load().nerfail_cnn_x3_packed_bytes(num_classes):
+        raise ValueError('%s: packed_x3 is not the bf16x3 image of cnn_pack_x3 (uint8, %d bytes)'
+                         % (what, _lib.load().nerfail_cnn_x3_packed_bytes(num_classes)))
+
+
+@custom_op(NS + '::cnn_pack_x3', mutates_args=(), device_types='cuda')
+def cnn_pack_x3(packed: Tensor, num_classes: int) -> Tensor:
+    """The bf16x3 weight image (uint8 bytes; layout in include/nerfail_hip.h) split on the device from MyCNN.packed()."""
+    lib = _lib.load()
+    if packed.dtype != torch.float32 or packed.numel() != lib.nerfail_cnn_packed_floats(num_classes):
+        raise ValueError('cnn_pack_x3: packed is not the weight image of a %d-class MyCNN' % num_classes)
+    out = torch.empty((lib.nerfail_cnn_x3_packed_bytes(num_classes),), dtype=torch.uint8, device=packed.device)
+    _chk(lib.nerfail_cnn_pack_x3(_lib.dev(packed, 'packed'), num_classes, _lib.dev(out), _s()))
+    return out
+
+
+@cnn_pack_x3.register_fake
+def _(packed, num_classes):
+    return packed.new_empty((_lib.load().nerfail_cnn_x3_packed_bytes(num_classes),), dtype=torch.uint8)
+
+
+@custom_op(NS + '::cnn_fwd_x3', mutates_args=(), device_types='cuda')
+def cnn_fwd_x3(packed: Tensor, packed_x3: Tensor, x: Tensor, num_classes: int, keep_masks: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """cnn_fwd with stages 2..7 on the bf16x3 image: (logits, workspace, masks) with cnn_fwd's shapes and contracts."""
+    B, _, H, W = x.shape
+    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
+    _x3_image_ok(packed_x3, num_classes, 'cnn_fwd_x3')
+    ws = torch.empty((n_ws,), dtype=torch.float32, device=x.device)
+    masks = torch.empty((n_mask,), dtype=torch.uint8, device=x.device)
+    logits = torch.empty((B, num_classes), dtype=torch.float32, device=x.device)
+    _chk(_lib.load().nerfail_cnn_fwd_x3(_lib.dev(packed), _lib.dev(packed_x3), num_classes, _lib.dev(x, 'x'), B, H, W, _lib.dev(ws),
+                                        _lib.dev(masks) if keep_masks else None, _lib.dev(logits), _s()))
+    return logits, ws, masks
+
+
+@cnn_fwd_x3.register_fake
+def _(packed, packed_x3, x, num_classes, keep_masks):
+    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
+    return (x.new_empty((x.shape[0], num_classes)), x.new_empty((n_ws,)), x.new_empty((n_mask,), dtype=torch.uint8))
+
+
+@custom_op(NS + '::cnn_bwd_data_x3', mutates_args=(), device_types='cuda')
+def cnn_bwd_data_x3(packed: Tensor, packed_x3: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
+    """cnn_bwd_data with stages 7..2 on the bf16x3 image."""
+    lib = _lib.load()
+    B, C = d_logits.shape
+    if masks.numel() == 0:
+        raise RuntimeError('cnn_bwd_data_x3: the forward kept no masks (keep_masks=False)')
+    _x3_image_ok(packed_x3, C, 'cnn_bwd_data_x3')
+    nb = lib.nerfail_cnn_bwd_scratch_bytes(B, H, W)
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
+    dx = torch.empty((B, 3, H, W), dtype=torch.float32, device=d_logits.device)
+    _chk(lib.nerfail_cnn_bwd_data_x3(_lib.dev(packed), _lib.dev(packed_x3), C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits),
+                                     B, H, W, _lib.dev(scratch), _lib.dev(dx), _s()))
+    return dx
+
+
+@cnn_bwd_data_x3.register_fake
+def _(packed, packed_x3, workspace, masks, d_logits, H, W):
+    return d_logits.new_empty((d_logits.shape[0], 3, H, W))
+
+
+@custom_op(NS + '::cnn_bwd_data_multi_x3', mutates_args=(), device_types='cuda')
+def cnn_bwd_data_multi_x3(packed: Tensor, packed_x3: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
+    """cnn_bwd_data_multi with stages 7..2 on the bf16x3 image: d_logits [R,B,num_classes] -> [R,B,3,H,W], slice r bitwise
+    cnn_bwd_data_x3(..., d_logits[r], ...)."""
+    lib = _lib.load()
+    if d_logits.dtype != torch.float32:
+        raise TypeError('cnn_bwd_data_multi_x3: d_logits must be float32 (got %s)' % d_logits.dtype)
+    if d_logits.dim() != 3:
+        raise ValueError('cnn_bwd_data_multi_x3: d_logits must be [R,B,num_classes] (got %s)' % (tuple(d_logits.shape),))
+    R, B, C = d_logits.shape
+    if masks.numel() == 0:
+        raise RuntimeError('cnn_bwd_data_multi_x3: the forward kept no masks (keep_masks=False)')
+    _x3_image_ok(packed_x3, C, 'cnn_bwd_data_multi_x3')
+    nb = lib.nerfail_cnn_bwd_multi_scratch_bytes(R, B, H, W)
+    if nb == 0 or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C) or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W):
+        raise ValueError('cnn_bwd_data_multi_x3: unsupported d_logits %s for a %d x %d forward (needs R >= 1, R * B <= 65535 and '
+                         'the workspace and masks of a forward of B images)' % (tuple(d_logits.shape), H, W))
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
+    dx = torch.empty((R, B, 3, H, W), dtype=torch.float32, device=d_logits.device)
+    _chk(lib.nerfail_cnn_bwd_data_multi_x3(_lib.dev(packed), _lib.dev(packed_x3), C, _lib.dev(workspace), _lib.dev(masks),
+                                           _lib.dev(d_logits, 'd_logits'), R, B, H, W, _lib.dev(scratch), _lib.dev(dx), _s()))
+    return dx
+
+
+@cnn_bwd_data_multi_x3.register_fake
+def _(packed, packed_x3, workspace, masks, d_logits, H, W):
+    return d_logits.new_empty((d_logits.shape[0], d_logits.shape[1], 3, H, W))
+
+
+def _cnn_x3_setup(ctx, inputs, output):
+    packed, packed_x3, x, num_classes, keep_masks = inputs
+    _, ws, masks = output
+    ctx.save_for_backward(packed, packed_x3, ws, masks)
+    ctx.hw = (x.shape[2], x.shape[3])
+    ctx.is_cnn_fwd = True
+    ctx.is_cnn_x3 = True                      # cnn_fwd_saved(): this node's backward family is the bf16x3 one
+    ctx.mark_non_differentiable(ws, masks)
+
+
+def _cnn_x3_backward(ctx, g_logits, g_ws, g_masks):
+    packed, packed_x3, ws, masks = ctx.saved_tensors
+    if g_logits is None:
+        return None, None, None, None, None
+    return None, None, cnn_bwd_data_x3(packed, packed_x3, ws, masks, g_logits.contiguous().float(), ctx.hw[0], ctx.hw[1]), None, None
+
+
+cnn_fwd_x3.register_autograd(_cnn_x3_backward, setup_context=_cnn_x3_setup)
+
+CNN_X3_OPS = ('cnn_pack_x3', 'cnn_fwd_x3', 'cnn_bwd_data_x3', 'cnn_bwd_data_multi_x3')
 
 
 # ----------------------------------------------------------------------------------------------- NeRFail-S epoch statistics (AS:319-344, 405-431; ABI 15)

@@ -10,7 +10,12 @@ victim on the automatic setting.
 
 --train: one model_train.py-shaped step (forward, cross-entropy, backward, torch.optim.SGD(lr=1e-3, momentum=0.9) step) at
 B = 16 and B = 8, 800x800: MyCNN(8, trainable=True) (nerfail_cnn_bwd_weights) against the stock module on MIOpen, arms
-alternated, three rounds. The number that matters is the ratio to the stock module in the same session."""
+alternated, three rounds. The number that matters is the ratio to the stock module in the same session.
+
+--x3: the bf16x3 victim (MyCNN(8, precision='bf16x3'), csrc/cnn_x3.hip) against the exact native victim, the same weights, in
+one session: forward at B = 8, forward + input backward at B = 8, the R = 8, B = 1 multi backward, and the NeRFail-S end-to-end
+step. Per arm: HIP events around one call, 5 warm-up calls, then 20 timed calls with the two victims ALTERNATED call by call;
+the median, and max - min as the spread. `faster_beyond_spread` says whether exact - x3 exceeds the sum of the two spreads."""
 import json
 import os
 import sys
@@ -188,13 +193,94 @@ def train_legs(dev, stock, rounds=3):
     return out
 
 
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def alternated(arms, warm=5, n=20):
+    """{arm: {'median_ms', 'spread_ms' (max - min), 'samples_ms'}}: every arm warmed, then n rounds of one call per arm."""
+    for _ in range(warm):
+        for fn in arms.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in arms}
+    for _ in range(n):
+        for k, fn in arms.items():
+            t[k].append(event_ms(fn))
+    return {k: {'median_ms': float(np.median(v)), 'spread_ms': float(max(v) - min(v)), 'samples_ms': [round(x, 4) for x in v]}
+            for k, v in t.items()}
+
+
+def x3_legs(dev, stock):
+    from nerfail_amd.GaussNet import gauss_net
+    from nerfail_amd.MyModel import MyCNN
+    from nerfail_amd.attack import nerfail_s_step
+    victims = {'exact': native_victim(stock)}
+    x3 = MyCNN(8, precision='bf16x3')
+    x3.load_state_dict(victims['exact'].state_dict(), strict=True)
+    victims['bf16x3'] = x3.to(dev).requires_grad_(False).eval()
+    H, W = BS.H, BS.W
+    x8 = torch.rand((8, 3, H, W), device=dev) * 255
+    eye = torch.eye(8, device=dev).reshape(8, 1, 8).contiguous()
+    out = {}
+
+    def fwd(v):
+        def f():
+            with torch.no_grad():
+                v(x8)
+        return f
+
+    def fwd_bwd(v):
+        def f():
+            x = x8.clone().requires_grad_(True)
+            v(x)[:, 4].sum().backward()
+        return f
+
+    def multi(v):
+        _, ws, mk = v.forward_masks(x8[:1].contiguous())
+        return lambda: v.backward_data(ws, mk, eye, H, W)
+    wi, ori, s_init = BS._attack_inputs(dev, 8, seed=0)
+    ori_u8 = ori.to(torch.uint8)
+    label = torch.tensor(4, device=dev)
+    ids = [('victim-bench', b) for b in range(8)]
+
+    def step(v):
+        net = gauss_net(dev, 0.02, v, 'my_model', epsilon=None)
+        s = [s_init.clone()]
+
+        def f():
+            s[0] = nerfail_s_step(net, s[0], s_init, wi, ori_u8, label, 2.0, 32.0, False, view_ids=ids)[0]
+        return f
+    for leg, make in (('forward_b8', fwd), ('forward_input_backward_b8', fwd_bwd), ('multi_backward_r8_b1', multi),
+                      ('nerfail_s_end_to_end_b8', step)):
+        r = alternated({k: make(v) for k, v in victims.items()})
+        e, b = r['exact'], r['bf16x3']
+        out[leg] = {'exact': e, 'bf16x3': b, 'exact_over_bf16x3': e['median_ms'] / b['median_ms'],
+                    'faster_beyond_spread': bool(e['median_ms'] - b['median_ms'] > e['spread_ms'] + b['spread_ms'])}
+    for k in ('exact', 'bf16x3'):
+        out['nerfail_s_end_to_end_b8'][k]['iters_per_sec'] = 1e3 / out['nerfail_s_end_to_end_b8'][k]['median_ms']
+    with torch.no_grad():                                       # faster and different is not faster: the two victims' logits
+        a, b = victims['exact'](x8).double(), victims['bf16x3'](x8).double()
+    out['logits_rel_l2_bf16x3_vs_exact'] = float((a - b).norm() / a.norm())
+    out['note'] = ('HIP events around one call; 5 warm-up calls per arm, then 20 rounds of one call per arm (arms alternated); '
+                   'median and max - min per arm; the same weights in both victims')
+    return out
+
+
 def main():
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     stock = BS.victim_cnn(8).to(dev).requires_grad_(False).eval()
     victims = {'miopen': stock, 'native': native_victim(stock)}
     res = {'device': torch.cuda.get_device_name(0), 'batch': 8, 'size': [BS.H, BS.W]}
-    if '--train' in sys.argv:
+    if '--x3' in sys.argv:
+        res.update(x3_legs(dev, stock))
+    elif '--train' in sys.argv:
         res['batch'] = [16, 8]
         res.update(train_legs(dev, stock))
     elif '--multi' in sys.argv:
