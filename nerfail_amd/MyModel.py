@@ -89,25 +89,28 @@ class MyCNN(nn.Module):
         packed() is (a parameter write or move), dropped by sgd_step()."""
         return self._images.get('x3')
 
+    def _family(self, x3, images=None):
+        """(forward op, backward op, multi backward op, leading weight-image arguments) of the exact family (x3 False) or the
+        bf16x3 family (x3 True): the one place that tells the two apart. images: the ones a forward saved, instead of the
+        module's current ones."""
+        if x3:
+            return ops.cnn_fwd_x3, ops.cnn_bwd_data_x3, ops.cnn_bwd_data_multi_x3, images or (self.packed(), self.packed_x3())
+        return ops.cnn_fwd, ops.cnn_bwd_data, ops.cnn_bwd_data_multi, images or (self.packed(),)
+
     def forward_masks(self, x):
         """(logits, workspace, masks) of a forward that keeps its pool masks, in this module's precision, without an autograd
         graph: what the graph-free attack loops hand to backward_data()."""
         with torch.no_grad():
-            if self._precision == 'bf16x3':
-                return ops.cnn_fwd_x3(self.packed(), self.packed_x3(), x, self.num_classes, True)
-            return ops.cnn_fwd(self.packed(), x, self.num_classes, True)
+            fwd, _, _, images = self._family(self._precision == 'bf16x3')
+            return fwd(*images, x, self.num_classes, True)
 
     def backward_data(self, workspace, masks, d_logits, H, W):
         """The input gradient from the buffers of forward_masks(), in this module's precision: d_logits [B,num_classes] ->
         [B,3,H,W] (one backward), d_logits [R,B,num_classes] -> [R,B,3,H,W] (the multi backward, slice r bitwise the single
         backward of row r)."""
-        multi = d_logits.dim() == 3
         with torch.no_grad():
-            if self._precision == 'bf16x3':
-                op = ops.cnn_bwd_data_multi_x3 if multi else ops.cnn_bwd_data_x3
-                return op(self.packed(), self.packed_x3(), workspace, masks, d_logits, H, W)
-            op = ops.cnn_bwd_data_multi if multi else ops.cnn_bwd_data
-            return op(self.packed(), workspace, masks, d_logits, H, W)
+            _, single, multi, images = self._family(self._precision == 'bf16x3')
+            return (multi if d_logits.dim() == 3 else single)(*images, workspace, masks, d_logits, H, W)
 
     def _is_flat(self):
         """True while every parameter still is the view of self._flat that flatten_parameters() made it (.to(), a deep copy
@@ -173,11 +176,8 @@ class MyCNN(nn.Module):
             raise RuntimeError('MyCNN: weight gradients are not enabled on this module - construct it with trainable=True, freeze '
                                'the classifier (requires_grad_(False)) or run under torch.no_grad()')
         keep = torch.is_grad_enabled() and x.requires_grad
-        if self._precision == 'bf16x3':
-            logits, _, _ = ops.cnn_fwd_x3(self.packed(), self.packed_x3(), x, self.num_classes, keep)
-        else:
-            logits, _, _ = ops.cnn_fwd(self.packed(), x, self.num_classes, keep)
-        return logits
+        fwd, _, _, images = self._family(self._precision == 'bf16x3')
+        return fwd(*images, x, self.num_classes, keep)[0]
 
     def input_gradients(self, logits, d_logits):
         """d (sum(logits * d_logits[r])) / d x for every row r, [R,B,3,H,W], in ONE backward pass.
@@ -202,6 +202,7 @@ class MyCNN(nn.Module):
                              % (logits.shape[0], logits.shape[1], tuple(getattr(d_logits, 'shape', ()))))
         if d_logits.shape[0] < 1:
             raise ValueError('MyCNN.input_gradients: d_logits holds no right-hand side (R = 0)')
-        if packed_x3 is not None:                    # the family that made `logits`, whatever self.precision is now
-            return ops.cnn_bwd_data_multi_x3(packed, packed_x3, ws, masks, _lib.f32c(d_logits, logits.device), H, W)
-        return ops.cnn_bwd_data_multi(packed, ws, masks, _lib.f32c(d_logits, logits.device), H, W)
+        # the family that made `logits` and the images it saved, whatever self.precision is now
+        saved_images = (packed,) if packed_x3 is None else (packed, packed_x3)
+        _, _, multi, images = self._family(packed_x3 is not None, saved_images)
+        return multi(*images, ws, masks, _lib.f32c(d_logits, logits.device), H, W)

@@ -13,6 +13,9 @@
 // A k-unit is 8 k-values: lane half h reads 4 consecutive channels with one ds_read_b128 for each operand, and the unit runs
 // 4 MFMAs per (m-tile, n-tile) pair. No atomics: every output element is written by one lane, sums run in a fixed order.
 // Stage 1's backward (N = 3) and the FC head are small VALU kernels.
+// The workgroup tile, the A-row map, the epilogue, the pool-mask rules (gate, gmask_addr) and the launch grid live in cnn_tile.h,
+// which the bf16x3 kernel (cnn_x3.hip) includes as well; the per-stage launch tables are dispatch_stage (cnn_layout.h) over
+// stage_cin / stage_cout. On the host one chain (bwd_data_chain) runs the backward-data pass for every entry point.
 //
 // Multi-RHS backward (nerfail_cnn_bwd_data_multi): R gradients of ONE forward. The backward kernels run one grid slice per
 // (r, b): slice g = r * B + b indexes every gradient buffer (d logits, gp, out, d x), image b = g % B indexes what the
@@ -35,12 +38,10 @@
 // Bias gradients: the sum of the gated pooled gradient over the pooled cells (db_kernel), through the same slabs. FC head:
 // VALU kernels, one thread per output, the batch summed in order; dW1's columns come out in PyTorch's c * 16 + y * 4 + x.
 #include "common.h"
-#include "cnn_layout.h"
+#include "cnn_tile.h"
 
 namespace nerfail {
 namespace cnn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------------------------- pack
 // One thread per element of the image; the source index is recomputed from the destination's.
@@ -77,23 +78,10 @@ __global__ void pack_fc1_kernel(const float* __restrict__ w, float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------- conv stage
-// MODE 0: forward, NHWC input.  MODE 1: forward, stage 1 (NCHW input, 3 channels padded to 4).  MODE 2: backward-data.
+// MODE, the workgroup's tile, the A-row map, the epilogue and the pool-mask rules: cnn_tile.h, shared with cnn_x3.hip.
 // KC: channels of the K dimension (forward: Cin, backward: Cout); NC: channels of the N dimension (forward: Cout, backward:
 // Cin); NT: 32-wide n-tiles per wave; CC: K channels staged per LDS round.
-// Workgroup: 4 waves, each 2 m-tiles x NT n-tiles. Forward: 8 x 8 pooled cells (wave w: pooled rows 2w, 2w+1; an m-tile is one
-// pooled row of 8 cells = 2 x 16 conv pixels). Backward: 8 rows x 32 columns of stage-input pixels (an m-tile is 32 pixels of
-// one row).
 // (ConvArgs: cnn_layout.h)
-template <int MODE>
-struct Geo {
-    static constexpr int TH = MODE == 2 ? 10 : 18;
-    static constexpr int TW = MODE == 2 ? 34 : 18;
-};
-
-__device__ __forceinline__ int tap_ofs(int mode, int tap, int tw) {
-    const int ky = tap / 3, kx = tap % 3;
-    return mode == 2 ? -(ky * tw + kx) : ky * tw + kx;
-}
 
 // Stage one CC-channel slice of the un-pooled, ReLU-masked output gradient at conv positions (gy0 + r, gx0 + c) into LDS
 // (row stride XS floats); positions outside [0, 2 hp) x [0, 2 wp) get 0 (rows and columns the floor pool dropped, halo).
@@ -108,18 +96,18 @@ __device__ __forceinline__ void stage_grad(float* xs, const float* __restrict__ 
         const int oy = gy0 + p / TW, ox = gx0 + p % TW;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (oy >= 0 && ox >= 0 && oy < 2 * hp && ox < 2 * wp) {
-            const int pr = oy >> 1, pc = ox >> 1, q = ((oy & 1) << 1) | (ox & 1);
+            const int pr = oy >> 1, pc = ox >> 1;
+            const unsigned q = (unsigned)(((oy & 1) << 1) | (ox & 1));
             const size_t cell = ((size_t)b * hp + pr) * wp + pc, gcell = ((size_t)g * hp + pr) * wp + pc;
             const int ch = c0 + 4 * q4;
             const float4 gv = *reinterpret_cast<const float4*>(gp + gcell * KC + ch);
             const float4 av = *reinterpret_cast<const float4*>(act + cell * KC + ch);
-            const unsigned mk = *reinterpret_cast<const unsigned*>(
-                gmask + ((((size_t)b * hp + pr) * n8 + (pc >> 3)) * 2 + (pc & 1)) * KC + ch);
-            const int sh = 2 * ((pc & 7) >> 1);
-            v.x = (((mk >> sh) & 3u) == (unsigned)q && !(av.x <= 0.f)) ? gv.x : 0.f;
-            v.y = (((mk >> (8 + sh)) & 3u) == (unsigned)q && !(av.y <= 0.f)) ? gv.y : 0.f;
-            v.z = (((mk >> (16 + sh)) & 3u) == (unsigned)q && !(av.z <= 0.f)) ? gv.z : 0.f;
-            v.w = (((mk >> (24 + sh)) & 3u) == (unsigned)q && !(av.w <= 0.f)) ? gv.w : 0.f;
+            const unsigned mk = *reinterpret_cast<const unsigned*>(gmask_addr(gmask, b, hp, n8, pr, pc, KC, ch));
+            const int sh = gate_shift(pc);                      // (one byte per channel: channel j's code at bit 8 j + sh)
+            v.x = gate(gv.x, av.x, mk, sh, q);
+            v.y = gate(gv.y, av.y, mk, 8 + sh, q);
+            v.z = gate(gv.z, av.z, mk, 16 + sh, q);
+            v.w = gate(gv.w, av.w, mk, 24 + sh, q);
         }
         *reinterpret_cast<float4*>(xs + p * XS + 4 * q4) = v;
     }
@@ -141,31 +129,11 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
     const int n = lane & 31, h = lane >> 5;
     const int g = blockIdx.z, b = MODE == 2 ? g % a.B : g;      // gradient slice / image (forward: the same)
     const int n0 = blockIdx.y * NT * 32;
-    int ty0, tx0, gy0, gx0;                                     // tile origin: output units / LDS tile in global coordinates
-    if (MODE == 2) {
-        const int nx = (a.win + 31) / 32;
-        ty0 = (blockIdx.x / nx) * 8;
-        tx0 = (blockIdx.x % nx) * 32;
-        gy0 = ty0 - 2;
-        gx0 = tx0 - 2;
-    } else {
-        const int nx = (a.wp + 7) / 8;
-        ty0 = (blockIdx.x / nx) * 8;                            // pooled
-        tx0 = (blockIdx.x % nx) * 8;
-        gy0 = 2 * ty0;
-        gx0 = 2 * tx0;
-    }
-    // LDS pixel of this lane's A row for tap (0,0), per m-tile
+    int ty0, tx0, gy0, gx0;
+    tile_origin<MODE>(a, ty0, tx0, gy0, gx0);
     int abase[2];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        if (MODE == 2) {
-            abase[mt] = (2 * wave + mt + 2) * TW + lane % 32 + 2;
-        } else {
-            const int cell = n >> 2, q = n & 3;
-            abase[mt] = (2 * (2 * wave + mt) + (q >> 1)) * TW + 2 * cell + (q & 1);
-        }
-    }
+    for (int mt = 0; mt < 2; ++mt) abase[mt] = a_row_pixel<MODE>(wave, n, mt);
     // (lane & 31 is both the A row m and the B column n of this lane)
 
     f32x16 acc[2][NT];
@@ -247,49 +215,7 @@ __global__ __launch_bounds__(256) void conv_stage_kernel(ConvArgs a) {
         }
     }
 
-    // ---- epilogue
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int co = n0 + nt * 32 + n;
-            if (MODE == 2) {
-                const int y = ty0 + 2 * wave + mt;
-                if (y < a.hin) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int x = tx0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                        if (x < a.win) a.out[(((size_t)g * a.hin + y) * a.win + x) * NC + co] = acc[mt][nt][i];
-                    }
-                }
-            } else {
-                const int pr = ty0 + 2 * wave + mt;
-                if (pr < a.hp) {
-                    const float bias = a.bias[co];
-                    unsigned code = 0;
-#pragma unroll
-                    for (int w4 = 0; w4 < 4; ++w4) {
-                        float best = -INFINITY;
-                        int bi = 0;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {           // window position j = (dy, dx) row-major; ATen's rule: first max, NaN wins
-                            float v = acc[mt][nt][4 * w4 + j] + bias;
-                            v = v < 0.f ? 0.f : v;              // ReLU (NaN stays NaN)
-                            if (v > best || __builtin_isnan(v)) {
-                                best = v;
-                                bi = j;
-                            }
-                        }
-                        code |= (unsigned)bi << (2 * w4);
-                        const int pc = tx0 + 2 * w4 + h;
-                        if (pc < a.wp) a.out[(((size_t)b * a.hp + pr) * a.wp + pc) * NC + co] = best;
-                    }
-                    if (a.mask)
-                        a.mask[((((size_t)b * a.hp + pr) * npc8(a.wp) + (tx0 >> 3)) * 2 + h) * NC + co] = (unsigned char)code;
-                }
-            }
-        }
-    }
+    epilogue<MODE, NC, NT>(acc, a, g, b, n0, ty0, tx0, wave, n, h);
 }
 
 // Stage 1 backward-data (N = 3 input channels: too narrow for a 32-wide MFMA tile): one thread per input pixel of a 16 x 16
@@ -380,35 +306,27 @@ __global__ __launch_bounds__(1024) void fc_bwd_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------- launches
 template <int MODE, int KC, int NC, int NT, int CC>
 static int launch_conv(const ConvArgs& a, int Z, hipStream_t st, const char* name) {   // Z: grid slices (B, or R * B)
-    unsigned tiles;
-    if (MODE == 2) tiles = (unsigned)(((a.win + 31) / 32) * ((a.hin + 7) / 8));
-    else tiles = (unsigned)(((a.wp + 7) / 8) * ((a.hp + 7) / 8));
-    conv_stage_kernel<MODE, KC, NC, NT, CC><<<dim3(tiles, NC / (NT * 32), Z), dim3(256), 0, st>>>(a);
+    conv_stage_kernel<MODE, KC, NC, NT, CC><<<conv_grid<MODE, NC, NT>(a, Z), dim3(256), 0, st>>>(a);
     NF_LAUNCHED(name);
     return 0;
 }
 
+constexpr int kConvCC = 16;                                     // K channels per LDS round (stage 1's forward: its 4 padded ones)
+
 static int conv_fwd_stage(int s, const ConvArgs& a, int B, hipStream_t st) {
-    switch (s) {
-        case 0: return launch_conv<1, 4, 32, 1, 4>(a, B, st, "cnn_conv_fwd_s1");
-        case 1: return launch_conv<0, 32, 64, 2, 16>(a, B, st, "cnn_conv_fwd_s2");
-        case 2: return launch_conv<0, 64, 128, 2, 16>(a, B, st, "cnn_conv_fwd_s3");
-        case 3: return launch_conv<0, 128, 256, 2, 16>(a, B, st, "cnn_conv_fwd_s4");
-        case 4: return launch_conv<0, 256, 256, 2, 16>(a, B, st, "cnn_conv_fwd_s5");
-        case 5: return launch_conv<0, 256, 128, 2, 16>(a, B, st, "cnn_conv_fwd_s6");
-        default: return launch_conv<0, 128, 64, 2, 16>(a, B, st, "cnn_conv_fwd_s7");
-    }
+    static const char* const name[kStages] = NF_STAGE_LABELS("cnn_conv_fwd");
+    return dispatch_stage(s, [&](auto S) {
+        constexpr int KC = fwd_kc(S), NC = stage_cout(S);
+        return launch_conv<S == 0 ? 1 : 0, KC, NC, conv_nt(NC), S == 0 ? KC : kConvCC>(a, B, st, name[S]);
+    });
 }
 
 static int conv_bwd_stage(int s, const ConvArgs& a, int Z, hipStream_t st) {   // s >= 1: KC = Cout, NC = Cin
-    switch (s) {
-        case 1: return launch_conv<2, 64, 32, 1, 16>(a, Z, st, "cnn_conv_bwd_s2");
-        case 2: return launch_conv<2, 128, 64, 2, 16>(a, Z, st, "cnn_conv_bwd_s3");
-        case 3: return launch_conv<2, 256, 128, 2, 16>(a, Z, st, "cnn_conv_bwd_s4");
-        case 4: return launch_conv<2, 256, 256, 2, 16>(a, Z, st, "cnn_conv_bwd_s5");
-        case 5: return launch_conv<2, 128, 256, 2, 16>(a, Z, st, "cnn_conv_bwd_s6");
-        default: return launch_conv<2, 64, 128, 2, 16>(a, Z, st, "cnn_conv_bwd_s7");
-    }
+    static const char* const name[kStages] = NF_STAGE_LABELS("cnn_conv_bwd");
+    return dispatch_stage(s, [&](auto S) {
+        if constexpr (S == 0) return NERFAIL_EINVAL;            // (stage 1's backward is conv1_bwd_kernel)
+        else return launch_conv<2, stage_cout(S), stage_cin(S), conv_nt(stage_cin(S)), kConvCC>(a, Z, st, name[S]);
+    });
 }
 
 static size_t workspace_floats(const Dims& d, int B) {
@@ -424,6 +342,8 @@ static size_t workspace_floats(const Dims& d, int B) {
 constexpr int kDwTH = 4, kDwTW = 16, kDw1TH = 8, kDw1TW = 32;
 constexpr int kDwWorkgroups = 1024;                             // slabs x channel blocks aimed at per stage
 constexpr size_t kDwPartFloats = (size_t)16 << 20;              // cap of the partial-slab region (64 MB)
+constexpr int kDwWM = 2;                                        // waves over Cout, waves over Cin: a workgroup's channel block
+constexpr int dw_wn(int cin) { return cin >= 64 ? 2 : 1; }
 
 struct DwArgs {
     const float* in;           // stage input: NHWC [B, hin, win, Cin], stage 1: the module's NCHW input
@@ -639,7 +559,7 @@ static DwPlan dw_plan(const Dims& d, int s, int B) {
     p.nty = (d.hin[s] - 2 + th - 1) / th;
     p.ntx = (d.win[s] - 2 + tw - 1) / tw;
     p.ntiles = B * p.nty * p.ntx;
-    p.ny = s == 0 ? 1 : (stage_cout(s) / 64) * (stage_cin(s) / (stage_cin(s) >= 64 ? 64 : 32));
+    p.ny = s == 0 ? 1 : (stage_cout(s) / (32 * kDwWM)) * (stage_cin(s) / (32 * dw_wn(stage_cin(s))));
     p.out = s == 0 ? 1024 : (size_t)stage_cout(s) * 9 * stage_cin(s);
     size_t want = (size_t)(kDwWorkgroups + p.ny - 1) / p.ny;
     if (want > kDwPartFloats / p.out) want = kDwPartFloats / p.out;
@@ -672,38 +592,23 @@ static DwScratch dw_scratch(const Dims& d, int B) {
     return L;
 }
 
-template <int KC, int NC, int WM, int WN>
-static int launch_dw(const DwArgs& a, const DwPlan& p, hipStream_t st, const char* name) {
-    conv_dw_kernel<KC, NC, WM, WN><<<dim3((unsigned)p.slabs, (unsigned)p.ny), dim3(64 * WM * WN), 0, st>>>(a);
-    NF_LAUNCHED(name);
-    return 0;
-}
-
 static int conv_dw_stage(int s, const DwArgs& a, const DwPlan& p, hipStream_t st) {
-    switch (s) {
-        case 0:
-            conv1_dw_kernel<<<dim3((unsigned)p.slabs), dim3(256), 0, st>>>(a);
-            NF_LAUNCHED("cnn_conv_dw_s1");
-            return 0;
-        case 1: return launch_dw<64, 32, 2, 1>(a, p, st, "cnn_conv_dw_s2");
-        case 2: return launch_dw<128, 64, 2, 2>(a, p, st, "cnn_conv_dw_s3");
-        case 3: return launch_dw<256, 128, 2, 2>(a, p, st, "cnn_conv_dw_s4");
-        case 4: return launch_dw<256, 256, 2, 2>(a, p, st, "cnn_conv_dw_s5");
-        case 5: return launch_dw<128, 256, 2, 2>(a, p, st, "cnn_conv_dw_s6");
-        default: return launch_dw<64, 128, 2, 2>(a, p, st, "cnn_conv_dw_s7");
-    }
+    static const char* const name[kStages] = NF_STAGE_LABELS("cnn_conv_dw");
+    return dispatch_stage(s, [&](auto S) {
+        constexpr int WN = dw_wn(stage_cin(S));
+        if constexpr (S == 0) conv1_dw_kernel<<<dim3((unsigned)p.slabs), dim3(256), 0, st>>>(a);
+        else conv_dw_kernel<stage_cout(S), stage_cin(S), kDwWM, WN><<<dim3((unsigned)p.slabs, (unsigned)p.ny), dim3(64 * kDwWM * WN), 0, st>>>(a);
+        NF_LAUNCHED(name[S]);
+        return 0;
+    });
 }
 
 static int db_stage(int s, const float* gp, const float* act, float* part, size_t cells, const DwPlan& p, hipStream_t st) {
-    const dim3 g((unsigned)p.db_slabs), t(256);
-    switch (stage_cout(s)) {
-        case 32: db_kernel<32><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
-        case 64: db_kernel<64><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
-        case 128: db_kernel<128><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
-        default: db_kernel<256><<<g, t, 0, st>>>(gp, act, part, cells, p.db_cps); break;
-    }
-    NF_LAUNCHED("cnn_db");
-    return 0;
+    return dispatch_stage(s, [&](auto S) {
+        db_kernel<stage_cout(S)><<<dim3((unsigned)p.db_slabs), dim3(256), 0, st>>>(gp, act, part, cells, p.db_cps);
+        NF_LAUNCHED("cnn_db");
+        return 0;
+    });
 }
 
 static int reduce_slabs(const float* part, int S, size_t n, int NC, int mode, float* dst, hipStream_t st) {
@@ -811,30 +716,37 @@ static int fwd_launch(const float* packed, const void* x3, int num_classes, cons
     return 0;
 }
 
-#define NF_CNN_FWD_CHECKS                                                                                              \
+// True when R right-hand sides of a B-image forward fit the grid's z dimension (R * B <= 65535).
+static bool multi_ok(int R, int B) { return R >= 1 && B >= 1 && R <= 65535 && B <= 65535 && (long long)R * B <= 65535; }
+
+template <class... P>
+static bool all_set(const P*... p) { return (... && (p != nullptr)); }
+
+// The refusals every forward and backward entry point shares, in this order: num_classes, the batch (BATCH = B, or RB for the
+// multi backward), H x W (fills the caller's Dims `d`), then the pointers of the entry point (`names` lists them for the message).
+#define NF_CNN_BATCH_B NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535")
+#define NF_CNN_BATCH_RB \
+    NF_REQUIRE(multi_ok(R, B), "R and B must be >= 1 with R * B <= 65535 (one grid slice per right-hand side and image)")
+#define NF_CNN_CHECKS(BATCH, d, names, ...)                                                                            \
     NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");                             \
-    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");                                                         \
+    NF_CNN_BATCH_##BATCH;                                                                                              \
     NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");        \
-    NF_REQUIRE(packed != nullptr && x != nullptr && workspace != nullptr && logits != nullptr,                         \
-               "packed, x, workspace or logits is NULL")
+    NF_REQUIRE(all_set(__VA_ARGS__), names " is NULL")
 
 extern "C" int nerfail_cnn_fwd(const float* packed, int num_classes, const float* x, int B, int H, int W, float* workspace,
                                unsigned char* masks, float* logits, void* stream) {
     Dims d;
-    NF_CNN_FWD_CHECKS;
+    NF_CNN_CHECKS(B, d, "packed, x, workspace or logits", packed, x, workspace, logits);
     return fwd_launch(packed, nullptr, num_classes, x, B, d, workspace, masks, logits, stream);
 }
 
 extern "C" int nerfail_cnn_fwd_x3(const float* packed, const void* packed_x3, int num_classes, const float* x, int B, int H, int W,
                                   float* workspace, unsigned char* masks, float* logits, void* stream) {
     Dims d;
-    NF_CNN_FWD_CHECKS;
+    NF_CNN_CHECKS(B, d, "packed, x, workspace or logits", packed, x, workspace, logits);
     NF_REQUIRE(packed_x3 != nullptr, "packed_x3 is NULL");
     return fwd_launch(packed, packed_x3, num_classes, x, B, d, workspace, masks, logits, stream);
 }
-
-// True when R right-hand sides of a B-image forward fit the grid's z dimension (R * B <= 65535).
-static bool multi_ok(int R, int B) { return R >= 1 && B >= 1 && R <= 65535 && B <= 65535 && (long long)R * B <= 65535; }
 
 extern "C" size_t nerfail_cnn_bwd_multi_scratch_bytes(int R, int B, int H, int W) {
     Dims d;
@@ -842,33 +754,40 @@ extern "C" size_t nerfail_cnn_bwd_multi_scratch_bytes(int R, int B, int H, int W
     return (act_floats(d, 0, R * B) + act_floats(d, 1, R * B)) * sizeof(float);
 }
 
-// The backward launch chain for R right-hand sides of one B-image forward (arguments already validated).
-static int bwd_data_launch(const float* packed, const void* x3, int num_classes, const float* workspace, const unsigned char* masks,
-                           const float* d_logits, int R, int B, int H, int W, const Dims& d, float* scratch, float* d_x,
-                           void* stream) {
-    const PackLayout L = pack_layout(num_classes);
-    hipStream_t st = as_stream(stream);
-    const int Z = R * B;                                         // gradient slices: the grid's z (FC head: x) dimension
+// What a forward of B images kept, per stage: its pooled outputs and pool masks in the workspace's and masks' order, then the
+// FC head's hidden layer.
+struct FwdView {
     const float* acts[kStages];
     const unsigned char* mks[kStages];
-    const float* p = workspace;
-    const unsigned char* q = masks;
-    for (int s = 0; s < kStages; ++s) {                          // what the forward kept: B images
-        acts[s] = p;
-        mks[s] = q;
-        p += act_floats(d, s, B);
-        q += mask_bytes_of(d, s, B);
+    const float* hidden;
+};
+static FwdView fwd_view(const float* workspace, const unsigned char* masks, const Dims& d, int B) {
+    FwdView v;
+    for (int s = 0; s < kStages; ++s) {
+        v.acts[s] = workspace;
+        v.mks[s] = masks;
+        workspace += act_floats(d, s, B);
+        masks += mask_bytes_of(d, s, B);
     }
-    float* bufs[2] = {scratch, scratch + act_floats(d, 0, Z)};   // [0] holds stage outputs 6, 4, 2, 0; [1] stage outputs 5, 3, 1
-    fc_bwd_kernel<<<dim3(Z), dim3(kFlat), 0, st>>>(d_logits, p, packed + L.fc1P, packed + L.w2, num_classes, B, bufs[0]);
+    v.hidden = workspace;
+    return v;
+}
+
+// The backward-data chain for Z = R * B gradient slices of one B-image forward (arguments already validated): the FC head,
+// stages 7..2 (x3 = NULL: the exact kernels; else on the bf16x3 image) and stage 1 (d_x = NULL: not wanted). gp[s]: where the
+// gradient of stage s's pooled output lives (Z slices); every caller's layout runs the same kernels, grids and arguments.
+static int bwd_data_chain(const float* packed, const void* x3, int num_classes, const FwdView& v, const float* d_logits, int Z, int B,
+                          const Dims& d, float* const* gp, float* d_x, hipStream_t st) {
+    const PackLayout L = pack_layout(num_classes);
+    fc_bwd_kernel<<<dim3(Z), dim3(kFlat), 0, st>>>(d_logits, v.hidden, packed + L.fc1P, packed + L.w2, num_classes, B, gp[6]);
     NF_LAUNCHED("cnn_fc_bwd");
     for (int s = kStages - 1; s >= 1; --s) {
         ConvArgs a = {};
         a.w = packed + L.bwd[s];
-        a.out = bufs[(s + 1) & 1];                // d (stage s input) = d (stage s-1 output)
-        a.gp = bufs[s & 1];
-        a.act = acts[s];
-        a.gmask = mks[s];
+        a.out = gp[s - 1];                        // d (stage s input) = d (stage s-1 output)
+        a.gp = gp[s];
+        a.act = v.acts[s];
+        a.gmask = v.mks[s];
         a.hin = d.hin[s];
         a.win = d.win[s];
         a.hp = d.hin[s + 1];
@@ -877,35 +796,39 @@ static int bwd_data_launch(const float* packed, const void* x3, int num_classes,
         int rc = x3 ? conv_bwd_stage_x3(s, a, x3, Z, st) : conv_bwd_stage(s, a, Z, st);
         if (rc) return rc;
     }
-    const unsigned tiles = (unsigned)(((W + 15) / 16) * ((H + 15) / 16));
-    conv1_bwd_kernel<<<dim3(tiles, 1, Z), dim3(256), 0, st>>>(packed + L.w1raw, bufs[0], acts[0], mks[0], d_x, H, W, d.hin[1],
-                                                             d.win[1], B);
-    NF_LAUNCHED("cnn_conv1_bwd");
+    if (d_x) {
+        const int H = d.hin[0], W = d.win[0];
+        const unsigned tiles = (unsigned)(((W + 15) / 16) * ((H + 15) / 16));
+        conv1_bwd_kernel<<<dim3(tiles, 1, Z), dim3(256), 0, st>>>(packed + L.w1raw, gp[0], v.acts[0], v.mks[0], d_x, H, W, d.hin[1],
+                                                                 d.win[1], B);
+        NF_LAUNCHED("cnn_conv1_bwd");
+    }
     return 0;
+}
+
+// nerfail_cnn_bwd_data[_multi][_x3]: R right-hand sides of one B-image forward, the gradients in a ping-pong pair of scratch.
+static int bwd_data_launch(const float* packed, const void* x3, int num_classes, const float* workspace, const unsigned char* masks,
+                           const float* d_logits, int R, int B, const Dims& d, float* scratch, float* d_x, void* stream) {
+    const int Z = R * B;                                         // gradient slices: the grid's z (FC head: x) dimension
+    float* const odd = scratch + act_floats(d, 0, Z);            // stage outputs 5, 3, 1; scratch itself: 6, 4, 2, 0
+    float* const gp[kStages] = {scratch, odd, scratch, odd, scratch, odd, scratch};
+    return bwd_data_chain(packed, x3, num_classes, fwd_view(workspace, masks, d, B), d_logits, Z, B, d, gp, d_x, as_stream(stream));
 }
 
 // The single backward is the R = 1 case: the same kernels, the same grid, the same bits.
 extern "C" int nerfail_cnn_bwd_data(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
                                     const float* d_logits, int B, int H, int W, float* scratch, float* d_x, void* stream) {
     Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
-                   d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
-    return bwd_data_launch(packed, nullptr, num_classes, workspace, masks, d_logits, 1, B, H, W, d, scratch, d_x, stream);
+    NF_CNN_CHECKS(B, d, "packed, workspace, masks, d_logits, scratch or d_x", packed, workspace, masks, d_logits, scratch, d_x);
+    return bwd_data_launch(packed, nullptr, num_classes, workspace, masks, d_logits, 1, B, d, scratch, d_x, stream);
 }
 
 extern "C" int nerfail_cnn_bwd_data_multi(const float* packed, int num_classes, const float* workspace, const unsigned char* masks,
                                           const float* d_logits, int R, int B, int H, int W, float* scratch, float* d_x,
                                           void* stream) {
     Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(multi_ok(R, B), "R and B must be >= 1 with R * B <= 65535 (one grid slice per right-hand side and image)");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr && scratch != nullptr &&
-                   d_x != nullptr, "packed, workspace, masks, d_logits, scratch or d_x is NULL");
-    return bwd_data_launch(packed, nullptr, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
+    NF_CNN_CHECKS(RB, d, "packed, workspace, masks, d_logits, scratch or d_x", packed, workspace, masks, d_logits, scratch, d_x);
+    return bwd_data_launch(packed, nullptr, num_classes, workspace, masks, d_logits, R, B, d, scratch, d_x, stream);
 }
 
 // The bf16x3 forms: the same refusals, the same buffers and size functions; stages 7..2 run on the bf16x3 image (cnn_x3.hip),
@@ -914,24 +837,18 @@ extern "C" int nerfail_cnn_bwd_data_x3(const float* packed, const void* packed_x
                                        const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch,
                                        float* d_x, void* stream) {
     Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && packed_x3 != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr &&
-                   scratch != nullptr && d_x != nullptr, "packed, packed_x3, workspace, masks, d_logits, scratch or d_x is NULL");
-    return bwd_data_launch(packed, packed_x3, num_classes, workspace, masks, d_logits, 1, B, H, W, d, scratch, d_x, stream);
+    NF_CNN_CHECKS(B, d, "packed, packed_x3, workspace, masks, d_logits, scratch or d_x", packed, packed_x3, workspace, masks, d_logits,
+                  scratch, d_x);
+    return bwd_data_launch(packed, packed_x3, num_classes, workspace, masks, d_logits, 1, B, d, scratch, d_x, stream);
 }
 
 extern "C" int nerfail_cnn_bwd_data_multi_x3(const float* packed, const void* packed_x3, int num_classes, const float* workspace,
                                              const unsigned char* masks, const float* d_logits, int R, int B, int H, int W,
                                              float* scratch, float* d_x, void* stream) {
     Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(multi_ok(R, B), "R and B must be >= 1 with R * B <= 65535 (one grid slice per right-hand side and image)");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && packed_x3 != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr &&
-                   scratch != nullptr && d_x != nullptr, "packed, packed_x3, workspace, masks, d_logits, scratch or d_x is NULL");
-    return bwd_data_launch(packed, packed_x3, num_classes, workspace, masks, d_logits, R, B, H, W, d, scratch, d_x, stream);
+    NF_CNN_CHECKS(RB, d, "packed, packed_x3, workspace, masks, d_logits, scratch or d_x", packed, packed_x3, workspace, masks, d_logits,
+                  scratch, d_x);
+    return bwd_data_launch(packed, packed_x3, num_classes, workspace, masks, d_logits, R, B, d, scratch, d_x, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- weight gradients
@@ -946,68 +863,32 @@ extern "C" size_t nerfail_cnn_bwd_weights_scratch_bytes(int B, int H, int W, int
     return dw_scratch(d, B).total * sizeof(float);
 }
 
-// The backward-data chain of nerfail_cnn_bwd_data (the same kernels, grids and arguments: the same bits) with every stage's
-// pooled gradient kept in its own region, then the FC head's and every stage's weight and bias gradient.
+// bwd_data_chain with every stage's pooled gradient kept in its own region (d_x as nerfail_cnn_bwd_data's, or NULL), then
+// the FC head's and every stage's weight and bias gradient.
 extern "C" int nerfail_cnn_bwd_weights(const float* packed, int num_classes, const float* x, const float* workspace,
                                        const unsigned char* masks, const float* d_logits, int B, int H, int W, float* scratch,
                                        float* d_params, float* d_x, void* stream) {
     Dims d;
-    NF_REQUIRE(num_classes >= 1 && num_classes <= 4096, "num_classes must be in 1..4096");
-    NF_REQUIRE(B >= 1 && B <= 65535, "B must be in 1..65535");
-    NF_REQUIRE(dims_of(H, W, d), "unsupported H x W: the seventh stage must be 4 x 4 (fc1 takes 1024 inputs)");
-    NF_REQUIRE(packed != nullptr && x != nullptr && workspace != nullptr && masks != nullptr && d_logits != nullptr &&
-                   scratch != nullptr && d_params != nullptr,
-               "packed, x, workspace, masks, d_logits, scratch or d_params is NULL");
+    NF_CNN_CHECKS(B, d, "packed, x, workspace, masks, d_logits, scratch or d_params", packed, x, workspace, masks, d_logits, scratch,
+                  d_params);
     const PackLayout L = pack_layout(num_classes);
     const GradLayout G = grad_layout(num_classes);
     const DwScratch S = dw_scratch(d, B);
     hipStream_t st = as_stream(stream);
-    const float* acts[kStages];
-    const unsigned char* mks[kStages];
-    const float* p = workspace;
-    const unsigned char* q = masks;
-    for (int s = 0; s < kStages; ++s) {
-        acts[s] = p;
-        mks[s] = q;
-        p += act_floats(d, s, B);
-        q += mask_bytes_of(d, s, B);
-    }
-    const float* hidden = p;
+    const FwdView v = fwd_view(workspace, masks, d, B);
     float* gpool[kStages];
     for (int s = 0; s < kStages; ++s) gpool[s] = scratch + S.gpool[s];
     float* dh = scratch + S.dh;
     float* part = scratch + S.part;
 
-    // ---- backward data
-    fc_bwd_kernel<<<dim3(B), dim3(kFlat), 0, st>>>(d_logits, hidden, packed + L.fc1P, packed + L.w2, num_classes, B, gpool[6]);
-    NF_LAUNCHED("cnn_fc_bwd");
-    for (int s = kStages - 1; s >= 1; --s) {
-        ConvArgs a = {};
-        a.w = packed + L.bwd[s];
-        a.out = gpool[s - 1];
-        a.gp = gpool[s];
-        a.act = acts[s];
-        a.gmask = mks[s];
-        a.hin = d.hin[s];
-        a.win = d.win[s];
-        a.hp = d.hin[s + 1];
-        a.wp = d.win[s + 1];
-        a.B = B;
-        int rc = conv_bwd_stage(s, a, B, st);
-        if (rc) return rc;
-    }
-    if (d_x) {
-        const unsigned tiles = (unsigned)(((W + 15) / 16) * ((H + 15) / 16));
-        conv1_bwd_kernel<<<dim3(tiles, 1, B), dim3(256), 0, st>>>(packed + L.w1raw, gpool[0], acts[0], mks[0], d_x, H, W, d.hin[1],
-                                                                 d.win[1], B);
-        NF_LAUNCHED("cnn_conv1_bwd");
-    }
+    int rc = bwd_data_chain(packed, nullptr, num_classes, v, d_logits, B, B, d, gpool, d_x, st);
+    if (rc) return rc;
 
     // ---- FC head
-    fc_dh_kernel<<<dim3(B), dim3(kHidden), 0, st>>>(d_logits, hidden, packed + L.w2, num_classes, dh);
+    fc_dh_kernel<<<dim3(B), dim3(kHidden), 0, st>>>(d_logits, v.hidden, packed + L.w2, num_classes, dh);
     NF_LAUNCHED("cnn_fc_dh");
     const size_t nfc = (size_t)kHidden * kFlat + kHidden + (size_t)num_classes * kHidden + num_classes;
-    fc_dw_kernel<<<dim3((unsigned)((nfc + 255) / 256)), dim3(256), 0, st>>>(d_logits, hidden, dh, acts[6], B, num_classes,
+    fc_dw_kernel<<<dim3((unsigned)((nfc + 255) / 256)), dim3(256), 0, st>>>(d_logits, v.hidden, dh, v.acts[6], B, num_classes,
                                                                            d_params + G.w[7], d_params + G.b[7],
                                                                            d_params + G.w[8], d_params + G.b[8]);
     NF_LAUNCHED("cnn_fc_dw");
@@ -1016,10 +897,10 @@ extern "C" int nerfail_cnn_bwd_weights(const float* packed, int num_classes, con
     for (int s = 0; s < kStages; ++s) {
         const DwPlan pl = dw_plan(d, s, B);
         DwArgs a = {};
-        a.in = s == 0 ? x : acts[s - 1];
+        a.in = s == 0 ? x : v.acts[s - 1];
         a.gp = gpool[s];
-        a.act = acts[s];
-        a.gmask = mks[s];
+        a.act = v.acts[s];
+        a.gmask = v.mks[s];
         a.part = part;
         a.hin = d.hin[s];
         a.win = d.win[s];
@@ -1029,11 +910,11 @@ extern "C" int nerfail_cnn_bwd_weights(const float* packed, int num_classes, con
         a.nty = pl.nty;
         a.ntiles = pl.ntiles;
         a.tps = pl.tps;
-        int rc = conv_dw_stage(s, a, pl, st);
+        rc = conv_dw_stage(s, a, pl, st);
         if (rc) return rc;
         rc = reduce_slabs(part, pl.slabs, pl.out, stage_cin(s), s == 0 ? 2 : 1, d_params + G.w[s], st);
         if (rc) return rc;
-        rc = db_stage(s, gpool[s], acts[s], part, (size_t)B * a.hp * a.wp, pl, st);
+        rc = db_stage(s, gpool[s], v.acts[s], part, (size_t)B * a.hp * a.wp, pl, st);
         if (rc) return rc;
         rc = reduce_slabs(part, pl.db_slabs, stage_cout(s), 0, 0, d_params + G.b[s], st);
         if (rc) return rc;

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <type_traits>
 
 namespace nerfail {
 namespace cnn {
@@ -14,6 +15,22 @@ constexpr int kHidden = 512;
 constexpr int kFlat = 1024;
 __host__ __device__ constexpr int stage_cin(int s) { return s == 0 ? 3 : (s == 1 ? 32 : (s == 2 ? 64 : (s == 3 ? 128 : (s == 6 ? 128 : 256)))); }
 __host__ __device__ constexpr int stage_cout(int s) { return s == 0 ? 32 : (s == 1 ? 64 : (s == 2 ? 128 : (s == 5 ? 128 : (s == 6 ? 64 : 256)))); }
+
+// The one per-stage table: f(std::integral_constant<int, s>) with the run-time stage index s = 0..6 as a compile-time value, so
+// that a launch takes its channel counts from stage_cin(S) / stage_cout(S). Labels: NF_STAGE_LABELS("x")[s] = "x_s<s + 1>".
+template <class F>
+static inline int dispatch_stage(int s, F&& f) {
+    switch (s) {
+        case 0: return f(std::integral_constant<int, 0>());
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 5: return f(std::integral_constant<int, 5>());
+        default: return f(std::integral_constant<int, 6>());
+    }
+}
+#define NF_STAGE_LABELS(p) {p "_s1", p "_s2", p "_s3", p "_s4", p "_s5", p "_s6", p "_s7"}
 
 // ---------------------------------------------------------------------------------------------------------------- host layout
 struct Dims {

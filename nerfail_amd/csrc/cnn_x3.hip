@@ -12,28 +12,27 @@
 // pre-scale. A NaN operand is NaN in all three pieces, so NaN shows where the exact kernel shows it; +-Inf (and a finite
 // value that rounds to a bf16 Inf, |x| >= 2^128 (1 - 2^-9)) becomes NaN, because Inf - Inf happens in the split.
 //
-// Kernel: conv_stage_kernel's implicit GEMM (cnn.hip) on v_mfma_f32_32x32x16_bf16. The same workgroup (4 waves, each 2 m-tiles
-// x NT n-tiles of 32 x 32), the same tiles (forward 8 x 8 pooled cells = 18 x 18 input pixels, backward 8 x 32 input pixels =
-// 10 x 34 gradient positions), the same accumulator-register-to-row map, hence the same epilogue: ReLU, 2 x 2 pool, first-maximum
-// / NaN-wins argmax code and mask byte on the accumulators. A k16 step is the 16 channels of one tap of a 16-channel slice:
-// lane half h holds channels 8h .. 8h+7, one ds_read_b128 per operand and plane.
+// Kernel: an implicit GEMM on v_mfma_f32_32x32x16_bf16 over the workgroup tile of cnn_tile.h, which it shares with the exact
+// conv_stage_kernel (cnn.hip): the tile geometry and origin, the A-row map, the accumulator-register-to-row map and the epilogue
+// on it (ReLU, 2 x 2 pool, first-maximum / NaN-wins argmax code, mask byte), the gate of the un-pooled gradient and the launch
+// grid are the functions there, not copies. What is this file's own: the staging, the LDS layout, the k-loop. A k16 step is the
+// 16 channels of one tap of a 16-channel slice: lane half h holds channels 8h .. 8h+7, one ds_read_b128 per operand and plane.
 //   * B operand: the bf16x3 image (nerfail_cnn_pack_x3, split ONCE on the device from the f32 image; layout in cnn_layout.h):
 //     the [n-block][9 taps][3 planes][16 channels] block of a slice is contiguous there and is copied to LDS as it is.
 //   * A operand: split WHILE it is staged, once per tile element and slice (forward: the input tile; backward: the gated
-//     un-pooled gradient, stage_grad's rule), then read by 9 taps and NT n-tiles.
+//     un-pooled gradient: gate() of cnn_tile.h, as stage_grad in cnn.hip), then read by 9 taps and NT n-tiles.
 //   * Staging: single-buffered LDS behind two barriers per slice, with the global loads of slice c + 1 (A and B, raw, in
 //     registers) issued before the MFMAs of slice c: the L2 latency lies under 216 MFMAs, what stays exposed per slice is the
 //     split (VALU) and the LDS writes. LDS: A 18 x 18 (10 x 34) pixels x 112 bytes (3 planes x 32 + 16 pad: an odd number of
 //     16-byte slots per pixel), B 64 rows x 880 bytes (864 + 16 pad, odd as well: the 16 lanes of a ds_read_b128 group fall on
 //     16 different slots): 36 288 (38 080) + 56 320 bytes, one workgroup per CU, one wave per SIMD.
 #include "common.h"
-#include "cnn_layout.h"
+#include "cnn_tile.h"
 #include "bf16_split.h"
 
 namespace nerfail {
 namespace cnn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -71,16 +70,11 @@ __global__ void pack_x3_conv_kernel(const float* __restrict__ src, u32x4* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------- conv stage
-// MODE 0: forward (stages 2..7, NHWC input).  MODE 2: backward-data. KC, NC, NT as in conv_stage_kernel; the slice is 16 channels.
-template <int MODE>
-struct GeoX3 {
-    static constexpr int TH = MODE == 2 ? 10 : 18;
-    static constexpr int TW = MODE == 2 ? 34 : 18;
-};
-
+// MODE 0: forward (stages 2..7, NHWC input).  MODE 2: backward-data (cnn_tile.h). KC: channels of the K dimension (forward: Cin,
+// backward: Cout), NC: of the N dimension, NT: 32-wide n-tiles per wave (conv_nt); the slice is 16 channels.
 template <int MODE, int KC, int NC, int NT>
 struct StageX3 {
-    static constexpr int TH = GeoX3<MODE>::TH, TW = GeoX3<MODE>::TW;
+    static constexpr int TH = Geo<MODE>::TH, TW = Geo<MODE>::TW;
     static constexpr int AITEMS = TH * TW * 2;                  // (pixel, channel half) items of the A tile
     static constexpr int AIT = (AITEMS + 255) / 256;
     static constexpr int BUNITS = NT * 32 * kX3RowSlots;        // 16-byte units of the B tile
@@ -127,8 +121,7 @@ struct StageX3 {
                         r.v[it][1] = *reinterpret_cast<const float4*>(gs + 4);
                         r.act[it][0] = *reinterpret_cast<const float4*>(as);
                         r.act[it][1] = *reinterpret_cast<const float4*>(as + 4);
-                        r.mk[it] = *reinterpret_cast<const u32x2*>(
-                            a.gmask + ((((size_t)b * a.hp + pr) * npc8(a.wp) + (pc >> 3)) * 2 + (pc & 1)) * KC + ch);
+                        r.mk[it] = *reinterpret_cast<const u32x2*>(gmask_addr(a.gmask, b, a.hp, npc8(a.wp), pr, pc, KC, ch));
                     }
                 }
             }
@@ -142,11 +135,6 @@ struct StageX3 {
         }
     }
 
-    // the gate of stage_grad (cnn.hip): the pooled gradient goes to the stored argmax position where the pooled value is not <= 0
-    static __device__ __forceinline__ float gate(float gv, float av, unsigned mk, int sh, unsigned q) {
-        return (((mk >> sh) & 3u) == q && !(av <= 0.f)) ? gv : 0.f;
-    }
-
     static __device__ __forceinline__ void store(const Regs& r, const ConvArgs& a, char* xs, char* ws, int tid, int gy0, int gx0) {
 #pragma unroll
         for (int it = 0; it < AIT; ++it) {
@@ -156,7 +144,7 @@ struct StageX3 {
             if (MODE == 2) {
                 const int oy = gy0 + p / TW, ox = gx0 + p % TW;
                 const unsigned q = (unsigned)(((oy & 1) << 1) | (ox & 1));
-                const int sh = 2 * (((ox >> 1) & 7) >> 1);
+                const int sh = gate_shift(ox >> 1);
                 const float av[8] = {r.act[it][0].x, r.act[it][0].y, r.act[it][0].z, r.act[it][0].w,
                                      r.act[it][1].x, r.act[it][1].y, r.act[it][1].z, r.act[it][1].w};
 #pragma unroll
@@ -196,29 +184,10 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvArgs a, const u32x4* _
     const int g = blockIdx.z, b = MODE == 2 ? g % a.B : g;
     const int n0 = blockIdx.y * NT * 32;
     int ty0, tx0, gy0, gx0;
-    if (MODE == 2) {
-        const int nx = (a.win + 31) / 32;
-        ty0 = (blockIdx.x / nx) * 8;
-        tx0 = (blockIdx.x % nx) * 32;
-        gy0 = ty0 - 2;
-        gx0 = tx0 - 2;
-    } else {
-        const int nx = (a.wp + 7) / 8;
-        ty0 = (blockIdx.x / nx) * 8;
-        tx0 = (blockIdx.x % nx) * 8;
-        gy0 = 2 * ty0;
-        gx0 = 2 * tx0;
-    }
-    int abase[2];                                               // LDS pixel of this lane's A row for tap (0,0), per m-tile
+    tile_origin<MODE>(a, ty0, tx0, gy0, gx0);
+    int abase[2];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        if (MODE == 2) {
-            abase[mt] = (2 * wave + mt + 2) * TW + n + 2;
-        } else {
-            const int cell = n >> 2, q = n & 3;
-            abase[mt] = (2 * (2 * wave + mt) + (q >> 1)) * TW + 2 * cell + (q & 1);
-        }
-    }
+    for (int mt = 0; mt < 2; ++mt) abase[mt] = a_row_pixel<MODE>(wave, n, mt);
 
     f32x16 acc[2][NT];
 #pragma unroll
@@ -238,7 +207,7 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvArgs a, const u32x4* _
         if (cb + 1 < KC / 16) S::load(regs, a, wimg, tid, g, b, gy0, gx0, n0, cb + 1);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const int tofs = MODE == 2 ? -((t / 3) * TW + t % 3) : (t / 3) * TW + t % 3;
+            const int tofs = tap_ofs(MODE, t, TW);
             u32x4 av[2][3], bv[NT][3];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
@@ -261,83 +230,37 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvArgs a, const u32x4* _
         }
     }
 
-    // ---- epilogue: conv_stage_kernel's (cnn.hip), on the same register-to-row map
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int co = n0 + nt * 32 + n;
-            if (MODE == 2) {
-                const int y = ty0 + 2 * wave + mt;
-                if (y < a.hin) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int x = tx0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                        if (x < a.win) a.out[(((size_t)g * a.hin + y) * a.win + x) * NC + co] = acc[mt][nt][i];
-                    }
-                }
-            } else {
-                const int pr = ty0 + 2 * wave + mt;
-                if (pr < a.hp) {
-                    const float bias = a.bias[co];
-                    unsigned code = 0;
-#pragma unroll
-                    for (int w4 = 0; w4 < 4; ++w4) {
-                        float best = -INFINITY;
-                        int bi = 0;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {           // window position j = (dy, dx) row-major; ATen's rule: first max, NaN wins
-                            float v = acc[mt][nt][4 * w4 + j] + bias;
-                            v = v < 0.f ? 0.f : v;              // ReLU (NaN stays NaN)
-                            if (v > best || __builtin_isnan(v)) {
-                                best = v;
-                                bi = j;
-                            }
-                        }
-                        code |= (unsigned)bi << (2 * w4);
-                        const int pc = tx0 + 2 * w4 + h;
-                        if (pc < a.wp) a.out[(((size_t)b * a.hp + pr) * a.wp + pc) * NC + co] = best;
-                    }
-                    if (a.mask)
-                        a.mask[((((size_t)b * a.hp + pr) * npc8(a.wp) + (tx0 >> 3)) * 2 + h) * NC + co] = (unsigned char)code;
-                }
-            }
-        }
-    }
+    epilogue<MODE, NC, NT>(acc, a, g, b, n0, ty0, tx0, wave, n, h);
 }
 
 template <int MODE, int KC, int NC, int NT>
 static int launch_x3(const ConvArgs& a, const void* img, int Z, hipStream_t st, const char* name) {
-    unsigned tiles;
-    if (MODE == 2) tiles = (unsigned)(((a.win + 31) / 32) * ((a.hin + 7) / 8));
-    else tiles = (unsigned)(((a.wp + 7) / 8) * ((a.hp + 7) / 8));
-    conv_x3_kernel<MODE, KC, NC, NT><<<dim3(tiles, NC / (NT * 32), Z), dim3(256), 0, st>>>(a, static_cast<const u32x4*>(img));
+    conv_x3_kernel<MODE, KC, NC, NT><<<conv_grid<MODE, NC, NT>(a, Z), dim3(256), 0, st>>>(a, static_cast<const u32x4*>(img));
     NF_LAUNCHED(name);
     return 0;
 }
 
-int conv_fwd_stage_x3(int s, const ConvArgs& a, const void* x3, int B, hipStream_t st) {   // s = 1..6 (stages 2..7)
+// s = 1..6 (stages 2..7): stage 1 has no bf16x3 kernel
+#define NF_X3_STAGE_CHECKS NF_REQUIRE(s >= 1 && s < kStages && x3 != nullptr, "stage index outside 1..6, or the bf16x3 image is NULL")
+
+int conv_fwd_stage_x3(int s, const ConvArgs& a, const void* x3, int B, hipStream_t st) {
+    static const char* const name[kStages] = NF_STAGE_LABELS("cnn_x3_conv_fwd");
+    NF_X3_STAGE_CHECKS;
     const void* img = static_cast<const char*>(x3) + x3_layout().fwd[s];
-    switch (s) {
-        case 1: return launch_x3<0, 32, 64, 2>(a, img, B, st, "cnn_x3_conv_fwd_s2");
-        case 2: return launch_x3<0, 64, 128, 2>(a, img, B, st, "cnn_x3_conv_fwd_s3");
-        case 3: return launch_x3<0, 128, 256, 2>(a, img, B, st, "cnn_x3_conv_fwd_s4");
-        case 4: return launch_x3<0, 256, 256, 2>(a, img, B, st, "cnn_x3_conv_fwd_s5");
-        case 5: return launch_x3<0, 256, 128, 2>(a, img, B, st, "cnn_x3_conv_fwd_s6");
-        default: return launch_x3<0, 128, 64, 2>(a, img, B, st, "cnn_x3_conv_fwd_s7");
-    }
+    return dispatch_stage(s, [&](auto S) {
+        if constexpr (S == 0) return NERFAIL_EINVAL;
+        else return launch_x3<0, stage_cin(S), stage_cout(S), conv_nt(stage_cout(S))>(a, img, B, st, name[S]);
+    });
 }
 
-int conv_bwd_stage_x3(int s, const ConvArgs& a, const void* x3, int Z, hipStream_t st) {   // s = 1..6: KC = Cout, NC = Cin
+int conv_bwd_stage_x3(int s, const ConvArgs& a, const void* x3, int Z, hipStream_t st) {   // KC = Cout, NC = Cin
+    static const char* const name[kStages] = NF_STAGE_LABELS("cnn_x3_conv_bwd");
+    NF_X3_STAGE_CHECKS;
     const void* img = static_cast<const char*>(x3) + x3_layout().bwd[s];
-    switch (s) {
-        case 1: return launch_x3<2, 64, 32, 1>(a, img, Z, st, "cnn_x3_conv_bwd_s2");
-        case 2: return launch_x3<2, 128, 64, 2>(a, img, Z, st, "cnn_x3_conv_bwd_s3");
-        case 3: return launch_x3<2, 256, 128, 2>(a, img, Z, st, "cnn_x3_conv_bwd_s4");
-        case 4: return launch_x3<2, 256, 256, 2>(a, img, Z, st, "cnn_x3_conv_bwd_s5");
-        case 5: return launch_x3<2, 128, 256, 2>(a, img, Z, st, "cnn_x3_conv_bwd_s6");
-        default: return launch_x3<2, 64, 128, 2>(a, img, Z, st, "cnn_x3_conv_bwd_s7");
-    }
+    return dispatch_stage(s, [&](auto S) {
+        if constexpr (S == 0) return NERFAIL_EINVAL;
+        else return launch_x3<2, stage_cout(S), stage_cin(S), conv_nt(stage_cin(S))>(a, img, Z, st, name[S]);
+    });
 }
 
 }  // namespace cnn

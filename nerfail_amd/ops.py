@@ -11,6 +11,7 @@ Each op is a `torch.library.custom_op` over ONE entry point of libnerfail_hip.so
 create_gauss_w, igsm_step, knn8, get_rays ...) call these ops. SURVEY's `render_rays_fused_fwd/bwd` is their composition:
 `_train.RenderRaysTrain` (a torch.autograd.Function over ray sampling, mlp_fwd_train, composite, sample_fine and, backwards,
 composite_bwd and mlp_bwd), selected by render_rays whenever a NeRF parameter requires grad."""
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -503,91 +504,156 @@ def _cnn_sizes(x, num_classes, keep_masks):
     return ws // 4, (lib.nerfail_cnn_mask_bytes(B, H, W) if keep_masks else 0)
 
 
+def _x3_image_ok(packed_x3, num_classes, what):
+    if packed_x3.dtype != torch.uint8 or packed_x3.numel() != _lib.load().nerfail_cnn_x3_packed_bytes(num_classes):
+        raise ValueError('%s: packed_x3 is not the bf16x3 image of cnn_pack_x3 (uint8, %d bytes)'
+                         % (what, _lib.load().nerfail_cnn_x3_packed_bytes(num_classes)))
+
+
+# One body per op pair. packed_x3 = None: the exact family (cnn_fwd, cnn_bwd_data[_multi]); else the bf16x3 family (csrc/cnn_x3.hip:
+# stages 2..7 as six bf16 products per f32 product, f32-accurate), whose entry points take the bf16x3 image after `packed`.
+# Buffers and sizes are the same: a workspace and masks of one family can be handed to the other family's backward. `op` names
+# the op that was called in the error texts.
+def _cnn_call(entry, packed, packed_x3, *args):
+    lib = _lib.load()
+    if packed_x3 is None:
+        _chk(getattr(lib, 'nerfail_cnn_' + entry)(_lib.dev(packed), *args))
+    else:
+        _chk(getattr(lib, 'nerfail_cnn_%s_x3' % entry)(_lib.dev(packed), _lib.dev(packed_x3), *args))
+
+
+def _cnn_masks_kept(op, masks, packed_x3, num_classes):
+    if masks.numel() == 0:
+        raise RuntimeError('%s: the forward kept no masks (%skeep_masks=False)' % (op, '' if packed_x3 is not None else 'cnn_fwd with '))
+    if packed_x3 is not None:
+        _x3_image_ok(packed_x3, num_classes, op)
+
+
+def _cnn_fwd(op, packed, packed_x3, x, num_classes, keep_masks):
+    B, _, H, W = x.shape
+    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
+    if packed_x3 is not None:
+        _x3_image_ok(packed_x3, num_classes, op)
+    ws = torch.empty((n_ws,), dtype=torch.float32, device=x.device)
+    masks = torch.empty((n_mask,), dtype=torch.uint8, device=x.device)
+    logits = torch.empty((B, num_classes), dtype=torch.float32, device=x.device)
+    _cnn_call('fwd', packed, packed_x3, num_classes, _lib.dev(x, 'x'), B, H, W, _lib.dev(ws), _lib.dev(masks) if keep_masks else None,
+              _lib.dev(logits), _s())
+    return logits, ws, masks
+
+
+def _cnn_fwd_fake(x, num_classes, keep_masks):
+    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
+    return (x.new_empty((x.shape[0], num_classes)), x.new_empty((n_ws,)), x.new_empty((n_mask,), dtype=torch.uint8))
+
+
+def _cnn_bwd_data(op, packed, packed_x3, workspace, masks, d_logits, H, W):
+    lib = _lib.load()
+    B, C = d_logits.shape
+    _cnn_masks_kept(op, masks, packed_x3, C)
+    nb = lib.nerfail_cnn_bwd_scratch_bytes(B, H, W)
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
+    dx = torch.empty((B, 3, H, W), dtype=torch.float32, device=d_logits.device)
+    _cnn_call('bwd_data', packed, packed_x3, C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits), B, H, W, _lib.dev(scratch),
+              _lib.dev(dx), _s())
+    return dx
+
+
+def _cnn_bwd_data_multi(op, packed, packed_x3, workspace, masks, d_logits, H, W):
+    lib = _lib.load()
+    if d_logits.dtype != torch.float32:
+        raise TypeError('%s: d_logits must be float32 (got %s)' % (op, d_logits.dtype))
+    if d_logits.dim() != 3:
+        raise ValueError('%s: d_logits must be [R,B,num_classes] (got %s)' % (op, tuple(d_logits.shape),))
+    R, B, C = d_logits.shape
+    _cnn_masks_kept(op, masks, packed_x3, C)
+    nb = lib.nerfail_cnn_bwd_multi_scratch_bytes(R, B, H, W)
+    if nb == 0 or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C) or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W):
+        raise ValueError('%s: unsupported d_logits %s for a %d x %d forward (needs R >= 1, R * B <= 65535 and '
+                         'the workspace and masks of a forward of B images)' % (op, tuple(d_logits.shape), H, W))
+    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
+    dx = torch.empty((R, B, 3, H, W), dtype=torch.float32, device=d_logits.device)
+    _cnn_call('bwd_data_multi', packed, packed_x3, C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits, 'd_logits'), R, B, H, W,
+              _lib.dev(scratch), _lib.dev(dx), _s())
+    return dx
+
+
 @custom_op(NS + '::cnn_fwd', mutates_args=(), device_types='cuda')
 def cnn_fwd(packed: Tensor, x: Tensor, num_classes: int, keep_masks: bool) -> tuple[Tensor, Tensor, Tensor]:
     """MyCNN forward: (logits [B,num_classes], workspace (saved activations), masks (pool argmax codes; empty unless
     keep_masks)). packed = nerfail_amd.MyModel.MyCNN.packed(). Differentiable with respect to x when keep_masks is set."""
-    B, _, H, W = x.shape
-    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
-    ws = torch.empty((n_ws,), dtype=torch.float32, device=x.device)
-    masks = torch.empty((n_mask,), dtype=torch.uint8, device=x.device)
-    logits = torch.empty((B, num_classes), dtype=torch.float32, device=x.device)
-    _chk(_lib.load().nerfail_cnn_fwd(_lib.dev(packed), num_classes, _lib.dev(x, 'x'), B, H, W, _lib.dev(ws),
-                                     _lib.dev(masks) if keep_masks else None, _lib.dev(logits), _s()))
-    return logits, ws, masks
+    return _cnn_fwd('cnn_fwd', packed, None, x, num_classes, keep_masks)
 
 
-@cnn_fwd.register_fake
-def _(packed, x, num_classes, keep_masks):
-    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
-    return (x.new_empty((x.shape[0], num_classes)), x.new_empty((n_ws,)), x.new_empty((n_mask,), dtype=torch.uint8))
+@custom_op(NS + '::cnn_fwd_x3', mutates_args=(), device_types='cuda')
+def cnn_fwd_x3(packed: Tensor, packed_x3: Tensor, x: Tensor, num_classes: int, keep_masks: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """cnn_fwd with stages 2..7 on the bf16x3 image: (logits, workspace, masks) with cnn_fwd's shapes and contracts."""
+    return _cnn_fwd('cnn_fwd_x3', packed, packed_x3, x, num_classes, keep_masks)
+
+
+cnn_fwd.register_fake(lambda packed, x, num_classes, keep_masks: _cnn_fwd_fake(x, num_classes, keep_masks))
+cnn_fwd_x3.register_fake(lambda packed, packed_x3, x, num_classes, keep_masks: _cnn_fwd_fake(x, num_classes, keep_masks))
 
 
 @custom_op(NS + '::cnn_bwd_data', mutates_args=(), device_types='cuda')
 def cnn_bwd_data(packed: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
     """d loss / d x [B,3,H,W] of cnn_fwd from d loss / d logits and the forward's workspace and masks (weights frozen)."""
-    lib = _lib.load()
-    B, C = d_logits.shape
-    if masks.numel() == 0:
-        raise RuntimeError('cnn_bwd_data: the forward kept no masks (cnn_fwd with keep_masks=False)')
-    nb = lib.nerfail_cnn_bwd_scratch_bytes(B, H, W)
-    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
-    dx = torch.empty((B, 3, H, W), dtype=torch.float32, device=d_logits.device)
-    _chk(lib.nerfail_cnn_bwd_data(_lib.dev(packed), C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits), B, H, W,
-                                  _lib.dev(scratch), _lib.dev(dx), _s()))
-    return dx
+    return _cnn_bwd_data('cnn_bwd_data', packed, None, workspace, masks, d_logits, H, W)
 
 
-@cnn_bwd_data.register_fake
-def _(packed, workspace, masks, d_logits, H, W):
-    return d_logits.new_empty((d_logits.shape[0], 3, H, W))
+@custom_op(NS + '::cnn_bwd_data_x3', mutates_args=(), device_types='cuda')
+def cnn_bwd_data_x3(packed: Tensor, packed_x3: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
+    """cnn_bwd_data with stages 7..2 on the bf16x3 image."""
+    return _cnn_bwd_data('cnn_bwd_data_x3', packed, packed_x3, workspace, masks, d_logits, H, W)
+
+
+cnn_bwd_data.register_fake(lambda packed, workspace, masks, d_logits, H, W: d_logits.new_empty((d_logits.shape[0], 3, H, W)))
+cnn_bwd_data_x3.register_fake(lambda packed, packed_x3, workspace, masks, d_logits, H, W: d_logits.new_empty((d_logits.shape[0], 3, H, W)))
 
 
 @custom_op(NS + '::cnn_bwd_data_multi', mutates_args=(), device_types='cuda')
 def cnn_bwd_data_multi(packed: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
     """cnn_bwd_data for R right-hand sides of ONE cnn_fwd in one launch chain: d_logits [R,B,num_classes] ->
     [R,B,3,H,W], slice r bitwise cnn_bwd_data(..., d_logits[r], ...). workspace and masks are that forward's (B images)."""
-    lib = _lib.load()
-    if d_logits.dtype != torch.float32:
-        raise TypeError('cnn_bwd_data_multi: d_logits must be float32 (got %s)' % d_logits.dtype)
-    if d_logits.dim() != 3:
-        raise ValueError('cnn_bwd_data_multi: d_logits must be [R,B,num_classes] (got %s)' % (tuple(d_logits.shape),))
-    R, B, C = d_logits.shape
-    if masks.numel() == 0:
-        raise RuntimeError('cnn_bwd_data_multi: the forward kept no masks (cnn_fwd with keep_masks=False)')
-    nb = lib.nerfail_cnn_bwd_multi_scratch_bytes(R, B, H, W)
-    if nb == 0 or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C) or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W):
-        raise ValueError('cnn_bwd_data_multi: unsupported d_logits %s for a %d x %d forward (needs R >= 1, R * B <= 65535 and '
-                         'the workspace and masks of a forward of B images)' % (tuple(d_logits.shape), H, W))
-    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
-    dx = torch.empty((R, B, 3, H, W), dtype=torch.float32, device=d_logits.device)
-    _chk(lib.nerfail_cnn_bwd_data_multi(_lib.dev(packed), C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits, 'd_logits'), R, B, H, W,
-                                        _lib.dev(scratch), _lib.dev(dx), _s()))
-    return dx
+    return _cnn_bwd_data_multi('cnn_bwd_data_multi', packed, None, workspace, masks, d_logits, H, W)
 
 
-@cnn_bwd_data_multi.register_fake
-def _(packed, workspace, masks, d_logits, H, W):
+@custom_op(NS + '::cnn_bwd_data_multi_x3', mutates_args=(), device_types='cuda')
+def cnn_bwd_data_multi_x3(packed: Tensor, packed_x3: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
+    """cnn_bwd_data_multi with stages 7..2 on the bf16x3 image: d_logits [R,B,num_classes] -> [R,B,3,H,W], slice r bitwise
+    cnn_bwd_data_x3(..., d_logits[r], ...)."""
+    return _cnn_bwd_data_multi('cnn_bwd_data_multi_x3', packed, packed_x3, workspace, masks, d_logits, H, W)
+
+
+def _cnn_multi_fake(d_logits, H, W):
     return d_logits.new_empty((d_logits.shape[0], d_logits.shape[1], 3, H, W))
 
 
+cnn_bwd_data_multi.register_fake(lambda packed, workspace, masks, d_logits, H, W: _cnn_multi_fake(d_logits, H, W))
+cnn_bwd_data_multi_x3.register_fake(lambda packed, packed_x3, workspace, masks, d_logits, H, W: _cnn_multi_fake(d_logits, H, W))
+
+
+# autograd of cnn_fwd and cnn_fwd_x3: the inputs are (packed[, packed_x3], x, num_classes, keep_masks); the weight images come
+# first among the saved tensors. ctx.cnn_fwd_x3 (whether a bf16x3 image was saved) also is how cnn_fwd_saved() knows the node.
 def _cnn_setup(ctx, inputs, output):
-    packed, x, num_classes, keep_masks = inputs
+    *images, x, num_classes, keep_masks = inputs
     _, ws, masks = output
-    ctx.save_for_backward(packed, ws, masks)
+    ctx.save_for_backward(*images, ws, masks)
     ctx.hw = (x.shape[2], x.shape[3])
-    ctx.is_cnn_fwd = True                     # how cnn_fwd_saved() knows this node
+    ctx.cnn_fwd_x3 = len(images) == 2
     ctx.mark_non_differentiable(ws, masks)
 
 
 def _cnn_backward(ctx, g_logits, g_ws, g_masks):
-    packed, ws, masks = ctx.saved_tensors
-    if g_logits is None:
-        return None, None, None, None
-    return None, cnn_bwd_data(packed, ws, masks, g_logits.contiguous().float(), ctx.hw[0], ctx.hw[1]), None, None
+    *images, ws, masks = ctx.saved_tensors
+    dx = None
+    if g_logits is not None:
+        dx = (cnn_bwd_data_x3 if ctx.cnn_fwd_x3 else cnn_bwd_data)(*images, ws, masks, g_logits.contiguous().float(), *ctx.hw)
+    return (None,) * len(images) + (dx, None, None)
 
 
 cnn_fwd.register_autograd(_cnn_backward, setup_context=_cnn_setup)
+cnn_fwd_x3.register_autograd(_cnn_backward, setup_context=_cnn_setup)
 
 
 def cnn_fwd_saved(logits):
@@ -597,17 +663,14 @@ def cnn_fwd_saved(logits):
     is not the direct output of a differentiable cnn_fwd[_x3], or when its graph was already freed (a backward without
     retain_graph)."""
     node = getattr(logits, 'grad_fn', None)
-    if node is None or not getattr(node, 'is_cnn_fwd', False):
+    x3 = getattr(node, 'cnn_fwd_x3', None)
+    if x3 is None:
         return None
     try:
-        saved = node.saved_tensors
+        packed, *image_x3, ws, masks = node.saved_tensors
     except RuntimeError:
         return None
-    if getattr(node, 'is_cnn_x3', False):
-        packed, packed_x3, ws, masks = saved
-        return packed, ws, masks, node.hw, packed_x3
-    packed, ws, masks = saved
-    return packed, ws, masks, node.hw, None
+    return packed, ws, masks, node.hw, (image_x3[0] if x3 else None)
 
 
 def cnn_grad_layout(num_classes):
@@ -620,11 +683,8 @@ def cnn_grad_layout(num_classes):
     shapes += [(512, 1024), (512,), (num_classes, 512), (num_classes,)]
     out, o = [], 0
     for sh in shapes:
-        n = 1
-        for d in sh:
-            n *= d
         out.append((o, sh))
-        o += (n + 3) // 4 * 4
+        o += (math.prod(sh) + 3) // 4 * 4
     return out, o
 
 
@@ -684,24 +744,14 @@ class CnnTrainFn(torch.autograd.Function):
         layout, _ = cnn_grad_layout(ctx.num_classes)
         grads = []
         for i, (o, sh) in enumerate(layout):
-            n = 1
-            for d in sh:
-                n *= d
-            grads.append(d_params[o:o + n].view(sh) if ctx.needs_input_grad[2 + i] else None)
+            grads.append(d_params[o:o + math.prod(sh)].view(sh) if ctx.needs_input_grad[2 + i] else None)
         return (None, dx if need_dx else None) + tuple(grads)
 
 
 CNN_OPS = ('cnn_fwd', 'cnn_bwd_data', 'cnn_bwd_data_multi', 'cnn_bwd_weights')
 
 
-# ---- the same victim on the bf16 matrix cores (csrc/cnn_x3.hip): stages 2..7 as six bf16 products per f32 product, f32-accurate.
-# Buffers and sizes are cnn_fwd's: a workspace and masks of one family can be handed to the other family's backward.
-def _x3_image_ok(packed_x3, num_classes, what):
-    if packed_x3.dtype != torch.uint8 or packed_x3.numel() != _lib.load().nerfail_cnn_x3_packed_bytes(num_classes):
-        raise ValueError('%s: packed_x3 is not the bf16x3 image of cnn_pack_x3 (uint8, %d bytes)'
-                         % (what, _lib.load().nerfail_cnn_x3_packed_bytes(num_classes)))
-
-
+# ---- the bf16x3 weight image of the cnn_*_x3 ops above
 @custom_op(NS + '::cnn_pack_x3', mutates_args=(), device_types='cuda')
 def cnn_pack_x3(packed: Tensor, num_classes: int) -> Tensor:
     """The bf16x3 weight image (uint8 bytes; layout in include/nerfail_hip.h) split on the device from MyCNN.packed()."""
@@ -717,95 +767,6 @@ def cnn_pack_x3(packed: Tensor, num_classes: int) -> Tensor:
 def _(packed, num_classes):
     return packed.new_empty((_lib.load().nerfail_cnn_x3_packed_bytes(num_classes),), dtype=torch.uint8)
 
-
-@custom_op(NS + '::cnn_fwd_x3', mutates_args=(), device_types='cuda')
-def cnn_fwd_x3(packed: Tensor, packed_x3: Tensor, x: Tensor, num_classes: int, keep_masks: bool) -> tuple[Tensor, Tensor, Tensor]:
-    """cnn_fwd with stages 2..7 on the bf16x3 image: (logits, workspace, masks) with cnn_fwd's shapes and contracts."""
-    B, _, H, W = x.shape
-    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
-    _x3_image_ok(packed_x3, num_classes, 'cnn_fwd_x3')
-    ws = torch.empty((n_ws,), dtype=torch.float32, device=x.device)
-    masks = torch.empty((n_mask,), dtype=torch.uint8, device=x.device)
-    logits = torch.empty((B, num_classes), dtype=torch.float32, device=x.device)
-    _chk(_lib.load().nerfail_cnn_fwd_x3(_lib.dev(packed), _lib.dev(packed_x3), num_classes, _lib.dev(x, 'x'), B, H, W, _lib.dev(ws),
-                                        _lib.dev(masks) if keep_masks else None, _lib.dev(logits), _s()))
-    return logits, ws, masks
-
-
-@cnn_fwd_x3.register_fake
-def _(packed, packed_x3, x, num_classes, keep_masks):
-    n_ws, n_mask = _cnn_sizes(x, num_classes, keep_masks)
-    return (x.new_empty((x.shape[0], num_classes)), x.new_empty((n_ws,)), x.new_empty((n_mask,), dtype=torch.uint8))
-
-
-@custom_op(NS + '::cnn_bwd_data_x3', mutates_args=(), device_types='cuda')
-def cnn_bwd_data_x3(packed: Tensor, packed_x3: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
-    """cnn_bwd_data with stages 7..2 on the bf16x3 image."""
-    lib = _lib.load()
-    B, C = d_logits.shape
-    if masks.numel() == 0:
-        raise RuntimeError('cnn_bwd_data_x3: the forward kept no masks (keep_masks=False)')
-    _x3_image_ok(packed_x3, C, 'cnn_bwd_data_x3')
-    nb = lib.nerfail_cnn_bwd_scratch_bytes(B, H, W)
-    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
-    dx = torch.empty((B, 3, H, W), dtype=torch.float32, device=d_logits.device)
-    _chk(lib.nerfail_cnn_bwd_data_x3(_lib.dev(packed), _lib.dev(packed_x3), C, _lib.dev(workspace), _lib.dev(masks), _lib.dev(d_logits),
-                                     B, H, W, _lib.dev(scratch), _lib.dev(dx), _s()))
-    return dx
-
-
-@cnn_bwd_data_x3.register_fake
-def _(packed, packed_x3, workspace, masks, d_logits, H, W):
-    return d_logits.new_empty((d_logits.shape[0], 3, H, W))
-
-
-@custom_op(NS + '::cnn_bwd_data_multi_x3', mutates_args=(), device_types='cuda')
-def cnn_bwd_data_multi_x3(packed: Tensor, packed_x3: Tensor, workspace: Tensor, masks: Tensor, d_logits: Tensor, H: int, W: int) -> Tensor:
-    """cnn_bwd_data_multi with stages 7..2 on the bf16x3 image: d_logits [R,B,num_classes] -> [R,B,3,H,W], slice r bitwise
-    cnn_bwd_data_x3(..., d_logits[r], ...)."""
-    lib = _lib.load()
-    if d_logits.dtype != torch.float32:
-        raise TypeError('cnn_bwd_data_multi_x3: d_logits must be float32 (got %s)' % d_logits.dtype)
-    if d_logits.dim() != 3:
-        raise ValueError('cnn_bwd_data_multi_x3: d_logits must be [R,B,num_classes] (got %s)' % (tuple(d_logits.shape),))
-    R, B, C = d_logits.shape
-    if masks.numel() == 0:
-        raise RuntimeError('cnn_bwd_data_multi_x3: the forward kept no masks (keep_masks=False)')
-    _x3_image_ok(packed_x3, C, 'cnn_bwd_data_multi_x3')
-    nb = lib.nerfail_cnn_bwd_multi_scratch_bytes(R, B, H, W)
-    if nb == 0 or workspace.numel() * 4 != lib.nerfail_cnn_workspace_bytes(B, H, W, C) or masks.numel() != lib.nerfail_cnn_mask_bytes(B, H, W):
-        raise ValueError('cnn_bwd_data_multi_x3: unsupported d_logits %s for a %d x %d forward (needs R >= 1, R * B <= 65535 and '
-                         'the workspace and masks of a forward of B images)' % (tuple(d_logits.shape), H, W))
-    scratch = torch.empty((nb // 4,), dtype=torch.float32, device=d_logits.device)
-    dx = torch.empty((R, B, 3, H, W), dtype=torch.float32, device=d_logits.device)
-    _chk(lib.nerfail_cnn_bwd_data_multi_x3(_lib.dev(packed), _lib.dev(packed_x3), C, _lib.dev(workspace), _lib.dev(masks),
-                                           _lib.dev(d_logits, 'd_logits'), R, B, H, W, _lib.dev(scratch), _lib.dev(dx), _s()))
-    return dx
-
-
-@cnn_bwd_data_multi_x3.register_fake
-def _(packed, packed_x3, workspace, masks, d_logits, H, W):
-    return d_logits.new_empty((d_logits.shape[0], d_logits.shape[1], 3, H, W))
-
-
-def _cnn_x3_setup(ctx, inputs, output):
-    packed, packed_x3, x, num_classes, keep_masks = inputs
-    _, ws, masks = output
-    ctx.save_for_backward(packed, packed_x3, ws, masks)
-    ctx.hw = (x.shape[2], x.shape[3])
-    ctx.is_cnn_fwd = True
-    ctx.is_cnn_x3 = True                      # cnn_fwd_saved(): this node's backward family is the bf16x3 one
-    ctx.mark_non_differentiable(ws, masks)
-
-
-def _cnn_x3_backward(ctx, g_logits, g_ws, g_masks):
-    packed, packed_x3, ws, masks = ctx.saved_tensors
-    if g_logits is None:
-        return None, None, None, None, None
-    return None, None, cnn_bwd_data_x3(packed, packed_x3, ws, masks, g_logits.contiguous().float(), ctx.hw[0], ctx.hw[1]), None, None
-
-
-cnn_fwd_x3.register_autograd(_cnn_x3_backward, setup_context=_cnn_x3_setup)
 
 CNN_X3_OPS = ('cnn_pack_x3', 'cnn_fwd_x3', 'cnn_bwd_data_x3', 'cnn_bwd_data_multi_x3')
 
